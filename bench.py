@@ -1,11 +1,24 @@
 """Benchmark: block-Lanczos iterations/sec + SpMM achieved HBM GB/s vs peak
 (BASELINE.json metric), n = 10M, nnz = 1e8, b = 16, fp64, on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4] [--full] [--dump-outputs DIR]
 
 A "step" is one block-Lanczos iteration (fused SpMM pass + alpha finish +
 update pass + beta sqrtm) over the whole synthetic operator, inputs resident in
 HBM.
+
+A plain one-GPU run does only what the headline figure needs: it generates the
+operator and start block (fixed seeds: the inputs are the same from run to
+run), warms up, times one solve of K steps, checks the device error word and
+that alpha is finite, and prints the result line.  `--full` adds everything
+else this file measures or checks at N = 1: the per-class kernel breakdown and
+the roofline / MFMA objects that need it, the plain SpMM, the CPU baselines
+and the parity checks against the oracle, and the extra workloads (C2, C5, the
+C3 random-column stress case).  Without it those fields of the line are null.
+A run at N > 1 is always the full one.
+`--dump-outputs DIR` writes what the timed solve returned to its caller as
+DIR/<name>.npy (float64; rank 0's arrays): q, alpha and beta whole, and a
+fixed seeded sample of the rows of each final-state block.
 
 --config c3 (default): BASELINE config C3.  N = 1: n = 1e7, nnz = 1e8, half
   width 4096 on one GPU.  N > 1 (launched by torch.distributed.run): weak
@@ -25,9 +38,10 @@ starting `python -m torch.distributed.run --nproc-per-node N ... bench.py`
 as a child process before anything touches the GPU and relaying its line.
 
 After the timed region the run checks itself: the device error word must be
-0 (no persistent kernel abandoned a bounded spin) and, on one GPU, the first
-steps' alpha / beta / row probe / Ritz values must match the CPU oracle run on
-the same operator and start block (the same call times the CPU baseline).
+0 (no persistent kernel abandoned a bounded spin) and, on one GPU with
+`--full`, the first steps' alpha / beta / row probe / Ritz values must match
+the CPU oracle run on the same operator and start block (the same call times
+the CPU baseline).
 rank 0 prints one JSON line on stdout (native libraries' own stdout output is
 routed to stderr).
 """
@@ -255,6 +269,33 @@ def compare_run(lz, m, b, got, ref, tol_rel, ritz_tol):
     return res
 
 
+DUMP_SAMPLE_ROWS = 32768  # rows kept of each final-state block (b = 16 fp64: 4 MiB per block)
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_sample_rows(n, k=DUMP_SAMPLE_ROWS, seed=DUMP_SAMPLE_SEED):
+    """The sorted row indices --dump-outputs keeps of an n-row block: all of them
+    up to k rows, else a fixed seeded choice (the same for every run and build)."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=k))
+
+
+def dump_outputs(path, arrays, blocks):
+    """Write what the timed solve returned as <path>/<name>.npy in float64:
+    `arrays` whole (q, alpha, beta: a few KiB per step), of each n x b block in
+    `blocks` the rows dump_sample_rows names (device tensors; only those rows
+    are copied to the host)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy().astype(np.float64, copy=False))
+    for name, t in blocks.items():
+        rows = torch.from_numpy(dump_sample_rows(t.shape[0])).to(t.device)
+        np.save(os.path.join(path, name + "_rows_sample.npy"),
+                t.index_select(0, rows).cpu().numpy().astype(np.float64, copy=False))
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -267,13 +308,18 @@ def parse_args():
     ap.add_argument("--nnz-per-row", type=float, default=None)
     ap.add_argument("--halfwidth", type=int, default=None)
     ap.add_argument("--b", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also the kernel breakdown, rooflines, plain SpMM, CPU baselines, parity checks "
+                         "and the extra workloads (a run at N > 1 always does)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed solve returned as DIR/<name>.npy (float64, rank 0)")
     ap.add_argument("--unfused", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=None,
                     help="oracle iterations after the start-up step; the first is a warm-up, the "
                          "CPU baseline is the best of the rest (BASELINE.md 3: best of 5; c3 default 6, "
                          "c4 default 2: BASELINE.md reports the C4 CPU baseline at C3 scale only)")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="N = 1: skip the oracle legs (CPU baselines + parity); N > 1 always checks parity")
+                    help="N = 1 with --full: skip the oracle legs (CPU baselines + parity); N > 1 always checks parity")
     ap.add_argument("--parity-steps", type=int, default=3, help="N > 1: steps checked against the oracle")
     ap.add_argument("--spmm-reps", type=int, default=20)
     ap.add_argument("--c2-steps", type=int, default=None, help="single-vector Lanczos steps at BASELINE config 1 (0: skip)")
@@ -400,14 +446,15 @@ def main():
     lc, lc_rank = 84, 0
 
     def make_runner(exchange):
-        """(run(m), description, halo rows) for this rank's path."""
+        """(run(m), description, halo rows, device operator, final-state blocks the
+        caller receives besides q / alpha / beta) for this rank's path."""
         if not dist_path:
             Ad = lz.CsrDevice.from_host(A)
             Q0, Q1, W = (torch.zeros(n, b, **kw) for _ in range(3))
 
             def run(m):
                 h.block_lanczos_blas(Ad, Bd, m, lc, q, alpha, beta, Q0, Q1, W, fused=not args.unfused)
-            return run, "single", 0, Ad
+            return run, "single", 0, Ad, {"Q0": Q0, "Q1": Q1, "W": W}
         if exchange == "halo":
             # only the referenced off-rank rows move each step
             ccol, rcnt, hrows = lz.halo_plan(A.col, np.asarray(bounds, np.int64), rank)
@@ -419,7 +466,7 @@ def main():
 
             def run(m):
                 h.block_lanczos_halo(Ad, Bd, m, lc, lc_rank, q, alpha, beta, X0, X1)
-            return run, f"rows{world}+rccl_halo({nh} halo rows on rank {rank})", nh, Ad
+            return run, f"rows{world}+rccl_halo({nh} halo rows on rank {rank})", nh, Ad, {}
         # all-gather (north star): padded slabs, columns in the padded numbering
         n_pad = max(bounds[g + 1] - bounds[g] for g in range(world))
         pcol = lz.remap_cols_padded(A.col, np.asarray(bounds, np.int64), n_pad)
@@ -431,14 +478,14 @@ def main():
 
         def run(m):
             h.block_lanczos_dist(Ad, n_pad, n_pad * world, Bp, m, lc, lc_rank, q, alpha, beta, Q0, W, X_full)
-        return run, f"rows{world}+rccl_allgather", 0, Ad
+        return run, f"rows{world}+rccl_allgather", 0, Ad, {}
 
     if dist_path:
         uid = [lz.comm_unique_id() if rank == 0 else None]
         if world > 1:
             dist.broadcast_object_list(uid, src=0)
         h.comm_init(world, rank, uid[0])
-    run, parallelism, halo_rows, Ad = make_runner(args.exchange)
+    run, parallelism, halo_rows, Ad, state = make_runner(args.exchange)
 
     def timed(run_fn, K, W):
         """W warmup steps, then exactly K steps between barriers; max over ranks.
@@ -478,17 +525,23 @@ def main():
     be_gpu = beta[: K + 1].cpu().numpy()
     q_gpu = q[: K * b].cpu().numpy()
     spmm_ms, spmm_cnt = prof[h.PROF_SPMM_PASS]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"q": q[: K * b], "alpha": alpha[:K], "beta": beta[: K + 1]}, state)
+    # everything below the timed solve's own checks runs only with --full (always at N > 1)
+    full = args.full or world > 1
     # per-class breakdown of the other kernels from a short untimed run with every class recorded
     K_bd = min(K, 5)
-    h.prof_enable(True)
-    run(K_bd)
-    torch.cuda.synchronize()
-    upd_ms, upd_cnt = h.prof_read(h.PROF_UPDATE_PASS)
-    small_ms, _ = h.prof_read(h.PROF_SMALL)
-    gram_ms, _ = h.prof_read(h.PROF_GRAM)
-    h.prof_enable(False)
-    if h.device_error() != 0:
-        raise RuntimeError("device error word set in the breakdown run")
+    upd_ms, upd_cnt, small_ms, gram_ms = 0.0, 0, 0.0, 0.0
+    if full:
+        h.prof_enable(True)
+        run(K_bd)
+        torch.cuda.synchronize()
+        upd_ms, upd_cnt = h.prof_read(h.PROF_UPDATE_PASS)
+        small_ms, _ = h.prof_read(h.PROF_SMALL)
+        gram_ms, _ = h.prof_read(h.PROF_GRAM)
+        h.prof_enable(False)
+        if h.device_error() != 0:
+            raise RuntimeError("device error word set in the breakdown run")
 
     # ---- N > 1: the first steps against the CPU oracle on the GLOBAL operator (rank 0
     # builds it; every rank learns the verdict).  A multi-GPU line is never printed
@@ -522,7 +575,7 @@ def main():
         ex2 = "allgather" if args.exchange == "halo" else "halo"
         del run, Ad
         torch.cuda.empty_cache()
-        run2, par2, _, Ad = make_runner(ex2)
+        run2, par2, _, Ad, _ = make_runner(ex2)
         el2, _ = timed(run2, K, args.warmup)
         if h.device_error() != 0:
             raise RuntimeError(f"device error word set in the {ex2} run")
@@ -543,7 +596,7 @@ def main():
 
     # ---- plain SpMM kernel (the BASELINE headline kernel) on the same operator
     plain = None
-    if world == 1 and not dist_path and args.spmm_reps > 0:
+    if full and world == 1 and not dist_path and args.spmm_reps > 0:
         Y = torch.empty(n, b, **kw)
         h.spmm(Ad, Bd, Y)
         torch.cuda.synchronize()
@@ -591,7 +644,7 @@ def main():
     # ---- CPU oracle on the same operator and start block, rank 0, N = 1: the CPU
     # baseline (best of the timed iterations) and the bench's own parity check
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         orc = ge.load_oracle()
         m_o = min(K, 1 + max(1, args.cpu_iters))
         t_o = time.time()
@@ -619,7 +672,7 @@ def main():
 
     # ---- BASELINE config 1 (single-vector Lanczos, n=1M, nnz=1e7): an extra line
     c2 = None
-    if world == 1 and args.c2_steps > 0:
+    if full and world == 1 and args.c2_steps > 0:
         n2 = 1_000_000
         A2 = lz.gen_banded(n2, 10.0, 4096, seed)
         A2d = lz.CsrDevice.from_host(A2)
@@ -687,7 +740,7 @@ def main():
 
     # ---- BASELINE config 4 (block Lanczos b=32 fp32, power-law rows): an extra line
     c5 = None
-    if world == 1 and args.c5_steps > 0:
+    if full and world == 1 and args.c5_steps > 0:
         n5, k5 = 10_000_000, args.c5_steps
         A5 = lz.gen_powerlaw(n5, 10.0, 2.1, 100000, seed=seed, dtype=np.float32)
         A5d = lz.CsrDevice.from_host(A5)
@@ -768,7 +821,7 @@ def main():
 
     # ---- C3 stress case: uniform-random columns (half width = n), same n, nnz/row, b
     c3r = None
-    if world == 1 and not dist_path and args.rand_steps > 0:
+    if full and world == 1 and not dist_path and args.rand_steps > 0:
         kr = args.rand_steps
         Ar = lz.gen_banded(n, args.nnz_per_row, n, seed)
         Ard = lz.CsrDevice.from_host(Ar)
@@ -828,8 +881,9 @@ def main():
         roof = mfma = None
         hw = args.halfwidth
         cb = col_bytes(n, hw)
-        # the wavefront step (lz_wf.hip) has no separate update pass
-        wf = fused and spmm_cnt > 0 and upd_cnt == 0
+        # the wavefront step (lz_wf.hip) has no separate update pass: known from the breakdown
+        # run, so the step form and the roofline / MFMA objects below exist only with --full
+        wf = full and fused and spmm_cnt > 0 and upd_cnt == 0
         if fused and wf:
             # one solve of K steps: the first step pass 1 only, the others pass 2 + pass 1 (at N > 1 the
             # boundary tiles' pass 1 is a launch of its own: same bytes, more launches)
@@ -880,7 +934,7 @@ def main():
                 ent["pmc_note"] = src
             mfma = {"unit": "TFLOP/s", "peak": FP64_MFMA_PEAK_TFS, "dtype": "f64 (v_mfma_f64_16x16x4f64)",
                     "wavefront_step": ent}
-        elif fused and t_pass:
+        elif full and fused and t_pass:
             ach = fused_pass_bytes(n, A.nnz, b, cb=cb) / t_pass / 1e9
             kname, kshort = fused_kernel(A.nnz, n)
             traffic, tsrc = pmc_traffic(kshort, n, A.nnz, hw, kname)
@@ -979,6 +1033,14 @@ def main():
                 "nnz_per_s_per_gpu": round(A.nnz * K / elapsed, 1),
             },
         }
+        out["full"] = bool(full)
+        if not full:  # no breakdown run: the other classes' times and the step form are unknown
+            for k in ("update_pass", "finish_sqrtm", "gram"):
+                out["extra"]["kernel_ms_per_step"][k] = None
+            out["extra"]["kernel_ms_per_step"]["note"] = ("fused_spmm_pass: HIP events in the timed region; "
+                                                          "the others: with --full")
+            for k in ("iteration_frac_qfree_bytes", "iteration_qfree_bytes", "iteration_bytes_note", "step_form"):
+                out["extra"][k] = None
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     h.close()
     if world > 1:

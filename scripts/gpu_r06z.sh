@@ -9,6 +9,6 @@ for i in 1 2; do
   tail -1 $O/pytest_$i.log
 done
 for i in 1 2 3; do
-  timeout -k 10 400 python bench.py --no-cpu-baseline > $O/bench_$i.json 2> $O/bench_$i.err || { tail -20 $O/bench_$i.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --no-cpu-baseline > $O/bench_$i.json 2> $O/bench_$i.err || { tail -20 $O/bench_$i.err; exit 1; }
   python -c "import json;d=json.load(open('$O/bench_$i.json'));print(d['value'],d['ms_per_step'],d['roofline']['avg_ms'],d['extra']['plain_spmm']['roofline']['avg_ms'],d['extra']['c5_block32_f32_powerlaw']['iters_per_s'])"
 done

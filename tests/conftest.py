@@ -34,6 +34,12 @@ def golden():
 
 
 @pytest.fixture(scope="session")
+def golden_ref():
+    """What the reference's own host code returned (tests/golden/make_golden.py ref_host)."""
+    return np.load(os.path.join(ROOT, "tests", "golden", "golden_ref_host.npz"))
+
+
+@pytest.fixture(scope="session")
 def handle(lz):
     h = lz.Handle(0)
     yield h

@@ -5,7 +5,8 @@ random_matrix_B after the lc draw); the Lanczos outputs come from the oracle's
 CPU restatement of block_lanczos_blas / vector_lanczos, cross-checked here
 against an independent numpy restatement before anything is written.
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py            (both files)
+    python tests/golden/make_golden.py ref_host   (golden_ref_host.npz only)
 """
 import os
 import sys
@@ -122,7 +123,36 @@ def main():
     out["N3_b4_fdtd_1e6"] = oracle.fdtd_block(A3, B3, 1000000, 1.0, lc)
     np.savez_compressed(os.path.join(HERE, "golden_matrix_a.npz"), **out)
     print("wrote", os.path.join(HERE, "golden_matrix_a.npz"), len(out), "arrays")
+    ref_host()
+
+
+REF_HOST_N = (1, 2, 4, 7, 12)
+
+
+def ref_host():
+    """golden_ref_host.npz: what the reference's own host code (oracle/_ref) returns, stored
+    so the tests that pin the restated generator and the oracle SpMM to it run without the
+    reference tree: Matrix_A + mult_diagonal as ELL (data, idx) for N in REF_HOST_N, as
+    written (bug0) and after the as-run change_order(4) (bug1, in the reference's layout),
+    and Ell_matrix::spmm of the N = 10 operator on the block default_rng(0).uniform(-1, 1,
+    (n, 4)) (column-major flat, as the reference returns it)."""
+    out = {}
+    for N in REF_HOST_N:
+        for bug in (0, 1):
+            n, d, ix = oracle.ref_matrix_a(N, bool(bug))
+            out[f"N{N}_n"] = np.int64(n)
+            out[f"N{N}_bug{bug}_data"] = d
+            out[f"N{N}_bug{bug}_idx"] = ix
+    n, d, ix = oracle.ref_matrix_a(10)
+    X = np.random.default_rng(0).uniform(-1, 1, (n, 4))
+    out["N10_ell_spmm_Y"] = oracle.ref_ell_spmm(n, d, ix, X.T.ravel())
+    np.savez_compressed(os.path.join(HERE, "golden_ref_host.npz"), **out)
+    print("wrote", os.path.join(HERE, "golden_ref_host.npz"), len(out), "arrays")
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ref_host"]:  # only golden_ref_host.npz
+        assert oracle.ref_available(4), "build oracle/_ref first (make -C oracle)"
+        ref_host()
+    else:
+        main()

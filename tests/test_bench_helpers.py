@@ -66,6 +66,40 @@ def test_pmc_record_guards(tmp_path, monkeypatch):
     assert d is None and "stale" in why
 
 
+def test_dump_outputs_fixed_sample_and_float64(tmp_path):
+    """--dump-outputs: the small arrays whole, of a large block a fixed seeded
+    row sample (the same from call to call), everything float64 .npy."""
+    import torch
+    n = 3 * bench.DUMP_SAMPLE_ROWS + 5
+    rows = bench.dump_sample_rows(n)
+    assert np.array_equal(rows, bench.dump_sample_rows(n))  # the same every call
+    assert rows.size <= bench.DUMP_SAMPLE_ROWS and rows.size > bench.DUMP_SAMPLE_ROWS // 2
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < n
+    assert np.array_equal(bench.dump_sample_rows(7), np.arange(7))  # a small block is kept whole
+    W = torch.arange(n * 2, dtype=torch.float32).reshape(n, 2)
+    al = torch.arange(8, dtype=torch.float64).reshape(2, 2, 2)
+    bench.dump_outputs(str(tmp_path / "d"), {"alpha": al}, {"W": W})
+    assert sorted(os.listdir(tmp_path / "d")) == ["W_rows_sample.npy", "alpha.npy"]
+    a = np.load(tmp_path / "d" / "alpha.npy")
+    w = np.load(tmp_path / "d" / "W_rows_sample.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, al.numpy())
+    assert w.dtype == np.float64 and np.array_equal(w, W.numpy()[rows].astype(np.float64))
+
+
+def test_plain_run_is_the_default():
+    """--full is off by default; --dump-outputs takes a directory."""
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1"]
+        a = bench.parse_args()
+        assert a.full is False and a.dump_outputs is None and a.steps == 4 and a.warmup == 1
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out"]
+        a = bench.parse_args()
+        assert a.full is True and a.dump_outputs == "out"
+    finally:
+        sys.argv = old
+
+
 def test_stream_ceiling():
     s = bench.stream_ceiling(4090.8, "r2w1")
     assert s["mix"] == "r2w1" and s["GBs"] == bench.STREAM_GBS["r2w1"]

@@ -53,13 +53,18 @@ def test_oracle_final_state_vs_numpy(lz, orc, m):
     assert np.allclose(Wf, Wn, rtol=1e-8, atol=1e-10 * np.abs(Wn).max())
 
 
-def test_oracle_spmm_vs_reference_ell_spmm(lz, orc, golden):
-    """CSR SpMM restatement == the reference's host Ell_matrix::spmm (ell_matrix.hpp:287-300)."""
-    if not orc.ref_available(4):
-        pytest.skip("oracle/_ref not built")
-    n, d, ix = orc.ref_matrix_a(10)
+def test_oracle_spmm_vs_reference_ell_spmm(lz, orc, golden, golden_ref):
+    """CSR SpMM restatement == the reference's host Ell_matrix::spmm (ell_matrix.hpp:287-300):
+    its stored result (golden_ref_host.npz) and, where oracle/_ref is built, the same code
+    compiled in place, which must agree with the stored block."""
+    n = int(golden["N10_n"])
     X = np.random.default_rng(0).uniform(-1, 1, (n, 4))
-    Yref = orc.ref_ell_spmm(n, d, ix, X.T.ravel()).reshape(4, n).T
+    Yflat = golden_ref["N10_ell_spmm_Y"]
+    if orc.ref_available(4):
+        nl, d, ix = orc.ref_matrix_a(10)
+        Yl = orc.ref_ell_spmm(n, d, ix, X.T.ravel())
+        assert nl == n and np.allclose(Yl, Yflat, rtol=0, atol=1e-15 * np.abs(Yflat).max())
+    Yref = Yflat.reshape(4, n).T
     Y = orc.csr_spmm(golden_csr(lz, golden, 10), X)
     assert np.allclose(Y, Yref, rtol=0, atol=1e-15 * np.abs(Yref).max())
 
