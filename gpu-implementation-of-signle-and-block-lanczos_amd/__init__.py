@@ -36,6 +36,11 @@ HOST_LIB = os.path.join(LIB_DIR, "liblz_host.so")
 
 LZ_F64, LZ_F32 = 0, 1
 LZ_ROW_MAJOR, LZ_COL_MAJOR = 0, 1
+# lz_debug_last_kernel ids (include/lz_hip.h): SpMM kernels, their flags, dense kernels
+(LZ_K_SEG768, LZ_K_SEG1536, LZ_K_SEG1024, LZ_K_FNZ, LZ_K_BUF, LZ_K_LDS, LZ_K_ANY_B, LZ_K_CM_DIRECT,
+ LZ_K_SPMV) = range(1, 10)
+LZ_K_WIN, LZ_K_YCM, LZ_K_EPI = 0x100, 0x200, 0x400
+LZ_K_GRAM16, LZ_K_GRAM32F, LZ_K_GRAM_GEN, LZ_K_TSMM16, LZ_K_TSMM32F, LZ_K_TSMM_GEN = range(1, 7)
 
 _c_i64, _c_i32, _c_int, _c_dbl, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_double, ctypes.c_void_p
 _c_u32, _c_u64 = ctypes.c_uint32, ctypes.c_uint64
@@ -98,6 +103,7 @@ HIP_SYMBOLS = [
     ("lz_comm_abort", _c_int, [_c_vp]),
     ("lz_debug_last_split", _c_int, [_c_vp, _c_vp]),
     ("lz_debug_last_wf", _c_int, [_c_vp, ctypes.POINTER(_c_int)]),
+    ("lz_debug_last_kernel", _c_int, [_c_vp, ctypes.POINTER(_c_int)]),
     ("lz_debug_wf_plan", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp,
                                   ctypes.POINTER(_c_int)]),
     ("lz_block_lanczos_dist", _c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp,
@@ -496,6 +502,15 @@ class Handle:
         _check(self.L.lz_to_row_major(self.ptr, rows, b, _dt(Xcm), _ptr(Xcm), ld, _ptr(Y)), "lz_to_row_major")
         return Y
 
+    def to_col_major(self, X, Ycm):
+        """The column-major block viewed as Ycm (b, ld) (ld >= rows) <- X (rows, b) row-major, contiguous."""
+        rows, b = X.shape
+        if not X.is_contiguous() or Ycm.shape[0] != b or (b > 1 and Ycm.stride(1) != 1):
+            raise LanczosError("to_col_major: X (rows, b) contiguous, Ycm (b, ld) with unit inner stride")
+        ld = Ycm.stride(0) if b > 1 else Ycm.shape[1]
+        _check(self.L.lz_to_col_major(self.ptr, rows, b, _dt(X), _ptr(X), _ptr(Ycm), ld), "lz_to_col_major")
+        return Ycm
+
     def spmv(self, A: CsrDevice, x, y):
         _check(self.L.lz_csr_spmv(self.ptr, A.n, A.n_cols, A.nnz, _ptr(A.row_ptr), _ptr(A.col),
                                   _ptr(A.val), A.dtype, _ptr(x), _ptr(y)), "lz_csr_spmv")
@@ -510,6 +525,8 @@ class Handle:
     def mm_tt2(self, W, Q, R):
         """R = 0.5 (W^T Q + Q^T W) (mm_tt2_cublas, lib_utils.hpp:164-202)."""
         n, b = W.shape
+        if Q.shape != W.shape or (n > 1 and Q.stride(0) != W.stride(0)):
+            raise LanczosError("mm_tt2: W and Q must have the same shape and row stride (one ld for both)")
         _check(self.L.lz_sym_cross_gram(self.ptr, n, b, _dt(W), _ptr(W), _ptr(Q), W.stride(0), _ptr(R)),
                "lz_sym_cross_gram")
         return R
@@ -517,6 +534,8 @@ class Handle:
     def mm_ts(self, beta: float, alpha: float, Q, S, W):
         """W = beta W + alpha Q S (mm_cublas(beta, alpha, Q, S, W), lib_utils.hpp:28-51)."""
         n, b = Q.shape
+        if W.shape != Q.shape or (n > 1 and Q.stride(0) != W.stride(0)):
+            raise LanczosError("mm_ts: Q and W must have the same shape and row stride (one ld for both)")
         _check(self.L.lz_tsmm(self.ptr, n, b, _dt(Q), beta, alpha, _ptr(Q), _ptr(S), _ptr(W), W.stride(0)),
                "lz_tsmm")
         return W
@@ -527,9 +546,11 @@ class Handle:
         _check(self.L.lz_sqrtm_pair(self.ptr, b, _dt(G), _ptr(G), _ptr(beta), _ptr(beta_inv), _ptr(eigval)),
                "lz_sqrtm_pair")
 
-    def copy_row_to_vector(self, lc: int, start: int, Q, q):
-        n, b = Q.shape
-        _check(self.L.lz_copy_row(self.ptr, b, _dt(Q), _ptr(Q), Q.stride(0), LZ_ROW_MAJOR, lc, _ptr(q), start),
+    def copy_row_to_vector(self, lc: int, start: int, Q, q, layout: int = LZ_ROW_MAJOR):
+        """q[start : start + b] = row lc of Q: (rows, b) row-major, or the
+        column-major block viewed as (b, ld) when layout=LZ_COL_MAJOR."""
+        b = Q.shape[1] if layout == LZ_ROW_MAJOR else Q.shape[0]
+        _check(self.L.lz_copy_row(self.ptr, b, _dt(Q), _ptr(Q), Q.stride(0), layout, lc, _ptr(q), start),
                "lz_copy_row")
 
     def block_lanczos_blas(self, A: CsrDevice, B, m: int, lc: int, q, alpha, beta, Q0, Q1, W,
@@ -617,6 +638,12 @@ class Handle:
         v = (_c_int * 2)()
         _check(self.L.lz_debug_last_wf(self._h, v), "lz_debug_last_wf")
         return bool(v[0]), bool(v[1])
+
+    def last_kernel(self):
+        """(SpMM-family id, dense-family id) of the handle's last launches (LZ_K_*; 0: none yet)."""
+        v = (_c_int * 2)()
+        _check(self.L.lz_debug_last_kernel(self._h, v), "lz_debug_last_kernel")
+        return int(v[0]), int(v[1])
 
     def wf_plan(self, A, nx=None, xoff=0):
         """The wavefront step's plan of device operator A (test hook): (info dict,

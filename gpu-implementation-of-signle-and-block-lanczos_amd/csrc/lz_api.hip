@@ -1680,6 +1680,14 @@ int lz_debug_last_wf(lz_handle *h, int out[2])
     return LZ_OK;
 }
 
+int lz_debug_last_kernel(lz_handle *h, int out[2])
+{
+    LZ_HANDLE_CHECK(h);
+    out[0] = h->last_kernel[0];
+    out[1] = h->last_kernel[1];
+    return LZ_OK;
+}
+
 int lz_debug_wf_plan(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col_idx,
                      int64_t nx, int64_t xoff, int32_t *deps_out, int16_t *col16_out, int32_t info[8])
 {

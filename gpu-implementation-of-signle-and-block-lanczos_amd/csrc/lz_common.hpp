@@ -84,6 +84,7 @@ struct lz_handle {
     hipEvent_t ev_bd = nullptr;  // the wavefront step's second boundary launch (exchange stream) -> main
     int64_t last_split[2] = {-1, -1};  // lz_debug_last_split
     int last_wf = 0, last_wf_pre = 0;  // lz_debug_last_wf: wavefront step, pass-2-first overlap
+    int last_kernel[2] = {0, 0};       // lz_debug_last_kernel: last SpMM-family / dense-family launch (LZ_K_*)
     // lz_block_lanczos leaves Q0 = Q1 = Q_{m-1}, W = W_m as the reference does
     // (one row-local pass per solve); lz_set_final_state(h, 0) skips that pass
     int final_state = 1;

@@ -426,6 +426,7 @@ int gram_partials(lz_handle *h, int64_t n, int b, const T *X, const T *Y, int64_
         const int64_t units = f32 ? ceil_div(ceil_div(n, 16), 8) : ceil_div(ceil_div(n, 4), 8);
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(units, f32 ? h->n_cu * 2 : h->n_cu));
         const int ev_ = prof_begin(h, PROF_GRAM);
+        h->last_kernel[1] = LZ_K_GRAM16;
         if constexpr (std::is_same<T, float>::value) {
             if (X == Y)
                 hipLaunchKernelGGL((k_gram16_f32<true>), dim3(grid), dim3(512), 0, h->stream, n, X, Y, h->partials);
@@ -446,6 +447,7 @@ int gram_partials(lz_handle *h, int64_t n, int b, const T *X, const T *Y, int64_
             const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, (int64_t)64), h->n_cu * 2));
             LZ_TRY(ensure_partials(h, (size_t)grid * 1024));
             const int ev_ = prof_begin(h, PROF_GRAM);
+            h->last_kernel[1] = LZ_K_GRAM32F;
             if (X == Y)
                 hipLaunchKernelGGL(k_gram32_f32<true>, dim3(grid), dim3(256), 0, h->stream, n, X, Y, h->partials);
             else
@@ -460,6 +462,7 @@ int gram_partials(lz_handle *h, int64_t n, int b, const T *X, const T *Y, int64_
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(units, (int64_t)h->n_cu * 2));
     {
     const int ev_ = prof_begin(h, PROF_GRAM);
+    h->last_kernel[1] = LZ_K_GRAM_GEN;
     hipLaunchKernelGGL((k_gram_gen<T>), dim3(grid), dim3(256), 0, h->stream, n, b, X, Y, ld,
                        h->partials);
     prof_end(h, ev_);
@@ -1026,6 +1029,7 @@ int tsmm(lz_handle *h, int64_t n, int b, T sw, T sq, const T *Q, const T *S, T *
         const int64_t units = ceil_div(ceil_div(n, 16), 8);
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(units, h->n_cu * 2));
         const int ev_ = prof_begin(h, PROF_TSMM);
+        h->last_kernel[1] = LZ_K_TSMM16;
         hipLaunchKernelGGL((k_tsmm16_f64<T>), dim3(grid), dim3(512), 0, h->stream, n, (double)sw, (double)sq, Q, S,
                            W);
         prof_end(h, ev_);
@@ -1036,6 +1040,7 @@ int tsmm(lz_handle *h, int64_t n, int b, T sw, T sq, const T *Q, const T *S, T *
         if (b == 32 && ld == 32) {
             const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, (int64_t)128), h->n_cu * 4));
             const int ev_ = prof_begin(h, PROF_TSMM);
+            h->last_kernel[1] = LZ_K_TSMM32F;
             hipLaunchKernelGGL(k_tsmm32_f32, dim3(grid), dim3(256), 0, h->stream, n, sw, sq, Q, S, W);
             prof_end(h, ev_);
             LZ_LAUNCH_CHECK();
@@ -1046,6 +1051,7 @@ int tsmm(lz_handle *h, int64_t n, int b, T sw, T sq, const T *Q, const T *S, T *
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(units, (int64_t)h->n_cu * 4));
     {
     const int ev_ = prof_begin(h, PROF_TSMM);
+    h->last_kernel[1] = LZ_K_TSMM_GEN;
     hipLaunchKernelGGL((k_tsmm_gen<T>), dim3(grid), dim3(256), 0, h->stream, n, b, sw, sq, Q, S, W,
                        ld);
     prof_end(h, ev_);

@@ -1439,6 +1439,8 @@ static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t 
     const int64_t st = ceil_div(n, (int64_t)TR);
     LZ_ARG_CHECK(st < (1LL << 31), "too many row tiles");
     LZ_TRY(ensure_longq(h, st));
+    h->last_kernel[0] = (CAP == 768 ? LZ_K_SEG768 : CAP == 1024 ? LZ_K_SEG1024 : LZ_K_SEG1536) | (WIN ? LZ_K_WIN : 0) |
+                        (YCM ? LZ_K_YCM : 0) | (EPI ? LZ_K_EPI : 0);
     if (plan_slot >= 0) {
         LZ_ARG_CHECK(plan_slot <= 1 && (size_t)st + 2 <= h->longq_cap, "planned SpMM: no earlier queue");
         if (!h->lstream) {
@@ -1517,6 +1519,7 @@ static int launch_spmm_rm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *r
         if (fz && fz[0] == '1' && !ycm && buf_ok && ldx == B && ldy == B)
             LZ_TRY(fnz_prepare(h, n, nnz, rp, col, &fnz));
         if (fnz) {
+            h->last_kernel[0] = LZ_K_FNZ;
             rc = launch_fnz<T, B>(h, nnz, val, X, ldx, nx, Y, ldy);
         } else if (ycm) {
             if (buf_ok && !wide) rc = launch_seg<T, B, 48, 768, false, true>(h, n, rp, col, val, X, ldx, nx, Y, ldy);
@@ -1532,6 +1535,7 @@ static int launch_spmm_rm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *r
         LZ_ARG_CHECK(tiles < (1LL << 31), "too many row tiles");
         constexpr int CAP = S::RB * 32 < 1024 ? 1024 : (S::RB * 32 > 4096 ? 4096 : S::RB * 32);
         constexpr int CAP2 = CAP * 2 < 4096 ? CAP * 2 : 4096;
+        h->last_kernel[0] = (buf_ok ? LZ_K_BUF : LZ_K_LDS) | (ycm ? LZ_K_YCM : 0);
         if (ycm && buf_ok)
             hipLaunchKernelGGL((k_spmm_buf<T, B, 1024, 2, 8, true>), dim3((unsigned)tiles), dim3(256), 0, h->stream, n,
                                rp, col, val, X, ldx, nx, Y, ldy);
@@ -1648,7 +1652,20 @@ int spmm_rm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32
             const T *X, int64_t ldx, int64_t nx, T *Y, int64_t ldy, bool ycm)
 {
     LZ_ARG_CHECK(!(ycm && b == 1), "column-major Y store: b >= 2");
-    switch (b) {
+    // The tuned kernels move X and Y rows in pieces of min(16, b sizeof(T))
+    // bytes (ldv / stv / buffer loads on piece-aligned addresses) and form the
+    // gather offset with a 24-bit multiply by the row pitch.  A base or pitch
+    // off that alignment (a slice of a wider tensor with ld = b + 1), or an X
+    // pitch of 16 MiB or more, takes the element-wise kernel: any b, any
+    // pitch, 64-bit addresses.
+    bool plain = false;
+    if (!ycm && b >= 2 && (b & (b - 1)) == 0) {
+        const uint64_t piece = std::min<uint64_t>(16, (uint64_t)b * sizeof(T));
+        const uint64_t px = (uint64_t)ldx * sizeof(T), py = (uint64_t)ldy * sizeof(T);
+        plain = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) | px | py) & (piece - 1)) != 0 ||
+                px >= (1u << 24);
+    }
+    switch (plain ? 0 : b) {
     case 1:
         LZ_ARG_CHECK(ldx == 1 && ldy == 1, "b = 1 row-major needs ldx = ldy = 1");
         return spmv<T>(h, n, rp, col, val, X, Y, nnz);
@@ -1664,6 +1681,7 @@ int spmm_rm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32
         const int64_t nb = n * b;
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(nb, (int64_t)256), (int64_t)h->n_cu * 16));
         const int ev = prof_begin(h, PROF_SPMM);
+        h->last_kernel[0] = LZ_K_ANY_B;
         hipLaunchKernelGGL((k_spmm_any_b<T>), dim3(grid), dim3(256), 0, h->stream, n, b, rp, col, val, X, ldx, Y, ldy);
         prof_end(h, ev);
         LZ_LAUNCH_CHECK();
@@ -1766,6 +1784,7 @@ int spmm_cm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32
     }
     const int grid = (int)std::min<int64_t>(ceil_div(n, 256), (int64_t)h->n_cu * 8);
     if (grid <= 0) return LZ_OK;
+    h->last_kernel[0] = LZ_K_CM_DIRECT;
     hipLaunchKernelGGL((k_spmm_cm<T>), dim3(grid), dim3(256), 0, h->stream, n, rp, col, val, b,
                        X, ldx, Y, ldy);
     LZ_LAUNCH_CHECK();
@@ -1783,7 +1802,8 @@ int spmv(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, const T
     const int64_t units = ceil_div(n, 256 / lv);
     const int grid = (int)std::min<int64_t>(units, (int64_t)h->n_cu * 8);
     if (grid <= 0) return LZ_OK;
-#define LZ_SPMV_CASE(LV)                                                                       \
+    h->last_kernel[0] = LZ_K_SPMV | (lv << 16);
+#define LZ_SPMV_CASE(LV)                                                                      \
     case LV:                                                                                   \
         hipLaunchKernelGGL((k_spmv<T, LV>), dim3(grid), dim3(256), 0, h->stream, n, rp, col,  \
                            val, x, y);                                                         \

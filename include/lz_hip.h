@@ -103,8 +103,12 @@ int lz_prof_read(lz_handle *h, int kernel_class, double *ms_total, int *count);
 /* Y = A*X with b columns.  Replaces spmm(Ell_matrix<T>&, Dense_matrix<T>&,
  * Dense_matrix<T>&) (kernels/spmv_spmm.hpp:262-333, kernel :137-199) and,
  * at b == 1, spmv(Ell_matrix<T>&, Vector<T>&, Vector<T>&) (:209-260, kernel
- * :105-135).  Row-major X/Y: b in {1,2,4,8,16,32,64}; column-major: any b<=64.
- * X has n_cols rows, Y has n_rows rows. */
+ * :105-135).  Row-major X/Y: b in {1,2,4,8,16,32,64} on the tuned kernels,
+ * any other b <= 64 element-wise; column-major: any b<=64.
+ * X has n_cols rows, Y has n_rows rows.  Row-major ldx, ldy >= b (b = 1: both
+ * 1).  The tuned kernels need X, Y and both pitches on multiples of
+ * min(16, b * sizeof(T)) bytes and an X pitch under 16 MiB; any other
+ * row-major call runs element-wise (correct, slower). */
 int lz_csr_spmm(lz_handle *h, int64_t n_rows, int64_t n_cols, int64_t nnz,
                 const int64_t *row_ptr, const int32_t *col, const void *val, lz_dtype dtype,
                 int b, const void *X, int64_t ldx, lz_layout layout, void *Y, int64_t ldy);
@@ -260,6 +264,33 @@ int lz_debug_last_split(lz_handle *h, int64_t out[2]);
  * wavefront step (b = 16 fp64), out[1] = 1 when it also ran the requested rows'
  * pass 2 first and the halo exchange beside the rest of each step. */
 int lz_debug_last_wf(lz_handle *h, int out[2]);
+/* Test support: which kernel the host-side dispatchers picked.  out[0]: the
+ * handle's last SpMM-family launch (lz_csr_spmm, lz_csr_spmv, the SpMM of a
+ * b = 32 fp32 or generic-b solve), out[1]: its last Gram / tall-skinny-product
+ * launch (lz_gram, lz_sym_cross_gram, lz_tsmm and the solves that call them);
+ * 0: none yet.  SpMM ids: a kernel in the low byte, or-ed with the LZ_K_WIN /
+ * LZ_K_YCM / LZ_K_EPI flags; LZ_K_SPMV carries its lanes per row in bits 16+. */
+enum {
+    LZ_K_SEG768 = 1,    /* nnz-split tiles, 768-entry stage (128-B rows, <= 13 nnz/row) */
+    LZ_K_SEG1536 = 2,   /* ... 1536-entry stage (> 13 nnz/row) */
+    LZ_K_SEG1024 = 3,   /* ... 1024-entry stage (the beta^2 step on a heavy-tailed operator) */
+    LZ_K_FNZ = 4,       /* fixed-nnz tiles (LZ_SPMM_FNZ=1) */
+    LZ_K_BUF = 5,       /* row per lane group, buffer-addressed gather */
+    LZ_K_LDS = 6,       /* row per lane group, 64-bit addresses (X past 2 GiB / 2^24 rows) */
+    LZ_K_ANY_B = 7,     /* one thread per element: b off the tuned set, odd pitches */
+    LZ_K_CM_DIRECT = 8, /* column-major one-pass kernel */
+    LZ_K_SPMV = 9,      /* b = 1; | lanes per row << 16 */
+    LZ_K_WIN = 0x100,   /* windowed gather (X past 2 GiB / 2^24 rows) */
+    LZ_K_YCM = 0x200,   /* column-major Y store */
+    LZ_K_EPI = 0x400,   /* the beta^2 step's epilogue U = A X - Wp M */
+    LZ_K_GRAM16 = 1,    /* dense ids: b = 16 MFMA Gram (fp64 and fp32) */
+    LZ_K_GRAM32F = 2,   /* b = 32 fp32 MFMA Gram */
+    LZ_K_GRAM_GEN = 3,  /* any b, any pitch */
+    LZ_K_TSMM16 = 4,
+    LZ_K_TSMM32F = 5,
+    LZ_K_TSMM_GEN = 6
+};
+int lz_debug_last_kernel(lz_handle *h, int out[2]);
 
 /* Test hook: the wavefront step's once-per-solve plan of a CSR operator (device
  * arrays), as lz_block_lanczos would make it for these rows. deps_out (device,

@@ -25,23 +25,42 @@ def dense_of(A):
     return sp.csr_matrix((A.val.astype(np.float64), A.col, A.row_ptr), shape=(A.n, A.n))
 
 
-def check_spmm(lz, orc, h, torch, A, b, dtype, layout="row"):
+def check_spmm(lz, orc, h, torch, A, b, dtype, layout="row", expect=None, ld=None):
+    """Y = A X against the fp64 scipy product of the exact (dtype-rounded) inputs,
+    |Y - ref| <= 64 eps(dtype) (|A| |X|) per element; Y starts as NaN.
+    expect: the SpMM kernel id lz_debug_last_kernel must report afterwards.
+    ld = (ldx, ldy), row-major only: X and Y are the first b columns of wider
+    tensors; X's padding holds NaN, Y's a sentinel that must come back untouched."""
     rng = np.random.default_rng(b * 7 + A.n)
     X = rng.uniform(-1, 1, (A.n, b)).astype(dtype)
-    Ad = lz.CsrDevice.from_host(lz.CsrHost(A.n, A.row_ptr, A.col, A.val.astype(dtype)))
+    A = lz.CsrHost(A.n, A.row_ptr, A.col, A.val.astype(dtype))
+    Ad = lz.CsrDevice.from_host(A)
     M = dense_of(A)
     ref = M @ X.astype(np.float64)
     bound = abs(M) @ np.abs(X.astype(np.float64))
-    if layout == "row":
+    if layout == "row" and ld is not None:
+        ldx, ldy = ld
+        Xw = torch.full((A.n, ldx), np.nan, dtype=torch.from_numpy(X).dtype, device="cuda")
+        Xw[:, :b] = torch.from_numpy(X).cuda()
+        Yw = torch.full((A.n, ldy), 7.0, dtype=Xw.dtype, device="cuda")
+        Yw[:, :b] = np.nan
+        h.spmm(Ad, Xw[:, :b], Yw[:, :b])
+        Yw = Yw.cpu().numpy()
+        assert np.all(Yw[:, b:] == 7.0)  # padding untouched
+        Y = Yw[:, :b]
+    elif layout == "row":
         Xd = torch.from_numpy(X).cuda()
         Yd = torch.full((A.n, b), np.nan, dtype=Xd.dtype, device="cuda")
         h.spmm(Ad, Xd, Yd)
         Y = Yd.cpu().numpy()
     else:  # column-major (the reference's Dense_matrix layout): tensors (b, n)
+        assert ld is None
         Xd = torch.from_numpy(np.ascontiguousarray(X.T)).cuda()
         Yd = torch.full((b, A.n), np.nan, dtype=Xd.dtype, device="cuda")
         h.spmm(Ad, Xd, Yd, layout=lz.LZ_COL_MAJOR)
         Y = Yd.cpu().numpy().T
+    if expect is not None:
+        assert h.last_kernel()[0] == expect, (hex(h.last_kernel()[0]), hex(expect))
     tol = 64 * EPS[dtype] * bound + 1e-300
     assert np.all(np.abs(Y - ref) <= tol), f"b={b} {dtype} max err {np.max(np.abs(Y - ref))}"
     if dtype == np.float64 and layout == "row":

@@ -236,14 +236,17 @@ def test_block_f32_b32_powerlaw(lz, orc, handle, torch_cuda, monkeypatch, n, cap
 
 
 @pytest.mark.parametrize("form", ["b2", "e"])
-@pytest.mark.parametrize("n,m", [(20_011, 4), (100_003, 3), (33, 2)])
+@pytest.mark.parametrize("n,m", [(20_011, 4), (100_003, 3), (33, 2), (600_011, 2)])
 def test_block_f32_b32_ub_dma_bitwise(lz, handle, torch_cuda, monkeypatch, n, m, form):
     """The b = 32 fp32 dense passes with their operands staged through LDS by
     DMA (the default: pass UB k_fused_ub32d in the beta^2 form; passes E and U,
     k_fused_e32d / k_fused_u32d, in the pass-E form, LZ_C5_B2=0) against the
     register-operand forms (LZ_UB_DMA=0): the same products in the same order,
     so alpha, beta, q and the post-call Q0 / Q1 / W are the same bits, including
-    the ragged last strip (n not a multiple of 32) and the last step's Q store."""
+    the ragged last strip (n not a multiple of 32) and the last step's Q store.
+    n = 600,011: every block of the passes walks four strips or more, so the
+    double buffer reaches steady state (a slot refilled after its rows were
+    stored, with row stores in flight)."""
     torch = torch_cuda
     if form == "e":
         monkeypatch.setenv("LZ_C5_B2", "0")
