@@ -41,6 +41,10 @@ LZ_ROW_MAJOR, LZ_COL_MAJOR = 0, 1
  LZ_K_SPMV) = range(1, 10)
 LZ_K_WIN, LZ_K_YCM, LZ_K_EPI = 0x100, 0x200, 0x400
 LZ_K_GRAM16, LZ_K_GRAM32F, LZ_K_GRAM_GEN, LZ_K_TSMM16, LZ_K_TSMM32F, LZ_K_TSMM_GEN = range(1, 7)
+LZ_K_PGRAM16, LZ_K_PGRAM_GEN, LZ_K_PAPPLY16, LZ_K_PAPPLY_GEN = range(7, 11)
+# blocks per group of the panel Gram kernels (W is re-read once per group): b = 16 fp64 MFMA, generic
+PANEL_GROUP_16, PANEL_GROUP_GEN = 16, 4
+PANEL_MAX_BLOCKS = 64
 
 _c_i64, _c_i32, _c_int, _c_dbl, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_double, ctypes.c_void_p
 _c_u32, _c_u64 = ctypes.c_uint32, ctypes.c_uint64
@@ -84,6 +88,10 @@ HIP_SYMBOLS = [
                                   _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_block_lanczos_unfused", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int,
                                           _c_int, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lz_panel_gram", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_int, _c_vp, _c_i64, _c_vp, _c_vp]),
+    ("lz_panel_apply", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _c_dbl, _c_vp, _c_i64, _c_vp, _c_vp]),
+    ("lz_block_lanczos_reorth", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int,
+                                         _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int]),
     ("lz_vector_lanczos", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_i64,
                                    _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_fdtd_block", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp,
@@ -130,6 +138,7 @@ HOST_SYMBOLS = [
     ("lzh_sym_eig", _c_int, [_c_int, _c_vp, _c_vp, _c_vp]),
     ("lzh_assemble_T", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     ("lzh_ritz_values", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_vp]),
+    ("lzh_ritz_pairs", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     ("lzh_block_solution", _c_int, [_c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_partition_rows", _c_int, [_c_i64, _c_vp, _c_int, _c_vp]),
     ("lzh_remap_cols_padded", _c_int, [_c_i64, _c_vp, _c_int, _c_vp, _c_i64, _c_vp]),
@@ -339,6 +348,24 @@ def ritz_values(m: int, b: int, alpha: np.ndarray, beta: np.ndarray) -> np.ndarr
     host_lib().lzh_ritz_values(m, b, _p(np.ascontiguousarray(alpha, np.float64)),
                                _p(np.ascontiguousarray(beta, np.float64)), _p(r))
     return r
+
+
+def ritz_pairs(m: int, b: int, alpha: np.ndarray, beta: np.ndarray, nev: int, which: str = "largest"):
+    """Ritz pairs of Assemble_T(m, alpha, beta) (lzh_ritz_pairs): (theta[nev], S (m*b, nev),
+    resid[nev]).  which = "smallest" (theta ascending) or "largest" (theta descending);
+    beta holds m + 1 blocks with the true beta_m last (block_lanczos_reorth), and
+    resid[i] = ||beta_m S[-b:, i]||."""
+    if which not in ("smallest", "largest"):
+        raise ValueError("which must be 'smallest' or 'largest'")
+    beta = np.ascontiguousarray(beta, np.float64)
+    if beta.size != (m + 1) * b * b:
+        raise ValueError("beta must hold m + 1 blocks of b x b")
+    theta, S, resid = np.empty(nev), np.empty((m * b, nev)), np.empty(nev)
+    rc = host_lib().lzh_ritz_pairs(m, b, _p(np.ascontiguousarray(alpha, np.float64)), _p(beta), nev,
+                                   0 if which == "smallest" else 1, _p(theta), _p(S), _p(resid))
+    if rc:
+        raise LanczosError("lzh_ritz_pairs failed (1 <= nev <= m*b)")
+    return theta, S, resid
 
 
 def block_solution(m: int, b: int, T_end: float, alpha, beta, q) -> np.ndarray:
@@ -562,6 +589,74 @@ class Handle:
         _check(fn(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b, m, lc,
                   _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta), _ptr(Q0), _ptr(Q1), _ptr(W)),
                "lz_block_lanczos")
+
+    # --- kept basis: panel kernels, reorthogonalised solve, Ritz vectors -----
+    @staticmethod
+    def _panel(V, vstride: int, n: int, b: int, k: int):
+        """A basis panel is a flat tensor: block j = V[j*vstride : j*vstride + n*b] viewed (n, b)."""
+        if V.dim() != 1 or not V.is_contiguous() or V.numel() < (k - 1) * vstride + n * b:
+            raise LanczosError("a basis panel is a flat contiguous tensor of at least (k-1)*vstride + n*b elements")
+
+    def panel_gram(self, V, vstride: int, k: int, W, C):
+        """C (k, b, b) = [V_j^T W for j < k] over the first k blocks of the panel V (lz_panel_gram)."""
+        n, b = W.shape
+        self._panel(V, vstride, n, b, max(k, 1))
+        if not W.is_contiguous() or not C.is_contiguous() or C.numel() < k * b * b or C.dtype != W.dtype \
+                or V.dtype != W.dtype:
+            raise LanczosError("panel_gram: W (n, b) and C (k, b, b) contiguous, one dtype")
+        _check(self.L.lz_panel_gram(self.ptr, n, b, k, _dt(W), _ptr(V), vstride, _ptr(W), _ptr(C)), "lz_panel_gram")
+        return C
+
+    def panel_apply(self, beta: float, alpha: float, V, vstride: int, k: int, S, W):
+        """W = beta W + alpha sum_{j<k} V_j S_j, S (k, b, b) on the device (lz_panel_apply)."""
+        n, b = W.shape
+        self._panel(V, vstride, n, b, max(k, 1))
+        if not W.is_contiguous() or not S.is_contiguous() or S.numel() < k * b * b or S.dtype != W.dtype \
+                or V.dtype != W.dtype:
+            raise LanczosError("panel_apply: W (n, b) and S (k, b, b) contiguous, one dtype")
+        _check(self.L.lz_panel_apply(self.ptr, n, b, k, _dt(W), beta, alpha, _ptr(V), vstride, _ptr(S), _ptr(W)),
+               "lz_panel_apply")
+        return W
+
+    def block_lanczos_reorth(self, A: CsrDevice, B, m: int, lc: int, q, alpha, beta, V, vstride: int, W,
+                             passes: int = 2):
+        """Block Lanczos on a kept basis with `passes` rounds of full reorthogonalisation
+        per step (lz_block_lanczos_reorth).  q[m*b], alpha[m,b,b], beta[m+1,b,b] (beta[m]
+        = the true beta_m), the panel V (m blocks) and W (the final residual) are written
+        in place."""
+        n, b = B.shape
+        self._panel(V, vstride, n, b, max(m, 1))
+        _check(self.L.lz_block_lanczos_reorth(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val),
+                                              A.dtype, b, m, lc, _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta),
+                                              _ptr(V), vstride, _ptr(W), passes), "lz_block_lanczos_reorth")
+
+    def ritz_vectors(self, V, vstride: int, S, X, n: int, b: int):
+        """X = [V_0 .. V_{m-1}] S: the Ritz vectors of host coefficients S ((m*b, nev),
+        ritz_pairs) into a second block-major panel X of ceil(nev / b) blocks (same
+        vstride, n and b as V), chunk c holding columns [c*b, (c+1)*b) of the product as
+        an (n, b) block; a last chunk narrower than b is zero-padded.  One lz_panel_apply
+        (beta = 0) per chunk.  V and X are contiguous tensors of any shape (flat, or
+        (blocks, vstride))."""
+        torch = _torch()
+        S = np.ascontiguousarray(S, np.float64)
+        mb, nev = S.shape
+        if not V.is_contiguous() or not X.is_contiguous():
+            raise LanczosError("ritz_vectors: V and X must be contiguous")
+        V, X = V.view(-1), X.view(-1)
+        if mb % b:
+            raise LanczosError("ritz_vectors: S must have m*b rows")
+        m, nch = mb // b, -(-nev // b)
+        self._panel(V, vstride, n, b, m)
+        self._panel(X, vstride, n, b, nch)
+        Sp = np.zeros((nch, m, b, b))
+        for c in range(nch):
+            w = min(b, nev - c * b)
+            Sp[c, :, :, :w] = S[:, c * b:c * b + w].reshape(m, b, w)
+        Sd = torch.from_numpy(Sp).to(device=V.device, dtype=V.dtype)
+        for c in range(nch):
+            Xc = X[c * vstride:c * vstride + n * b].view(n, b)
+            self.panel_apply(0.0, 1.0, V, vstride, m, Sd[c], Xc)
+        return X
 
     def set_final_state(self, on: bool) -> None:
         """True (default): block_lanczos_blas leaves Q0 = Q1 = Q_{m-1} and W = the

@@ -162,6 +162,76 @@ static int block_lanczos_unfused(lz_handle *h, int64_t n, int64_t nnz, const int
     return LZ_OK;
 }
 
+// The same recurrence on a kept basis, with full reorthogonalisation
+// (lz_block_lanczos_reorth; the reference has no counterpart).  Q_j is stored
+// into block j of the caller's panel V (block j is the SpMM's input, so there
+// is no Q0 / Q1) and, after W -= Q_j alpha_j, `passes` rounds of classical
+// Gram-Schmidt against the whole panel follow: C = [Q_0 .. Q_j]^T W
+// (panel_gram), W -= [Q_0 .. Q_j] C (panel_apply).  beta[m] is the true beta_m
+// = sqrtm(W_m^T W_m) of the final residual; the inverse square roots live in
+// the handle's scratch.  passes = 0 issues block_lanczos_unfused's kernels on
+// the same data, then the Gram and sqrtm of beta_m.  No host synchronisation
+// between steps: the coefficient workspace and the panel Gram's slab
+// workspace are sized for m blocks before the first.
+template <typename T>
+static int block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                                const T *val, int b, int m, int64_t lc, const T *B, T *q, T *alpha, T *beta, T *V,
+                                int64_t vstride, T *W, int passes)
+{
+    const int64_t bb = (int64_t)b * b;
+    T *binv = reinterpret_cast<T *>(h->scratch + 4 * kMaxB * kMaxB);
+    if (passes > 0) {
+        // both workspaces of the reorthogonalisation, for the last step's m blocks
+        LZ_TRY(panel_gram_reserve(h, n, b, m, std::is_same<T, double>::value));
+        const size_t need = sizeof(T) * (size_t)m * bb;
+        if (need > h->coef_cap) {
+            LZ_HIP_TRY(hipStreamSynchronize(h->stream));
+            (void)hipFree(h->coef);
+            h->coef = nullptr;
+            h->coef_cap = 0;
+            LZ_HIP_TRY(hipMalloc(&h->coef, need));
+            h->coef_cap = need;
+        }
+    }
+    T *C = static_cast<T *>(h->coef);
+    auto reorth = [&](int k) -> int {
+        for (int p = 0; p < passes; ++p) {
+            LZ_TRY(panel_gram<T>(h, n, b, k, V, vstride, W, C));
+            LZ_TRY(panel_apply<T>(h, n, b, k, 1.0, -1.0, V, vstride, C, W));
+        }
+        return LZ_OK;
+    };
+    int P = 0;
+    T *Qp = nullptr, *Qj = V;
+    LZ_TRY(gram_partials<T>(h, n, b, B, B, b, &P));
+    LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, beta, binv, nullptr));      // beta_0 = sqrtm(B'B)
+    LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), B, binv, Qj, b));               // Q_0 = B beta_0^-1
+    LZ_TRY(copy_row<T>(h, b, Qj, b, 0, lc, q));
+    LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, Qj, b, n, W, b));     // W = A Q_0
+    LZ_TRY(gram_partials<T>(h, n, b, W, Qj, b, &P));
+    LZ_TRY(gram_finish<T>(h, b, P, 1, alpha));                          // alpha_0
+    LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qj, alpha, W, b));             // W -= Q_0 alpha_0
+    LZ_TRY(reorth(1));
+    for (int j = 1; j < m; ++j) {
+        T *bj = beta + j * bb, *aj = alpha + j * bb;
+        Qp = Qj;
+        Qj = V + (int64_t)j * vstride;
+        LZ_TRY(gram_partials<T>(h, n, b, W, W, b, &P));
+        LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, bj, binv, nullptr));     // beta_j = sqrtm(W'W)
+        LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), W, binv, Qj, b));           // Q_j = W beta_j^-1
+        LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, Qj, b, n, W, b)); // W = A Q_j
+        LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qp, bj, W, b));            // W -= Q_{j-1} beta_j
+        LZ_TRY(gram_partials<T>(h, n, b, W, Qj, b, &P));
+        LZ_TRY(gram_finish<T>(h, b, P, 1, aj));                         // alpha_j
+        LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qj, aj, W, b));            // W -= Q_j alpha_j
+        LZ_TRY(reorth(j + 1));
+        LZ_TRY(copy_row<T>(h, b, Qj, b, 0, lc, q + (int64_t)j * b));
+    }
+    LZ_TRY(gram_partials<T>(h, n, b, W, W, b, &P));                     // beta_m of the final residual
+    LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, beta + m * bb, binv, nullptr));
+    return LZ_OK;
+}
+
 // Fused device-resident iteration, b = 16 fp64 (lz_fused.hip), Q-free: the
 // normalised block Q_j = W_j beta_j^-1 is formed in registers where it is used
 // (pass 1: the alpha slabs and the row probe; Q_j's other two uses fold into
@@ -1328,6 +1398,7 @@ int lz_finalize(lz_handle *h)
     (void)hipFree(h->longq);
     (void)hipFree(h->cm_buf);
     (void)hipFree(h->ybuf);
+    (void)hipFree(h->coef);
     (void)hipFree(h->c16buf);
     (void)hipFree(h->wf_deps);
     (void)hipFree(h->wf_flags);
@@ -1619,6 +1690,76 @@ int lz_block_lanczos(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, co
                                          (double *)W);
     return block_lanczos_sep<float>(h, n, nnz, rp, col, (const float *)val, b, m, lc, (const float *)B, (float *)q,
                                     (float *)alpha, (float *)beta, (float *)Q0, (float *)Q1, (float *)W);
+}
+
+static int panel_args(int64_t n, int b, int k, lz_dtype dtype, const void *V, int64_t vstride)
+{
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n >= 1, "n >= 1");
+    LZ_ARG_CHECK(b >= 1 && b <= 32, "a basis panel supports 1 <= b <= 32");
+    LZ_ARG_CHECK(k >= 1 && k <= kPanelMaxK, "a basis panel holds 1 <= k <= 64 blocks");
+    LZ_ARG_CHECK(V != nullptr, "V is NULL");
+    LZ_ARG_CHECK(vstride >= n * b, "vstride >= n*b");
+    const int64_t per16 = dtype == LZ_F64 ? 2 : 4;
+    LZ_ARG_CHECK(vstride % per16 == 0 && reinterpret_cast<uintptr_t>(V) % 16 == 0,
+                 "V and vstride must be multiples of 16 bytes");
+    return LZ_OK;
+}
+
+int lz_panel_gram(lz_handle *h, int64_t n, int b, int k, lz_dtype dtype, const void *V, int64_t vstride,
+                  const void *W, void *C)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(panel_args(n, b, k, dtype, V, vstride));
+    LZ_ARG_CHECK(W && C, "W/C NULL");
+    if (dtype == LZ_F64)
+        return panel_gram<double>(h, n, b, k, (const double *)V, vstride, (const double *)W, (double *)C);
+    return panel_gram<float>(h, n, b, k, (const float *)V, vstride, (const float *)W, (float *)C);
+}
+
+int lz_panel_apply(lz_handle *h, int64_t n, int b, int k, lz_dtype dtype, double beta, double alpha, const void *V,
+                   int64_t vstride, const void *S, void *W)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(panel_args(n, b, k, dtype, V, vstride));
+    LZ_ARG_CHECK(S && W, "S/W NULL");
+    {
+        const char *v0 = (const char *)V, *w0 = (const char *)W;
+        const int64_t es = dtype == LZ_F64 ? 8 : 4;
+        LZ_ARG_CHECK(w0 + n * b * es <= v0 || w0 >= v0 + ((int64_t)(k - 1) * vstride + n * b) * es,
+                     "W must not overlap the panel");
+    }
+    if (dtype == LZ_F64)
+        return panel_apply<double>(h, n, b, k, beta, alpha, (const double *)V, vstride, (const double *)S,
+                                   (double *)W);
+    return panel_apply<float>(h, n, b, k, beta, alpha, (const float *)V, vstride, (const float *)S, (float *)W);
+}
+
+int lz_block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                            const void *val, lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q,
+                            void *alpha, void *beta, void *V, int64_t vstride, void *W, int passes)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_ARG_CHECK(m >= 1 && m <= kPanelMaxK, "the kept basis holds 1 <= m <= 64 blocks");
+    LZ_TRY(panel_args(n, b, m, dtype, V, vstride));
+    LZ_ARG_CHECK(passes >= 0 && passes <= 2, "passes in {0, 1, 2}");
+    LZ_ARG_CHECK(lc >= 0 && lc < n, "lc must be a row index");
+    LZ_ARG_CHECK(B && q && alpha && beta && W, "NULL buffer");
+    {
+        const int64_t es = dtype == LZ_F64 ? 8 : 4;
+        const char *v0 = (const char *)V, *v1 = v0 + ((int64_t)(m - 1) * vstride + n * b) * es;
+        const char *w0 = (const char *)W, *b0 = (const char *)B;
+        LZ_ARG_CHECK((w0 + n * b * es <= v0 || w0 >= v1) && (b0 + n * b * es <= v0 || b0 >= v1) && B != W,
+                     "B, W and the panel V must be distinct buffers");
+    }
+    if (dtype == LZ_F64)
+        return block_lanczos_reorth<double>(h, n, nnz, rp, col, (const double *)val, b, m, lc, (const double *)B,
+                                            (double *)q, (double *)alpha, (double *)beta, (double *)V, vstride,
+                                            (double *)W, passes);
+    return block_lanczos_reorth<float>(h, n, nnz, rp, col, (const float *)val, b, m, lc, (const float *)B,
+                                       (float *)q, (float *)alpha, (float *)beta, (float *)V, vstride, (float *)W,
+                                       passes);
 }
 
 int lz_vector_lanczos(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,

@@ -103,6 +103,8 @@ struct lz_handle {
     size_t wf_cap = 0;
     void *ybuf = nullptr;         // distributed generic-b iteration: the local SpMM result
     size_t ybuf_cap = 0;          // bytes
+    void *coef = nullptr;         // lz_block_lanczos_reorth: the panel Gram's m b x b coefficients
+    size_t coef_cap = 0;          // bytes
     void *halo = nullptr;         // lz::HaloPlan when lz_halo_init was called
     uint64_t *pairs = nullptr;    // per-16-row-strip row order by length (k_strip_pairs)
     int *longq = nullptr;         // k_spmm_seg long-tile queue: [0], [1] counts (alternate calls), [2..] tile ids

@@ -553,6 +553,33 @@ int lzh_ritz_values(int m, int b, const double *alpha, const double *beta, doubl
     return lzh_sym_eig(k, T.data(), ritz, nullptr);
 }
 
+int lzh_ritz_pairs(int m, int b, const double *alpha, const double *beta, int nev, int which, double *theta,
+                   double *S, double *resid)
+{
+    const int k = m * b;
+    if (m <= 0 || b <= 0 || !alpha || !beta || nev < 1 || nev > k || (which != 0 && which != 1) || !theta || !S)
+        return -1;
+    std::vector<double> T((size_t)k * k), ev(k), Z((size_t)k * k);
+    if (lzh_assemble_T(m, b, alpha, beta, T.data())) return -1;
+    if (lzh_sym_eig(k, T.data(), ev.data(), Z.data())) return -1;
+    const double *bm = beta + (size_t)m * b * b;  // the true beta_m of the final residual
+    for (int i = 0; i < nev; ++i) {
+        const int src = which == 0 ? i : k - 1 - i;
+        theta[i] = ev[src];
+        for (int r = 0; r < k; ++r) S[(size_t)r * nev + i] = Z[(size_t)r * k + src];
+        if (resid) {  // || A x - theta x || = || beta_m s_last || in exact arithmetic
+            double s2 = 0.0;
+            for (int r = 0; r < b; ++r) {
+                double t = 0.0;
+                for (int c = 0; c < b; ++c) t += bm[r * b + c] * Z[(size_t)((m - 1) * b + c) * k + src];
+                s2 += t * t;
+            }
+            resid[i] = std::sqrt(s2);
+        }
+    }
+    return 0;
+}
+
 int lzh_block_solution(int m, int b, double T_end, const double *alpha, const double *beta,
                        const double *q, double *solution)
 {

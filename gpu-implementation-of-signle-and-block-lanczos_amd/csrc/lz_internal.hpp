@@ -63,6 +63,22 @@ int final_state(lz_handle *h, int64_t n, int b, const T *Y, const T *Vp, const T
 template <typename T>
 int to_col_major(lz_handle *h, int64_t rows, int b, const T *src, int64_t ld, T *dst);
 
+// ---- kept-basis panel kernels (lz_basis.hip): block j of the panel is n x b
+// row-major (ld = b) at V + j * vstride elements, k <= kPanelMaxK blocks
+constexpr int kPanelMaxK = 64;
+constexpr int kPanelG16 = 16;   // blocks per group of the b = 16 fp64 MFMA Gram (W is re-read once per group)
+constexpr int kPanelGGen = 4;   // ... of the generic Gram
+// C (k b x b row-major, device): block j = V_j^T W; slabs in h->partials, folded in a fixed order
+template <typename T>
+int panel_gram(lz_handle *h, int64_t n, int b, int k, const T *V, int64_t vstride, const T *W, T *C);
+// size the slab workspace for every panel_gram over 1 .. kmax blocks of this shape (may
+// synchronise; afterwards those calls never do)
+int panel_gram_reserve(lz_handle *h, int64_t n, int b, int kmax, bool f64);
+// W = sw W + sq sum_j V_j S_j (S k b x b row-major, device); sw == 0 never reads W
+template <typename T>
+int panel_apply(lz_handle *h, int64_t n, int b, int k, double sw, double sq, const T *V, int64_t vstride, const T *S,
+                T *W);
+
 // ---- fused block-Lanczos passes, b = 16 fp64 (lz_fused.hip)
 // Q-free form: Q_j = W_j beta_j^-1 is formed in registers wherever it is used
 // and never stored.

@@ -201,6 +201,50 @@ int lz_block_lanczos_unfused(lz_handle *h, int64_t n, int64_t nnz, const int64_t
                              int64_t lc, const void *B, void *q, void *alpha, void *beta,
                              void *Q0, void *Q1, void *W);
 
+/* ---------------------------------------------- kept basis (no reference counterpart)
+ * A basis panel is a caller-owned device buffer of k blocks: block j is n x b
+ * row-major with ld = b at V + j*vstride elements, vstride >= n*b and a
+ * multiple of 16 bytes' worth of elements (V itself on 16 bytes), so every
+ * block is a valid X for lz_csr_spmm.  1 <= b <= 32, 1 <= k <= 64, fp64 or
+ * fp32.  b = 16 fp64 runs MFMA kernels, every other shape VALU kernels (fp32
+ * sums accumulate in fp64).  Both calls read the panel once; results are
+ * bitwise reproducible run to run (fixed-order two-stage fold of per-workgroup
+ * slabs, no float atomics); all addressing is 64-bit (a panel may exceed
+ * 4 GiB). */
+/* C (k*b x b row-major, device; block j = V_j^T W) */
+int lz_panel_gram(lz_handle *h, int64_t n, int b, int k, lz_dtype dtype, const void *V, int64_t vstride,
+                  const void *W, void *C);
+/* W = beta*W + alpha * sum_j V_j S_j  (S k*b x b row-major, device).  beta == 0
+ * never reads W.  W is written once; it must not overlap the panel. */
+int lz_panel_apply(lz_handle *h, int64_t n, int b, int k, lz_dtype dtype, double beta, double alpha,
+                   const void *V, int64_t vstride, const void *S, void *W);
+
+/* m <= 64 steps of block Lanczos on a kept basis with full
+ * reorthogonalisation: the recurrence and symmetric-sqrtm normalisation of
+ * lz_block_lanczos_unfused, with Q_j stored into block j of the panel V (m
+ * blocks, layout above) and, after W -= Q_j alpha_j, `passes` in {0, 1, 2}
+ * rounds of classical Gram-Schmidt against the whole kept basis, C =
+ * [Q_0..Q_j]^T W (lz_panel_gram) then W -= [Q_0..Q_j] C (lz_panel_apply).
+ * passes = 2 is the setting for eigenvector work; passes = 0 is the plain
+ * recurrence on a kept basis.  Outputs:
+ *   q[m*b], alpha[m*b*b]  as lz_block_lanczos
+ *   beta[(m+1)*b*b]       beta_j for j = 0..m.  beta[m] is the TRUE beta_m =
+ *                         sqrtm(W_m^T W_m) of the final residual (the residual
+ *                         estimate of lzh_ritz_pairs needs it) -- NOT the
+ *                         reference's inverse-square-root slot that
+ *                         lz_block_lanczos leaves there
+ *   V                     Q_0 .. Q_{m-1}
+ *   W                     the final unnormalised residual W_m
+ * B (read only), W: n x b row-major, distinct from each other and from V.
+ * Any b <= 32, fp64 or fp32, one GPU.  A rank-deficient residual block is
+ * undefined behaviour, as in the other solves.  No host synchronisation
+ * between steps (the coefficient and slab workspaces are sized for m blocks
+ * before the first, which may synchronise once). */
+int lz_block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr,
+                            const int32_t *col, const void *val, lz_dtype dtype, int b, int m,
+                            int64_t lc, const void *B, void *q, void *alpha, void *beta, void *V,
+                            int64_t vstride, void *W, int passes);
+
 /* Single-vector Lanczos.  Replaces vector_lanczos<T>(A, b, m, lc, q, alpha,
  * beta, q0, q1, w) (methods/vector_lanczos.hpp:8-67; the correct variant -- the
  * BLAS variant's axpy at :116 is a reference bug not reproduced).  alpha[m],
@@ -288,7 +332,11 @@ enum {
     LZ_K_GRAM_GEN = 3,  /* any b, any pitch */
     LZ_K_TSMM16 = 4,
     LZ_K_TSMM32F = 5,
-    LZ_K_TSMM_GEN = 6
+    LZ_K_TSMM_GEN = 6,
+    LZ_K_PGRAM16 = 7,   /* panel Gram, b = 16 fp64 MFMA (lz_panel_gram, lz_block_lanczos_reorth) */
+    LZ_K_PGRAM_GEN = 8, /* panel Gram, any other shape */
+    LZ_K_PAPPLY16 = 9,  /* panel apply, b = 16 fp64 MFMA (lz_panel_apply) */
+    LZ_K_PAPPLY_GEN = 10 /* panel apply, any other shape */
 };
 int lz_debug_last_kernel(lz_handle *h, int out[2]);
 

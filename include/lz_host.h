@@ -82,6 +82,17 @@ int lzh_sym_eig(int k, const double *A, double *eval, double *evec);
 int lzh_assemble_T(int m, int b, const double *alpha, const double *beta, double *T);
 /* Ritz values = ascending eigenvalues of T */
 int lzh_ritz_values(int m, int b, const double *alpha, const double *beta, double *ritz);
+/* Ritz pairs of T = Assemble_T(m, alpha, beta) for a solve that kept its basis
+ * (lz_block_lanczos_reorth; the reference has no counterpart): the nev
+ * smallest (which = 0, theta ascending) or largest (which = 1, theta
+ * descending) eigenvalues, their eigenvectors as the columns of S ((m*b) x nev
+ * row-major; the Ritz vectors are X = [Q_0 .. Q_{m-1}] S), and resid[i] =
+ * || beta_m S[(m-1)b : mb, i] ||_2, the residual norm || A x_i - theta_i x_i ||
+ * of an orthonormal basis.  beta holds m + 1 blocks and beta[m] must be the
+ * true beta_m of the final residual, as lz_block_lanczos_reorth returns it.
+ * resid may be NULL. */
+int lzh_ritz_pairs(int m, int b, const double *alpha, const double *beta, int nev, int which,
+                   double *theta, double *S, double *resid);
 /* solution = (expm(T_end T)[:, :b] beta_0)^T q  (test_lanczos.cu:272-286) */
 int lzh_block_solution(int m, int b, double T_end, const double *alpha, const double *beta,
                        const double *q, double *solution);
