@@ -45,6 +45,8 @@ LZ_K_PGRAM16, LZ_K_PGRAM_GEN, LZ_K_PAPPLY16, LZ_K_PAPPLY_GEN = range(7, 11)
 # blocks per group of the panel Gram kernels (W is re-read once per group): b = 16 fp64 MFMA, generic
 PANEL_GROUP_16, PANEL_GROUP_GEN = 16, 4
 PANEL_MAX_BLOCKS = 64
+LZ_K_PCOMP16, LZ_K_PCOMP_GEN = 11, 12
+PANEL_MAX_KEEP = 16  # most output blocks of one panel_compress (LZ_PANEL_MAX_KEEP)
 
 _c_i64, _c_i32, _c_int, _c_dbl, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_double, ctypes.c_void_p
 _c_u32, _c_u64 = ctypes.c_uint32, ctypes.c_uint64
@@ -92,6 +94,10 @@ HIP_SYMBOLS = [
     ("lz_panel_apply", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _c_dbl, _c_vp, _c_i64, _c_vp, _c_vp]),
     ("lz_block_lanczos_reorth", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int,
                                          _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int]),
+    ("lz_panel_compress", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_i64, _c_vp]),
+    ("lz_block_lanczos_reorth_resume", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int,
+                                                _c_int, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
+                                                _c_int]),
     ("lz_vector_lanczos", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_i64,
                                    _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_fdtd_block", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp,
@@ -139,6 +145,9 @@ HOST_SYMBOLS = [
     ("lzh_assemble_T", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     ("lzh_ritz_values", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     ("lzh_ritz_pairs", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
+    ("lzh_ritz_pairs_dense", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
+    ("lzh_restart_coeffs", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lzh_restart_fill", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     ("lzh_block_solution", _c_int, [_c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_partition_rows", _c_int, [_c_i64, _c_vp, _c_int, _c_vp]),
     ("lzh_remap_cols_padded", _c_int, [_c_i64, _c_vp, _c_int, _c_vp, _c_i64, _c_vp]),
@@ -366,6 +375,58 @@ def ritz_pairs(m: int, b: int, alpha: np.ndarray, beta: np.ndarray, nev: int, wh
     if rc:
         raise LanczosError("lzh_ritz_pairs failed (1 <= nev <= m*b)")
     return theta, S, resid
+
+
+def _which(which: str) -> int:
+    if which not in ("smallest", "largest"):
+        raise ValueError("which must be 'smallest' or 'largest'")
+    return 0 if which == "smallest" else 1
+
+
+def ritz_pairs_dense(m: int, b: int, T: np.ndarray, beta_m: np.ndarray, nev: int, which: str = "largest"):
+    """ritz_pairs for a dense symmetric projected matrix T ((m*b, m*b), what a restarted
+    solve has) and the b x b true beta_m of the final residual (lzh_ritz_pairs_dense):
+    (theta[nev], S (m*b, nev), resid[nev])."""
+    w = _which(which)
+    T = np.ascontiguousarray(T, np.float64)
+    beta_m = np.ascontiguousarray(beta_m, np.float64)
+    if T.shape != (m * b, m * b) or beta_m.size != b * b:
+        raise ValueError("T must be (m*b, m*b) and beta_m (b, b)")
+    theta, S, resid = np.empty(nev), np.empty((m * b, nev)), np.empty(nev)
+    if host_lib().lzh_ritz_pairs_dense(m, b, _p(T), _p(beta_m), nev, w, _p(theta), _p(S), _p(resid)):
+        raise LanczosError("lzh_ritz_pairs_dense failed (1 <= nev <= m*b)")
+    return theta, S, resid
+
+
+def restart_coeffs(m: int, b: int, r: int, T: np.ndarray, beta_m: np.ndarray, which: str = "largest"):
+    """The host side of a thick restart that keeps the first r*b Ritz pairs of T
+    (lzh_restart_coeffs): (theta_k[r*b], Z (r, m, b, b) in the layout of panel_compress,
+    sigma (r, b, b) for block_lanczos_reorth_resume, T_next (m*b, m*b) with diag(theta_k)
+    and the mirrored arrow block; restart_fill adds the resumed cycle's alpha / beta)."""
+    w = _which(which)
+    T = np.ascontiguousarray(T, np.float64)
+    beta_m = np.ascontiguousarray(beta_m, np.float64)
+    if T.shape != (m * b, m * b) or beta_m.size != b * b:
+        raise ValueError("T must be (m*b, m*b) and beta_m (b, b)")
+    if not 1 <= r < m:
+        raise LanczosError("lzh_restart_coeffs: 1 <= r < m")
+    theta_k, Z, sigma, Tn = np.empty(r * b), np.empty((r, m, b, b)), np.empty((r, b, b)), np.empty((m * b, m * b))
+    if host_lib().lzh_restart_coeffs(m, b, r, _p(T), _p(beta_m), w, _p(theta_k), _p(Z), _p(sigma), _p(Tn)):
+        raise LanczosError("lzh_restart_coeffs failed")
+    return theta_k, Z, sigma, Tn
+
+
+def restart_fill(r: int, m: int, b: int, alpha: np.ndarray, beta: np.ndarray, T_next: np.ndarray) -> np.ndarray:
+    """T_next (from restart_coeffs, modified in place and returned) += the block-tridiagonal
+    tail alpha_r, beta_{r+1}, alpha_{r+1}, ... of a resumed cycle (lzh_restart_fill)."""
+    alpha = np.ascontiguousarray(alpha, np.float64)
+    beta = np.ascontiguousarray(beta, np.float64)
+    if T_next.dtype != np.float64 or not T_next.flags.c_contiguous or T_next.shape != (m * b, m * b) \
+            or alpha.size < m * b * b or beta.size < m * b * b:
+        raise ValueError("T_next must be a contiguous fp64 (m*b, m*b) array; alpha, beta hold m blocks")
+    if host_lib().lzh_restart_fill(r, m, b, _p(alpha), _p(beta), _p(T_next)):
+        raise LanczosError("lzh_restart_fill failed (1 <= r < m)")
+    return T_next
 
 
 def block_solution(m: int, b: int, T_end: float, alpha, beta, q) -> np.ndarray:
@@ -657,6 +718,111 @@ class Handle:
             Xc = X[c * vstride:c * vstride + n * b].view(n, b)
             self.panel_apply(0.0, 1.0, V, vstride, m, Sd[c], Xc)
         return X
+
+    def panel_compress(self, V, vstride: int, k: int, r: int, Z, n: Optional[int] = None):
+        """In place: block c < r of the panel V = sum_{j<k} V_j Z[c][j], Z (r, k, b, b) on the
+        device (lz_panel_compress; b is Z's).  Blocks r .. k-1 and the padding between blocks
+        are not written.  n: rows of a block; default vstride / b, an unpadded panel."""
+        if Z.dim() != 4 or Z.shape[2] != Z.shape[3] or not Z.is_contiguous() or Z.dtype != V.dtype \
+                or (k >= 1 and r >= 1 and tuple(Z.shape[:2]) != (r, k)):
+            raise LanczosError("panel_compress: Z (r, k, b, b) contiguous, of the panel's dtype")
+        b = Z.shape[2]
+        if n is None:
+            if vstride % b:
+                raise LanczosError("panel_compress: pass n for a padded panel (vstride is no multiple of b)")
+            n = vstride // b
+        self._panel(V, vstride, n, b, max(k, 1))
+        _check(self.L.lz_panel_compress(self.ptr, n, b, k, r, _dt(V), _ptr(V), vstride, _ptr(Z)), "lz_panel_compress")
+        return V
+
+    def block_lanczos_reorth_resume(self, A: CsrDevice, r: int, m: int, lc: int, sigma, q, alpha, beta, V,
+                                    vstride: int, W, passes: int = 2):
+        """Steps r .. m-1 of block_lanczos_reorth on a thick-restarted basis
+        (lz_block_lanczos_reorth_resume): blocks 0 .. r-1 of V hold the kept Ritz blocks
+        (panel_compress), W the previous cycle's residual, sigma (r, b, b) the device copy of
+        restart_coeffs' sigma.  Writes alpha[r:], beta[r:], q[r*b:], blocks r .. m-1 and W."""
+        n, b = W.shape
+        self._panel(V, vstride, n, b, max(m, 1))
+        if not sigma.is_contiguous() or sigma.numel() < max(r, 0) * b * b or sigma.dtype != W.dtype \
+                or V.dtype != W.dtype or not W.is_contiguous():
+            raise LanczosError("block_lanczos_reorth_resume: W (n, b) and sigma (r, b, b) contiguous, one dtype")
+        _check(self.L.lz_block_lanczos_reorth_resume(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val),
+                                                     A.dtype, b, r, m, lc, _ptr(sigma), _ptr(q), _ptr(alpha),
+                                                     _ptr(beta), _ptr(V), vstride, _ptr(W), passes),
+               "lz_block_lanczos_reorth_resume")
+
+    def eigsh(self, A: CsrDevice, nev: int, which: str = "largest", b: int = 16, m: Optional[int] = None,
+              keep: Optional[int] = None, tol: float = 1e-10, max_cycles: int = 100, B=None, lc: int = 0,
+              passes: int = 2):
+        """The nev outermost eigenpairs of A by thick-restart block Lanczos in a fixed panel
+        of m blocks.  Cycle 1 is block_lanczos_reorth from B (default uniform_B); every later
+        cycle keeps the first keep*b Ritz pairs (restart_coeffs), compresses the panel onto
+        them in place (panel_compress) and resumes (block_lanczos_reorth_resume).  It stops
+        when the nev wanted pairs all have resid <= tol * max|theta| (ritz_pairs_dense; the
+        maximum over every Ritz value of T, the cycle's estimate of ||A||_2), or after
+        max_cycles cycles (converged = False, no exception).  One more panel_compress
+        leaves the nev Ritz vectors in the first ceil(nev / b) blocks of the panel, the last
+        zero-padded.  keep * b >= nev, keep <= PANEL_MAX_KEEP, keep < m <= PANEL_MAX_BLOCKS;
+        default keep: the smallest with keep * b >= nev + b, clipped to those limits; default
+        m: twice that, at least 4.  The solve's precision is A's.  Device memory that scales with n: the
+        panel, W and B.  Returns a dict: theta[nev], resid[nev], V (the panel, flat), vstride,
+        cycles, n_spmm, converged, history (the largest wanted residual of each cycle), scale
+        (the last cycle's max|theta|)."""
+        torch = _torch()
+        _which(which)
+        n = A.n
+        tdt = A.val.dtype
+        want = -(-(nev + b) // b)  # the smallest keep with keep * b >= nev + b
+        if m is None:
+            m = min(PANEL_MAX_BLOCKS, max(4, 2 * want))
+        r = min(want, PANEL_MAX_KEEP, m - 1) if keep is None else keep
+        if nev < 1 or r * b < nev:
+            raise LanczosError(f"eigsh: keep * b = {r * b} < nev = {nev}")
+        if r >= m:
+            raise LanczosError(f"eigsh: keep = {r} >= m = {m}")
+        if r > PANEL_MAX_KEEP or m > PANEL_MAX_BLOCKS or r < 1:
+            raise LanczosError(f"eigsh: 1 <= keep <= {PANEL_MAX_KEEP} and m <= {PANEL_MAX_BLOCKS}")
+        per16 = 16 // A.val.element_size()
+        vstride = -(-n * b // per16) * per16
+        kw = dict(dtype=tdt, device=A.val.device)
+        if B is None:
+            B = torch.from_numpy(uniform_B(n, b, dtype=np.float64 if tdt == torch.float64 else np.float32)).to(A.val.device)
+        V = torch.zeros(m * vstride, **kw)
+        W = torch.empty(n, b, **kw)
+        q, al, be = torch.zeros(m * b, **kw), torch.zeros(m, b, b, **kw), torch.zeros(m + 1, b, b, **kw)
+        self.block_lanczos_reorth(A, B, m, lc, q, al, be, V, vstride, W, passes=passes)
+        n_spmm, cycles, history, converged = m, 1, [], False
+        f64 = lambda t: t.cpu().numpy().astype(np.float64)
+        alpha, beta = f64(al), f64(be)
+        T = Assemble_T(m, b, alpha, beta[:m])
+        while True:
+            theta, S, resid = ritz_pairs_dense(m, b, T, beta[m], m * b, which)
+            scale = float(np.abs(theta).max())
+            theta, S, resid = theta[:nev], S[:, :nev], resid[:nev]
+            history.append(float(resid.max()))
+            converged = bool(resid.max() <= tol * scale)
+            if converged or cycles >= max_cycles:
+                break
+            _, Z, sigma, T = restart_coeffs(m, b, r, T, beta[m], which)
+            self.panel_compress(V, vstride, m, r, torch.from_numpy(Z).to(**kw), n=n)
+            # row lc of Y = P Z_k
+            Zk = Z.transpose(1, 2, 0, 3).reshape(m * b, r * b)
+            q[:r * b] = torch.from_numpy(f64(q) @ Zk).to(**kw)
+            self.block_lanczos_reorth_resume(A, r, m, lc, torch.from_numpy(sigma).to(**kw), q, al, be, V, vstride,
+                                             W, passes=passes)
+            alpha, beta = f64(al), f64(be)
+            restart_fill(r, m, b, alpha, beta, T)
+            n_spmm += m - r
+            cycles += 1
+        # the wanted Ritz vectors, in place, into the first ceil(nev / b) blocks
+        nch = -(-nev // b)
+        Zx = np.zeros((nch, m, b, b))
+        for c in range(nch):
+            w = min(b, nev - c * b)
+            Zx[c, :, :, :w] = S[:, c * b:c * b + w].reshape(m, b, w)
+        self.panel_compress(V, vstride, m, nch, torch.from_numpy(Zx).to(**kw), n=n)
+        return dict(theta=theta, resid=resid, V=V, vstride=vstride, cycles=cycles, n_spmm=n_spmm,
+                    converged=converged, history=history, scale=scale)
 
     def set_final_state(self, on: bool) -> None:
         """True (default): block_lanczos_blas leaves Q0 = Q1 = Q_{m-1} and W = the

@@ -173,49 +173,51 @@ static int block_lanczos_unfused(lz_handle *h, int64_t n, int64_t nnz, const int
 // the same data, then the Gram and sqrtm of beta_m.  No host synchronisation
 // between steps: the coefficient workspace and the panel Gram's slab
 // workspace are sized for m blocks before the first.
+// Both workspaces of the reorthogonalisation, for the last step's m blocks (may
+// synchronise; the steps then never do).
 template <typename T>
-static int block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
-                                const T *val, int b, int m, int64_t lc, const T *B, T *q, T *alpha, T *beta, T *V,
-                                int64_t vstride, T *W, int passes)
+static int reorth_reserve(lz_handle *h, int64_t n, int b, int m, int passes)
+{
+    if (passes <= 0) return LZ_OK;
+    LZ_TRY(panel_gram_reserve(h, n, b, m, std::is_same<T, double>::value));
+    const size_t need = sizeof(T) * (size_t)m * b * b;
+    if (need > h->coef_cap) {
+        LZ_HIP_TRY(hipStreamSynchronize(h->stream));
+        (void)hipFree(h->coef);
+        h->coef = nullptr;
+        h->coef_cap = 0;
+        LZ_HIP_TRY(hipMalloc(&h->coef, need));
+        h->coef_cap = need;
+    }
+    return LZ_OK;
+}
+
+// `passes` rounds of classical Gram-Schmidt of W against the first k blocks
+template <typename T>
+static int reorth_rounds(lz_handle *h, int64_t n, int b, int k, const T *V, int64_t vstride, T *W, int passes)
+{
+    T *C = static_cast<T *>(h->coef);
+    for (int p = 0; p < passes; ++p) {
+        LZ_TRY(panel_gram<T>(h, n, b, k, V, vstride, W, C));
+        LZ_TRY(panel_apply<T>(h, n, b, k, 1.0, -1.0, V, vstride, C, W));
+    }
+    return LZ_OK;
+}
+
+// Steps j0 .. m - 1 (j0 >= 1; block j0 - 1 holds Q_{j0-1}, W the residual of
+// step j0 - 1), then beta_m of the final residual: the part a first cycle and
+// a resumed one share.
+template <typename T>
+static int reorth_steps(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val,
+                        int b, int j0, int m, int64_t lc, T *q, T *alpha, T *beta, T *V, int64_t vstride, T *W,
+                        int passes)
 {
     const int64_t bb = (int64_t)b * b;
     T *binv = reinterpret_cast<T *>(h->scratch + 4 * kMaxB * kMaxB);
-    if (passes > 0) {
-        // both workspaces of the reorthogonalisation, for the last step's m blocks
-        LZ_TRY(panel_gram_reserve(h, n, b, m, std::is_same<T, double>::value));
-        const size_t need = sizeof(T) * (size_t)m * bb;
-        if (need > h->coef_cap) {
-            LZ_HIP_TRY(hipStreamSynchronize(h->stream));
-            (void)hipFree(h->coef);
-            h->coef = nullptr;
-            h->coef_cap = 0;
-            LZ_HIP_TRY(hipMalloc(&h->coef, need));
-            h->coef_cap = need;
-        }
-    }
-    T *C = static_cast<T *>(h->coef);
-    auto reorth = [&](int k) -> int {
-        for (int p = 0; p < passes; ++p) {
-            LZ_TRY(panel_gram<T>(h, n, b, k, V, vstride, W, C));
-            LZ_TRY(panel_apply<T>(h, n, b, k, 1.0, -1.0, V, vstride, C, W));
-        }
-        return LZ_OK;
-    };
     int P = 0;
-    T *Qp = nullptr, *Qj = V;
-    LZ_TRY(gram_partials<T>(h, n, b, B, B, b, &P));
-    LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, beta, binv, nullptr));      // beta_0 = sqrtm(B'B)
-    LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), B, binv, Qj, b));               // Q_0 = B beta_0^-1
-    LZ_TRY(copy_row<T>(h, b, Qj, b, 0, lc, q));
-    LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, Qj, b, n, W, b));     // W = A Q_0
-    LZ_TRY(gram_partials<T>(h, n, b, W, Qj, b, &P));
-    LZ_TRY(gram_finish<T>(h, b, P, 1, alpha));                          // alpha_0
-    LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qj, alpha, W, b));             // W -= Q_0 alpha_0
-    LZ_TRY(reorth(1));
-    for (int j = 1; j < m; ++j) {
+    for (int j = j0; j < m; ++j) {
         T *bj = beta + j * bb, *aj = alpha + j * bb;
-        Qp = Qj;
-        Qj = V + (int64_t)j * vstride;
+        T *Qp = V + (int64_t)(j - 1) * vstride, *Qj = V + (int64_t)j * vstride;
         LZ_TRY(gram_partials<T>(h, n, b, W, W, b, &P));
         LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, bj, binv, nullptr));     // beta_j = sqrtm(W'W)
         LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), W, binv, Qj, b));           // Q_j = W beta_j^-1
@@ -224,12 +226,62 @@ static int block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int6
         LZ_TRY(gram_partials<T>(h, n, b, W, Qj, b, &P));
         LZ_TRY(gram_finish<T>(h, b, P, 1, aj));                         // alpha_j
         LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qj, aj, W, b));            // W -= Q_j alpha_j
-        LZ_TRY(reorth(j + 1));
+        LZ_TRY(reorth_rounds<T>(h, n, b, j + 1, V, vstride, W, passes));
         LZ_TRY(copy_row<T>(h, b, Qj, b, 0, lc, q + (int64_t)j * b));
     }
     LZ_TRY(gram_partials<T>(h, n, b, W, W, b, &P));                     // beta_m of the final residual
     LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, beta + m * bb, binv, nullptr));
     return LZ_OK;
+}
+
+template <typename T>
+static int block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                                const T *val, int b, int m, int64_t lc, const T *B, T *q, T *alpha, T *beta, T *V,
+                                int64_t vstride, T *W, int passes)
+{
+    T *binv = reinterpret_cast<T *>(h->scratch + 4 * kMaxB * kMaxB);
+    LZ_TRY(reorth_reserve<T>(h, n, b, m, passes));
+    int P = 0;
+    T *Qj = V;
+    LZ_TRY(gram_partials<T>(h, n, b, B, B, b, &P));
+    LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, beta, binv, nullptr));      // beta_0 = sqrtm(B'B)
+    LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), B, binv, Qj, b));               // Q_0 = B beta_0^-1
+    LZ_TRY(copy_row<T>(h, b, Qj, b, 0, lc, q));
+    LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, Qj, b, n, W, b));     // W = A Q_0
+    LZ_TRY(gram_partials<T>(h, n, b, W, Qj, b, &P));
+    LZ_TRY(gram_finish<T>(h, b, P, 1, alpha));                          // alpha_0
+    LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qj, alpha, W, b));             // W -= Q_0 alpha_0
+    LZ_TRY(reorth_rounds<T>(h, n, b, 1, V, vstride, W, passes));
+    return reorth_steps<T>(h, n, nnz, rp, col, val, b, 1, m, lc, q, alpha, beta, V, vstride, W, passes);
+}
+
+// A cycle on a thick-restarted basis (lz_block_lanczos_reorth_resume): blocks
+// 0 .. r - 1 hold the kept Ritz blocks Y, W the previous cycle's residual.  With
+// A Y = Y Theta + Q_r Sigma, step r subtracts Y Sigma^T = sum_i Y_i S_i (sigma
+// holds the S_i, so this is one panel_apply over the r kept blocks) where an
+// ordinary step subtracts Q_{j-1} beta_j; from step r + 1 on the recurrence is
+// the three-term one again.
+template <typename T>
+static int block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                                       const T *val, int b, int r, int m, int64_t lc, const T *sigma, T *q,
+                                       T *alpha, T *beta, T *V, int64_t vstride, T *W, int passes)
+{
+    const int64_t bb = (int64_t)b * b;
+    T *binv = reinterpret_cast<T *>(h->scratch + 4 * kMaxB * kMaxB);
+    LZ_TRY(reorth_reserve<T>(h, n, b, m, passes));
+    int P = 0;
+    T *br = beta + r * bb, *ar = alpha + r * bb, *Qr = V + (int64_t)r * vstride;
+    LZ_TRY(gram_partials<T>(h, n, b, W, W, b, &P));
+    LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, br, binv, nullptr));         // beta_r = sqrtm(W'W)
+    LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), W, binv, Qr, b));               // Q_r = W beta_r^-1
+    LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, Qr, b, n, W, b));     // W = A Q_r
+    LZ_TRY(panel_apply<T>(h, n, b, r, 1.0, -1.0, V, vstride, sigma, W)); // W -= sum_i Y_i S_i
+    LZ_TRY(gram_partials<T>(h, n, b, W, Qr, b, &P));
+    LZ_TRY(gram_finish<T>(h, b, P, 1, ar));                             // alpha_r
+    LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qr, ar, W, b));                // W -= Q_r alpha_r
+    LZ_TRY(reorth_rounds<T>(h, n, b, r + 1, V, vstride, W, passes));
+    LZ_TRY(copy_row<T>(h, b, Qr, b, 0, lc, q + (int64_t)r * b));
+    return reorth_steps<T>(h, n, nnz, rp, col, val, b, r + 1, m, lc, q, alpha, beta, V, vstride, W, passes);
 }
 
 // Fused device-resident iteration, b = 16 fp64 (lz_fused.hip), Q-free: the
@@ -1760,6 +1812,47 @@ int lz_block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t 
     return block_lanczos_reorth<float>(h, n, nnz, rp, col, (const float *)val, b, m, lc, (const float *)B,
                                        (float *)q, (float *)alpha, (float *)beta, (float *)V, vstride, (float *)W,
                                        passes);
+}
+
+int lz_panel_compress(lz_handle *h, int64_t n, int b, int k, int r, lz_dtype dtype, void *V, int64_t vstride,
+                      const void *Z)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(panel_args(n, b, k, dtype, V, vstride));
+    LZ_ARG_CHECK(r >= 1 && r <= k, "panel_compress keeps 1 <= r <= k blocks");
+    LZ_ARG_CHECK(r <= kPanelMaxKeep, "panel_compress keeps at most LZ_PANEL_MAX_KEEP = 16 blocks");
+    LZ_ARG_CHECK(Z != nullptr, "Z is NULL");
+    if (dtype == LZ_F64) return panel_compress<double>(h, n, b, k, r, (double *)V, vstride, (const double *)Z);
+    return panel_compress<float>(h, n, b, k, r, (float *)V, vstride, (const float *)Z);
+}
+
+int lz_block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                                   const void *val, lz_dtype dtype, int b, int r, int m, int64_t lc,
+                                   const void *sigma, void *q, void *alpha, void *beta, void *V, int64_t vstride,
+                                   void *W, int passes)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_ARG_CHECK(m >= 1 && m <= kPanelMaxK, "the kept basis holds 1 <= m <= 64 blocks");
+    LZ_ARG_CHECK(r >= 1 && r < m, "a resumed solve keeps 1 <= r < m blocks");
+    LZ_TRY(panel_args(n, b, m, dtype, V, vstride));
+    LZ_ARG_CHECK(passes >= 0 && passes <= 2, "passes in {0, 1, 2}");
+    LZ_ARG_CHECK(lc >= 0 && lc < n, "lc must be a row index");
+    LZ_ARG_CHECK(sigma != nullptr, "sigma is NULL");
+    LZ_ARG_CHECK(q && alpha && beta && W, "NULL buffer");
+    {
+        const int64_t es = dtype == LZ_F64 ? 8 : 4;
+        const char *v0 = (const char *)V, *v1 = v0 + ((int64_t)(m - 1) * vstride + n * b) * es;
+        const char *w0 = (const char *)W;
+        LZ_ARG_CHECK(w0 + n * b * es <= v0 || w0 >= v1, "W and the panel V must be distinct buffers");
+    }
+    if (dtype == LZ_F64)
+        return block_lanczos_reorth_resume<double>(h, n, nnz, rp, col, (const double *)val, b, r, m, lc,
+                                                   (const double *)sigma, (double *)q, (double *)alpha,
+                                                   (double *)beta, (double *)V, vstride, (double *)W, passes);
+    return block_lanczos_reorth_resume<float>(h, n, nnz, rp, col, (const float *)val, b, r, m, lc,
+                                              (const float *)sigma, (float *)q, (float *)alpha, (float *)beta,
+                                              (float *)V, vstride, (float *)W, passes);
 }
 
 int lz_vector_lanczos(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,

@@ -559,10 +559,21 @@ int lzh_ritz_pairs(int m, int b, const double *alpha, const double *beta, int ne
     const int k = m * b;
     if (m <= 0 || b <= 0 || !alpha || !beta || nev < 1 || nev > k || (which != 0 && which != 1) || !theta || !S)
         return -1;
-    std::vector<double> T((size_t)k * k), ev(k), Z((size_t)k * k);
+    std::vector<double> T((size_t)k * k);
     if (lzh_assemble_T(m, b, alpha, beta, T.data())) return -1;
-    if (lzh_sym_eig(k, T.data(), ev.data(), Z.data())) return -1;
-    const double *bm = beta + (size_t)m * b * b;  // the true beta_m of the final residual
+    // the true beta_m of the final residual is the last block of beta
+    return lzh_ritz_pairs_dense(m, b, T.data(), beta + (size_t)m * b * b, nev, which, theta, S, resid);
+}
+
+int lzh_ritz_pairs_dense(int m, int b, const double *T, const double *bm, int nev, int which, double *theta,
+                         double *S, double *resid)
+{
+    const int k = m * b;
+    if (m <= 0 || b <= 0 || !T || nev < 1 || nev > k || (which != 0 && which != 1) || !theta || !S ||
+        (resid && !bm))
+        return -1;
+    std::vector<double> ev(k), Z((size_t)k * k);
+    if (lzh_sym_eig(k, T, ev.data(), Z.data())) return -1;
     for (int i = 0; i < nev; ++i) {
         const int src = which == 0 ? i : k - 1 - i;
         theta[i] = ev[src];
@@ -575,6 +586,66 @@ int lzh_ritz_pairs(int m, int b, const double *alpha, const double *beta, int ne
                 s2 += t * t;
             }
             resid[i] = std::sqrt(s2);
+        }
+    }
+    return 0;
+}
+
+// Thick restart (Wu & Simon), block form.  With A P = P T + W E_m^T and
+// T = Z Theta Z^T, keeping the first r b pairs Z_k gives Y = P Z_k with
+// A Y = Y Theta_k + Q_r Sigma, Q_r = W beta_m^-1, Sigma = beta_m Z_k[last b rows, :].
+int lzh_restart_coeffs(int m, int b, int r, const double *T, const double *bm, int which, double *theta_k,
+                       double *Z, double *sigma, double *T_next)
+{
+    const int k = m * b, rb = r * b;
+    if (m <= 0 || b <= 0 || r < 1 || r >= m || !T || !bm || (which != 0 && which != 1) || !theta_k || !Z ||
+        !sigma || !T_next)
+        return -1;
+    std::vector<double> ev(k), E((size_t)k * k), Sg((size_t)b * rb);
+    if (lzh_sym_eig(k, T, ev.data(), E.data())) return -1;
+    auto src = [&](int i) { return which == 0 ? i : k - 1 - i; };
+    for (int i = 0; i < rb; ++i) theta_k[i] = ev[src(i)];
+    // compress layout (r, m, b, b): Z[c][j] takes block j of the panel into output block c
+    for (int c = 0; c < r; ++c)
+        for (int j = 0; j < m; ++j)
+            for (int i = 0; i < b; ++i)
+                for (int cc = 0; cc < b; ++cc)
+                    Z[(((size_t)c * m + j) * b + i) * b + cc] = E[(size_t)(j * b + i) * k + src(c * b + cc)];
+    for (int p = 0; p < b; ++p)
+        for (int i = 0; i < rb; ++i) {
+            double s = 0.0;
+            for (int c = 0; c < b; ++c) s += bm[p * b + c] * E[(size_t)((m - 1) * b + c) * k + src(i)];
+            Sg[(size_t)p * rb + i] = s;
+        }
+    // S_i = Sigma[:, i b : (i + 1) b]^T, the (r, b, b) operand of the resumed step's panel apply
+    for (int i = 0; i < r; ++i)
+        for (int p = 0; p < b; ++p)
+            for (int q = 0; q < b; ++q) sigma[((size_t)i * b + p) * b + q] = Sg[(size_t)q * rb + i * b + p];
+    std::fill(T_next, T_next + (size_t)k * k, 0.0);
+    for (int i = 0; i < rb; ++i) T_next[(size_t)i * k + i] = theta_k[i];
+    for (int p = 0; p < b; ++p)
+        for (int i = 0; i < rb; ++i) {
+            T_next[(size_t)(rb + p) * k + i] = Sg[(size_t)p * rb + i];
+            T_next[(size_t)i * k + rb + p] = Sg[(size_t)p * rb + i];
+        }
+    return 0;
+}
+
+int lzh_restart_fill(int r, int m, int b, const double *alpha, const double *beta, double *T_next)
+{
+    const int k = m * b;
+    if (m <= 0 || b <= 0 || r < 1 || r >= m || !alpha || !beta || !T_next) return -1;
+    for (int blk = r; blk < m; ++blk) {  // (the blocks of assemble_T, from block r on)
+        const double *a = alpha + (size_t)blk * b * b;
+        for (int p = 0; p < b; ++p)
+            for (int c = 0; c < b; ++c) T_next[(size_t)(blk * b + p) * k + blk * b + c] = a[p * b + c];
+        if (blk > r) {
+            const double *bt = beta + (size_t)blk * b * b;
+            for (int p = 0; p < b; ++p)
+                for (int c = 0; c < b; ++c) {
+                    T_next[(size_t)((blk - 1) * b + p) * k + blk * b + c] = bt[p * b + c];
+                    T_next[(size_t)(blk * b + c) * k + (blk - 1) * b + p] = bt[p * b + c];
+                }
         }
     }
     return 0;

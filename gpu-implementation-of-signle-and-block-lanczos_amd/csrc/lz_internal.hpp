@@ -78,6 +78,11 @@ int panel_gram_reserve(lz_handle *h, int64_t n, int b, int kmax, bool f64);
 template <typename T>
 int panel_apply(lz_handle *h, int64_t n, int b, int k, double sw, double sq, const T *V, int64_t vstride, const T *S,
                 T *W);
+// in place: block c < r of the panel = sum_{j < k} V_j Z[c][j] (Z (r, k, b, b) row-major, device),
+// r <= kPanelMaxKeep; blocks r .. k - 1 and the padding between blocks are not written
+constexpr int kPanelMaxKeep = 16;
+template <typename T>
+int panel_compress(lz_handle *h, int64_t n, int b, int k, int r, T *V, int64_t vstride, const T *Z);
 
 // ---- fused block-Lanczos passes, b = 16 fp64 (lz_fused.hip)
 // Q-free form: Q_j = W_j beta_j^-1 is formed in registers wherever it is used

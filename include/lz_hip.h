@@ -218,6 +218,18 @@ int lz_panel_gram(lz_handle *h, int64_t n, int b, int k, lz_dtype dtype, const v
  * never reads W.  W is written once; it must not overlap the panel. */
 int lz_panel_apply(lz_handle *h, int64_t n, int b, int k, lz_dtype dtype, double beta, double alpha,
                    const void *V, int64_t vstride, const void *S, void *W);
+/* In-place compress of the panel: block c < r becomes sum_{j<k} V_j Z[c][j].
+ * Z (device, (r, k, b, b) row-major): Z[c][j] is the b x b block that takes
+ * V_j into output block c.  1 <= r <= k <= 64 and r <= LZ_PANEL_MAX_KEEP.
+ * Blocks r .. k-1 and the padding between blocks (vstride > n*b) are not
+ * written.  The panel is read once and the r kept blocks are written once,
+ * (k + r) n b s bytes, with no second panel and no workspace: the owner of a
+ * row tile reads the tile's rows of all k blocks before it stores any output.
+ * b = 16 fp64 runs on the f64 MFMA, every other shape a VALU kernel (fp64 sums,
+ * rounded once on store).  Bitwise reproducible; 64-bit addressing. */
+#define LZ_PANEL_MAX_KEEP 16
+int lz_panel_compress(lz_handle *h, int64_t n, int b, int k, int r, lz_dtype dtype, void *V, int64_t vstride,
+                      const void *Z);
 
 /* m <= 64 steps of block Lanczos on a kept basis with full
  * reorthogonalisation: the recurrence and symmetric-sqrtm normalisation of
@@ -244,6 +256,23 @@ int lz_block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t 
                             const int32_t *col, const void *val, lz_dtype dtype, int b, int m,
                             int64_t lc, const void *B, void *q, void *alpha, void *beta, void *V,
                             int64_t vstride, void *W, int passes);
+
+/* Steps r .. m-1 of the same solve on a thick-restarted basis (1 <= r < m <=
+ * 64).  On entry blocks 0 .. r-1 of V hold the kept Ritz blocks Y (lz_panel_compress
+ * with the Z of lzh_restart_coeffs), W holds the residual the previous call left,
+ * and sigma (device, (r, b, b), the solve's dtype) holds the S_i of
+ * lzh_restart_coeffs.  Step r: beta_r = sqrtm(W^T W), Q_r = W beta_r^-1 into
+ * block r, W = A Q_r - sum_i Y_i S_i (one lz_panel_apply over the r kept
+ * blocks), alpha_r = sym(W^T Q_r), W -= Q_r alpha_r, `passes` rounds against the
+ * r + 1 blocks; steps r+1 .. m-1 are lz_block_lanczos_reorth's, then beta[m].
+ * Writes alpha[r .. m), beta[r .. m], q[r*b .. m*b), blocks r .. m-1 of V and W;
+ * alpha[0 .. r), beta[0 .. r), q[0 .. r*b) and blocks 0 .. r-1 are not written
+ * (row lc of Y is the caller's q^T Z_k).  No host synchronisation between
+ * steps; workspaces are reserved for m blocks before the first. */
+int lz_block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr,
+                                   const int32_t *col, const void *val, lz_dtype dtype, int b, int r, int m,
+                                   int64_t lc, const void *sigma, void *q, void *alpha, void *beta, void *V,
+                                   int64_t vstride, void *W, int passes);
 
 /* Single-vector Lanczos.  Replaces vector_lanczos<T>(A, b, m, lc, q, alpha,
  * beta, q0, q1, w) (methods/vector_lanczos.hpp:8-67; the correct variant -- the
@@ -336,7 +365,9 @@ enum {
     LZ_K_PGRAM16 = 7,   /* panel Gram, b = 16 fp64 MFMA (lz_panel_gram, lz_block_lanczos_reorth) */
     LZ_K_PGRAM_GEN = 8, /* panel Gram, any other shape */
     LZ_K_PAPPLY16 = 9,  /* panel apply, b = 16 fp64 MFMA (lz_panel_apply) */
-    LZ_K_PAPPLY_GEN = 10 /* panel apply, any other shape */
+    LZ_K_PAPPLY_GEN = 10, /* panel apply, any other shape */
+    LZ_K_PCOMP16 = 11,   /* panel compress, b = 16 fp64 MFMA (lz_panel_compress) */
+    LZ_K_PCOMP_GEN = 12  /* panel compress, any other shape */
 };
 int lz_debug_last_kernel(lz_handle *h, int out[2]);
 

@@ -93,6 +93,34 @@ int lzh_ritz_values(int m, int b, const double *alpha, const double *beta, doubl
  * resid may be NULL. */
 int lzh_ritz_pairs(int m, int b, const double *alpha, const double *beta, int nev, int which,
                    double *theta, double *S, double *resid);
+/* lzh_ritz_pairs for a dense symmetric projected matrix T ((m*b)^2 row-major,
+ * lower triangle read) -- what a restarted solve has, whose T is no longer
+ * block tridiagonal.  beta_m: the b x b true beta_m of the final residual
+ * (may be NULL when resid is).  Same `which`, outputs and residual formula;
+ * lzh_ritz_pairs is this call on Assemble_T(m, alpha, beta) and beta[m]. */
+int lzh_ritz_pairs_dense(int m, int b, const double *T, const double *beta_m, int nev, int which,
+                         double *theta, double *S, double *resid);
+/* Thick restart (Wu & Simon, block form) of a kept-basis solve.  After a cycle
+ * A P = P T + W E_m^T with P = [Q_0 .. Q_{m-1}] and beta_m = sqrtm(W^T W).
+ * With T = Z Theta Z^T (the wanted end first: which as above), keep the first
+ * r*b pairs Z_k, 1 <= r < m:
+ *   theta_k[r*b]     the kept Ritz values
+ *   Z (r, m, b, b)   Z_k in the layout of lz_panel_compress: Z[c][j] is rows
+ *                    [j*b, (j+1)*b), columns [c*b, (c+1)*b) of Z_k, so the
+ *                    compress leaves Y = P Z_k in blocks 0 .. r-1
+ *   sigma (r, b, b)  sigma[i] = (Sigma[:, i*b : (i+1)*b])^T with Sigma = beta_m
+ *                    Z_k[last b rows, :] (b x r*b): the operand of
+ *                    lz_block_lanczos_reorth_resume (A Y = Y Theta_k + Q_r Sigma,
+ *                    Q_r = W beta_m^-1)
+ *   T_next (m*b)^2   zero except diag(theta_k) and Sigma in block row r, columns
+ *                    0 .. r*b-1, mirrored into block column r
+ * lzh_restart_fill then adds what the resumed cycle computed: alpha_j on the
+ * diagonal for j = r .. m-1 and beta_j (block row j-1, block column j; beta_j^T
+ * below) for j = r+1 .. m-1, as Assemble_T places them.  The result is the T
+ * of the next lzh_ritz_pairs_dense / lzh_restart_coeffs. */
+int lzh_restart_coeffs(int m, int b, int r, const double *T, const double *beta_m, int which,
+                       double *theta_k, double *Z, double *sigma, double *T_next);
+int lzh_restart_fill(int r, int m, int b, const double *alpha, const double *beta, double *T_next);
 /* solution = (expm(T_end T)[:, :b] beta_0)^T q  (test_lanczos.cu:272-286) */
 int lzh_block_solution(int m, int b, double T_end, const double *alpha, const double *beta,
                        const double *q, double *solution);
