@@ -39,7 +39,7 @@ LZ_ROW_MAJOR, LZ_COL_MAJOR = 0, 1
 # lz_debug_last_kernel ids (include/lz_hip.h): SpMM kernels, their flags, dense kernels
 (LZ_K_SEG768, LZ_K_SEG1536, LZ_K_SEG1024, LZ_K_FNZ, LZ_K_BUF, LZ_K_LDS, LZ_K_ANY_B, LZ_K_CM_DIRECT,
  LZ_K_SPMV) = range(1, 10)
-LZ_K_WIN, LZ_K_YCM, LZ_K_EPI = 0x100, 0x200, 0x400
+LZ_K_WIN, LZ_K_YCM, LZ_K_EPI, LZ_K_AX3 = 0x100, 0x200, 0x400, 0x800
 LZ_K_GRAM16, LZ_K_GRAM32F, LZ_K_GRAM_GEN, LZ_K_TSMM16, LZ_K_TSMM32F, LZ_K_TSMM_GEN = range(1, 7)
 LZ_K_PGRAM16, LZ_K_PGRAM_GEN, LZ_K_PAPPLY16, LZ_K_PAPPLY_GEN = range(7, 11)
 # blocks per group of the panel Gram kernels (W is re-read once per group): b = 16 fp64 MFMA, generic
@@ -98,6 +98,16 @@ HIP_SYMBOLS = [
     ("lz_block_lanczos_reorth_resume", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int,
                                                 _c_int, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
                                                 _c_int]),
+    ("lz_csr_spmm_axpby", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp,
+                                   _c_dbl, _c_dbl, _c_vp, _c_vp]),
+    ("lz_cheb_apply", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp,
+                               _c_vp]),
+    ("lz_block_lanczos_reorth_cheb", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int,
+                                              _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int,
+                                              _c_vp, _c_vp]),
+    ("lz_block_lanczos_reorth_resume_cheb", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int,
+                                                     _c_int, _c_int, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                                     _c_i64, _c_vp, _c_int, _c_vp, _c_vp]),
     ("lz_vector_lanczos", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_i64,
                                    _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_fdtd_block", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp,
@@ -148,6 +158,7 @@ HOST_SYMBOLS = [
     ("lzh_ritz_pairs_dense", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     ("lzh_restart_coeffs", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_restart_fill", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
+    ("lzh_gershgorin", _c_int, [_c_i64, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_block_solution", _c_int, [_c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_partition_rows", _c_int, [_c_i64, _c_vp, _c_int, _c_vp]),
     ("lzh_remap_cols_padded", _c_int, [_c_i64, _c_vp, _c_int, _c_vp, _c_i64, _c_vp]),
@@ -280,6 +291,50 @@ def gen_powerlaw(n: int, nnz_per_row: float = 10.0, a: float = 2.1, cap: int = 1
     if L.lzh_gen_powerlaw_fill(n, nnz_per_row, a, cap, seed, _p(rp), _p(col), v64, v32):
         raise LanczosError("lzh_gen_powerlaw_fill failed")
     return CsrHost(n, rp, col, val)
+
+
+def gen_laplace2d(nx: int, ny: int, dtype=np.float64) -> CsrHost:
+    """The 5-point Laplacian of an nx x ny grid with Dirichlet boundaries (4 on the
+    diagonal, -1 to each neighbour; row iy*nx + ix, columns sorted).  Its eigenvalues are
+    4 - 2 cos(i pi / (nx+1)) - 2 cos(j pi / (ny+1)), inside the Gershgorin interval [0, 8]."""
+    if nx < 1 or ny < 1:
+        raise ValueError("gen_laplace2d: nx, ny >= 1")
+    n = nx * ny
+    i = np.arange(n, dtype=np.int64)
+    ix, iy = i % nx, i // nx
+    # the row's five slots in column order; absent neighbours masked out
+    cols = np.stack([i - nx, i - 1, i, i + 1, i + nx], axis=1)
+    mask = np.stack([iy > 0, ix > 0, np.ones(n, bool), ix < nx - 1, iy < ny - 1], axis=1)
+    vals = np.broadcast_to(np.array([-1, -1, 4, -1, -1], dtype), (n, 5))
+    rp = np.zeros(n + 1, np.int64)
+    np.cumsum(mask.sum(axis=1), out=rp[1:])
+    return CsrHost(n, rp, cols[mask].astype(np.int32), np.ascontiguousarray(vals[mask]))
+
+
+def gershgorin(A: CsrHost):
+    """(lo, hi): the Gershgorin enclosure of a square CSR operator's spectrum
+    (lzh_gershgorin; fp64 whatever A's precision).  An empty row's disc is [0, 0]."""
+    out = np.empty(2)
+    host = lambda t: t if isinstance(t, np.ndarray) else t.cpu().numpy()  # (a CsrDevice: copied back once)
+    val = np.ascontiguousarray(host(A.val), np.float64)
+    if host_lib().lzh_gershgorin(A.n, _p(np.ascontiguousarray(host(A.row_ptr), np.int64)),
+                                 _p(np.ascontiguousarray(host(A.col), np.int32)), _p(val), _p(out)):
+        raise LanczosError("lzh_gershgorin failed (n >= 1)")
+    return float(out[0]), float(out[1])
+
+
+class ChebFilter(ctypes.Structure):
+    """lz_cheb (include/lz_hip.h): the scaled Chebyshev filter of `degree` that damps
+    [lo, hi] and is 1 at ref."""
+    _fields_ = [("degree", _c_int), ("lo", _c_dbl), ("hi", _c_dbl), ("ref", _c_dbl)]
+
+
+def _cheb(filt):
+    """A ChebFilter from a (degree, lo, hi, ref) tuple (or one passed through)."""
+    if isinstance(filt, ChebFilter):
+        return filt
+    degree, lo, hi, ref = filt
+    return ChebFilter(int(degree), float(lo), float(hi), float(ref))
 
 
 def matrix_a_ell(N: int, bug_compat: bool = False):
@@ -583,6 +638,39 @@ class Handle:
                                   _ptr(A.val), A.dtype, b, _ptr(X), ldx, layout, _ptr(Y), ldy), "lz_csr_spmm")
         return Y
 
+    def _blocks(self, what: str, A: CsrDevice, *ts):
+        """n x b contiguous blocks of A's dtype for the three-term step and the filter."""
+        n, b = ts[0].shape
+        if A.n != A.n_cols or n != A.n:
+            raise LanczosError(f"{what}: a square operator with as many rows as the blocks")
+        for t in ts:
+            if t is not None and (tuple(t.shape) != (n, b) or not t.is_contiguous() or t.dtype != A.val.dtype):
+                raise LanczosError(f"{what}: every block (n, b) contiguous (ld = b), of A's dtype")
+        return n, b
+
+    def spmm_axpby(self, A: CsrDevice, a: float, X, c: float, d: float, Z, Y):
+        """Y = a (A X) + c X + d Z (lz_csr_spmm_axpby): A square, X / Z / Y (n, b) contiguous and
+        pairwise distinct; d == 0 never reads Z, which may be None."""
+        n, b = self._blocks("spmm_axpby", A, X, Y, Z)
+        _check(self.L.lz_csr_spmm_axpby(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                        a, _ptr(X), c, d, _ptr(Z), _ptr(Y)), "lz_csr_spmm_axpby")
+        return Y
+
+    def _work(self, what: str, work, n: int, b: int, like):
+        if work.dim() != 1 or not work.is_contiguous() or work.numel() < 2 * n * b or work.dtype != like.dtype:
+            raise LanczosError(f"{what}: work is a flat contiguous tensor of 2*n*b elements of the solve's dtype")
+
+    def cheb_apply(self, A: CsrDevice, filt, X, Y, work):
+        """Y = p(A) X with p the scaled Chebyshev filter filt = (degree, lo, hi, ref)
+        (lz_cheb_apply): damped on [lo, hi], 1 at ref.  work: flat, 2*n*b elements; X is only
+        read."""
+        n, b = self._blocks("cheb_apply", A, X, Y)
+        self._work("cheb_apply", work, n, b, X)
+        f = _cheb(filt)
+        _check(self.L.lz_cheb_apply(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                    ctypes.addressof(f), _ptr(X), _ptr(Y), _ptr(work)), "lz_cheb_apply")
+        return Y
+
     def to_row_major(self, Xcm, Y):
         """Y (rows, b) row-major <- the column-major block viewed as Xcm (b, ld) (ld >= rows)."""
         b, ld = Xcm.shape
@@ -680,16 +768,25 @@ class Handle:
         return W
 
     def block_lanczos_reorth(self, A: CsrDevice, B, m: int, lc: int, q, alpha, beta, V, vstride: int, W,
-                             passes: int = 2):
+                             passes: int = 2, filt=None, work=None):
         """Block Lanczos on a kept basis with `passes` rounds of full reorthogonalisation
         per step (lz_block_lanczos_reorth).  q[m*b], alpha[m,b,b], beta[m+1,b,b] (beta[m]
         = the true beta_m), the panel V (m blocks) and W (the final residual) are written
-        in place."""
+        in place.  filt = (degree, lo, hi, ref) with work (flat, 2*n*b elements): the same
+        solve on the Chebyshev-filtered operator p(A) (lz_block_lanczos_reorth_cheb)."""
         n, b = B.shape
         self._panel(V, vstride, n, b, max(m, 1))
-        _check(self.L.lz_block_lanczos_reorth(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val),
-                                              A.dtype, b, m, lc, _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta),
-                                              _ptr(V), vstride, _ptr(W), passes), "lz_block_lanczos_reorth")
+        if filt is None:
+            _check(self.L.lz_block_lanczos_reorth(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val),
+                                                  A.dtype, b, m, lc, _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta),
+                                                  _ptr(V), vstride, _ptr(W), passes), "lz_block_lanczos_reorth")
+            return
+        self._work("block_lanczos_reorth", work, n, b, W)
+        f = _cheb(filt)
+        _check(self.L.lz_block_lanczos_reorth_cheb(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val),
+                                                   A.dtype, b, m, lc, _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta),
+                                                   _ptr(V), vstride, _ptr(W), passes, ctypes.addressof(f),
+                                                   _ptr(work)), "lz_block_lanczos_reorth_cheb")
 
     def ritz_vectors(self, V, vstride: int, S, X, n: int, b: int):
         """X = [V_0 .. V_{m-1}] S: the Ritz vectors of host coefficients S ((m*b, nev),
@@ -736,24 +833,34 @@ class Handle:
         return V
 
     def block_lanczos_reorth_resume(self, A: CsrDevice, r: int, m: int, lc: int, sigma, q, alpha, beta, V,
-                                    vstride: int, W, passes: int = 2):
+                                    vstride: int, W, passes: int = 2, filt=None, work=None):
         """Steps r .. m-1 of block_lanczos_reorth on a thick-restarted basis
         (lz_block_lanczos_reorth_resume): blocks 0 .. r-1 of V hold the kept Ritz blocks
         (panel_compress), W the previous cycle's residual, sigma (r, b, b) the device copy of
-        restart_coeffs' sigma.  Writes alpha[r:], beta[r:], q[r*b:], blocks r .. m-1 and W."""
+        restart_coeffs' sigma.  Writes alpha[r:], beta[r:], q[r*b:], blocks r .. m-1 and W.
+        filt, work: as block_lanczos_reorth (the same filter for every cycle of a solve)."""
         n, b = W.shape
         self._panel(V, vstride, n, b, max(m, 1))
         if not sigma.is_contiguous() or sigma.numel() < max(r, 0) * b * b or sigma.dtype != W.dtype \
                 or V.dtype != W.dtype or not W.is_contiguous():
             raise LanczosError("block_lanczos_reorth_resume: W (n, b) and sigma (r, b, b) contiguous, one dtype")
-        _check(self.L.lz_block_lanczos_reorth_resume(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val),
-                                                     A.dtype, b, r, m, lc, _ptr(sigma), _ptr(q), _ptr(alpha),
-                                                     _ptr(beta), _ptr(V), vstride, _ptr(W), passes),
-               "lz_block_lanczos_reorth_resume")
+        if filt is None:
+            _check(self.L.lz_block_lanczos_reorth_resume(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col),
+                                                         _ptr(A.val), A.dtype, b, r, m, lc, _ptr(sigma), _ptr(q),
+                                                         _ptr(alpha), _ptr(beta), _ptr(V), vstride, _ptr(W), passes),
+                   "lz_block_lanczos_reorth_resume")
+            return
+        self._work("block_lanczos_reorth_resume", work, n, b, W)
+        f = _cheb(filt)
+        _check(self.L.lz_block_lanczos_reorth_resume_cheb(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col),
+                                                          _ptr(A.val), A.dtype, b, r, m, lc, _ptr(sigma), _ptr(q),
+                                                          _ptr(alpha), _ptr(beta), _ptr(V), vstride, _ptr(W), passes,
+                                                          ctypes.addressof(f), _ptr(work)),
+               "lz_block_lanczos_reorth_resume_cheb")
 
     def eigsh(self, A: CsrDevice, nev: int, which: str = "largest", b: int = 16, m: Optional[int] = None,
               keep: Optional[int] = None, tol: float = 1e-10, max_cycles: int = 100, B=None, lc: int = 0,
-              passes: int = 2):
+              passes: int = 2, filter_degree: Optional[int] = None, cut: Optional[float] = None):
         """The nev outermost eigenpairs of A by thick-restart block Lanczos in a fixed panel
         of m blocks.  Cycle 1 is block_lanczos_reorth from B (default uniform_B); every later
         cycle keeps the first keep*b Ritz pairs (restart_coeffs), compresses the panel onto
@@ -767,9 +874,26 @@ class Handle:
         m: twice that, at least 4.  The solve's precision is A's.  Device memory that scales with n: the
         panel, W and B.  Returns a dict: theta[nev], resid[nev], V (the panel, flat), vstride,
         cycles, n_spmm, converged, history (the largest wanted residual of each cycle), scale
-        (the last cycle's max|theta|)."""
+        (the last cycle's max|theta|).
+
+        filter_degree = d (1 .. 256): the same restart on p(A), a degree-d scaled Chebyshev
+        filter, for ends that converge slowly (the smallest eigenvalues of Laplacian-like
+        operators).  One unfiltered solve of m blocks gives the Ritz values theta of A (and
+        returns at once if it already meets the stop test); p damps [theta[keep*b], g_hi]
+        (which = "smallest"; mirrored for "largest"; g: gershgorin(A); cut replaces the
+        Ritz-value end) and is 1 at the outermost theta, fixed for the whole solve.  After
+        every cycle's compress the first ceil(nev / b) kept blocks are checked on A itself,
+        block by block (Rayleigh-Ritz within the block, true residual norms); it stops when
+        the nev candidates at the wanted end have residuals <= tol * scale (scale: the
+        unfiltered solve's max|theta|).  The dict then also has cols[nev] (the panel column
+        of each pair, which need not be the first nev: V is not re-packed), filter = (degree,
+        lo, hi, ref), n_steps (Lanczos steps, the unfiltered solve included); resid is the
+        measured residual on A, cycles counts the filtered cycles, n_spmm every SpMM
+        (bounds, filter steps and checks).  Needs 2 n b more elements of device memory."""
         torch = _torch()
         _which(which)
+        if filter_degree is not None and not 1 <= int(filter_degree) <= 256:
+            raise LanczosError("eigsh: 1 <= filter_degree <= 256")
         n = A.n
         tdt = A.val.dtype
         want = -(-(nev + b) // b)  # the smallest keep with keep * b >= nev + b
@@ -790,6 +914,9 @@ class Handle:
         V = torch.zeros(m * vstride, **kw)
         W = torch.empty(n, b, **kw)
         q, al, be = torch.zeros(m * b, **kw), torch.zeros(m, b, b, **kw), torch.zeros(m + 1, b, b, **kw)
+        if filter_degree is not None:
+            return self._eigsh_cheb(A, nev, which, b, m, r, tol, max_cycles, B, lc, passes, int(filter_degree), cut,
+                                    V, vstride, W, q, al, be)
         self.block_lanczos_reorth(A, B, m, lc, q, al, be, V, vstride, W, passes=passes)
         n_spmm, cycles, history, converged = m, 1, [], False
         f64 = lambda t: t.cpu().numpy().astype(np.float64)
@@ -823,6 +950,103 @@ class Handle:
         self.panel_compress(V, vstride, m, nch, torch.from_numpy(Zx).to(**kw), n=n)
         return dict(theta=theta, resid=resid, V=V, vstride=vstride, cycles=cycles, n_spmm=n_spmm,
                     converged=converged, history=history, scale=scale)
+
+    def _eigsh_cheb(self, A, nev, which, b, m, r, tol, max_cycles, B, lc, passes, degree, cut, V, vstride, W, q, al,
+                    be):
+        """eigsh(filter_degree=degree) on the buffers eigsh allocated (its docstring)."""
+        torch = _torch()
+        n = A.n
+        kw = dict(dtype=A.val.dtype, device=A.val.device)
+        f64 = lambda t: t.cpu().numpy().astype(np.float64)
+        nch = -(-nev // b)
+        # 1. bounds: one unfiltered solve; its Ritz values place the filter
+        self.block_lanczos_reorth(A, B, m, lc, q, al, be, V, vstride, W, passes=passes)
+        n_steps = n_spmm = m
+        alpha, beta = f64(al), f64(be)
+        T = Assemble_T(m, b, alpha, beta[:m])
+        theta, S, resid = ritz_pairs_dense(m, b, T, beta[m], m * b, which)
+        scale = float(np.abs(theta).max())
+        if resid[:nev].max() <= tol * scale:  # finished as the unfiltered eigsh finishes
+            Zx = np.zeros((nch, m, b, b))
+            for c in range(nch):
+                w = min(b, nev - c * b)
+                Zx[c, :, :, :w] = S[:, c * b:c * b + w].reshape(m, b, w)
+            self.panel_compress(V, vstride, m, nch, torch.from_numpy(Zx).to(**kw), n=n)
+            return dict(theta=theta[:nev], resid=resid[:nev], V=V, vstride=vstride, cycles=0, n_spmm=n_spmm,
+                        converged=True, history=[float(resid[:nev].max())], scale=scale, cols=np.arange(nev),
+                        filter=None, n_steps=n_steps)
+        # 2. the filter, fixed for the whole solve (the Lanczos relation across restarts needs
+        # one operator).  The far end is Gershgorin's: a guaranteed enclosure, where a Lanczos
+        # estimate that falls short would let p blow up.  theta_i >= lambda_i (Cauchy
+        # interlacing), so the keep*b wanted eigenvalues lie outside the damped interval.
+        g_lo, g_hi = gershgorin(A)
+        asc = np.sort(theta)
+        if which == "smallest":
+            lo, hi, ref = (asc[r * b] if cut is None else float(cut)), g_hi, asc[0]
+        else:
+            lo, hi, ref = g_lo, (asc[-1 - r * b] if cut is None else float(cut)), asc[-1]
+        if not lo < hi:
+            raise LanczosError(f"eigsh: the damped interval [{lo}, {hi}] is empty (cut beyond the far end?)")
+        if lo <= ref <= hi:
+            raise LanczosError(f"eigsh: cut = {cut} leaves the outermost Ritz value {ref} inside the damped interval")
+        filt = (degree, float(lo), float(hi), float(ref))
+        work = torch.empty(2 * n * b, **kw)
+        U = work[:n * b].view(n, b)  # the check's block (the filter's workspace is free between solves)
+        Th, G = torch.empty(b, b, **kw), torch.empty(b, b, **kw)
+
+        def check():
+            """Rayleigh-Ritz on A within each of the first nch kept blocks Y_i: U = A Y_i, Theta_i =
+            sym(Y_i^T U) = C Lambda C^T, R = U - Y_i Theta_i; the residual norms of the pairs
+            (Lambda, Y_i C) are the column norms of R C, from R^T R.  W is not touched."""
+            lam, res, Cs = [], [], []
+            for i in range(nch):
+                Yi = V[i * vstride:i * vstride + n * b].view(n, b)
+                self.spmm(A, Yi, U)
+                self.mm_tt2(U, Yi, Th)
+                self.mm_ts(1.0, -1.0, Yi, Th, U)
+                self.mm_tt(U, G)
+                Thh, Gh = f64(Th), f64(G)
+                lm, C = np.linalg.eigh(0.5 * (Thh + Thh.T))
+                lam.append(lm)
+                res.append(np.sqrt(np.maximum(np.einsum("ij,ik,kj->j", C, 0.5 * (Gh + Gh.T), C), 0.0)))
+                Cs.append(C)
+            return np.concatenate(lam), np.concatenate(res), Cs
+
+        # 3. thick restart on p(A) from the same B: eigsh's loop, the largest end of T
+        self.block_lanczos_reorth(A, B, m, lc, q, al, be, V, vstride, W, passes=passes, filt=filt, work=work)
+        n_steps += m
+        n_spmm += m * degree
+        cycles, history = 1, []
+        alpha, beta = f64(al), f64(be)
+        T = Assemble_T(m, b, alpha, beta[:m])
+        while True:
+            _, Z, sigma, T = restart_coeffs(m, b, r, T, beta[m], "largest")
+            self.panel_compress(V, vstride, m, r, torch.from_numpy(Z).to(**kw), n=n)
+            # 4. the true residuals on A of the first nch kept blocks
+            lam, res, Cs = check()
+            n_spmm += nch
+            # 5. the nev candidates at the wanted end
+            sel = np.argsort(lam if which == "smallest" else -lam, kind="stable")[:nev]
+            history.append(float(res[sel].max()))
+            converged = bool(res[sel].max() <= tol * scale)
+            if converged or cycles >= max_cycles:
+                break
+            Zk = Z.transpose(1, 2, 0, 3).reshape(m * b, r * b)
+            q[:r * b] = torch.from_numpy(f64(q) @ Zk).to(**kw)
+            self.block_lanczos_reorth_resume(A, r, m, lc, torch.from_numpy(sigma).to(**kw), q, al, be, V, vstride, W,
+                                             passes=passes, filt=filt, work=work)
+            alpha, beta = f64(al), f64(be)
+            restart_fill(r, m, b, alpha, beta, T)
+            n_steps += m - r
+            n_spmm += (m - r) * degree
+            cycles += 1
+        # block i <- Y_i C_i, in place: one compress over the nch blocks with a block-diagonal Z
+        Zr = np.zeros((nch, nch, b, b))
+        for i in range(nch):
+            Zr[i, i] = Cs[i]
+        self.panel_compress(V, vstride, nch, nch, torch.from_numpy(Zr).to(**kw), n=n)
+        return dict(theta=lam[sel], resid=res[sel], V=V, vstride=vstride, cycles=cycles, n_spmm=n_spmm,
+                    converged=converged, history=history, scale=scale, cols=sel, filter=filt, n_steps=n_steps)
 
     def set_final_state(self, on: bool) -> None:
         """True (default): block_lanczos_blas leaves Q0 = Q1 = Q_{m-1} and W = the

@@ -1,6 +1,8 @@
 // lz_api.hip -- the extern "C" boundary of liblz_hip.so (include/lz_hip.h)
 // plus the device-resident Lanczos methods behind it.
+#include <cmath>
 #include <cstdarg>
+#include <cstdlib>
 #include <cstring>
 #include <algorithm>
 #include <utility>
@@ -204,13 +206,62 @@ static int reorth_rounds(lz_handle *h, int64_t n, int b, int k, const T *V, int6
     return LZ_OK;
 }
 
+// LZ_AX3=0 (read per call, measurement): lz_csr_spmm_axpby's two-launch form at every shape
+static bool ax3_fused()
+{
+    const char *e = getenv("LZ_AX3");
+    return !(e && e[0] == '0');
+}
+
+static int cheb_args(const lz_cheb *f)
+{
+    LZ_ARG_CHECK(f->degree >= 1 && f->degree <= 256, "Chebyshev filter: 1 <= degree <= 256");
+    LZ_ARG_CHECK(std::isfinite(f->lo) && std::isfinite(f->hi) && std::isfinite(f->ref) && f->lo < f->hi,
+                 "Chebyshev filter: lo < hi, finite");
+    LZ_ARG_CHECK(f->ref < f->lo || f->ref > f->hi, "Chebyshev filter: ref outside [lo, hi]");
+    return LZ_OK;
+}
+
+// Y = p(A) X, the Zhou-Saad scaled Chebyshev filter (lz_cheb_apply): `degree`
+// three-term steps, one spmm_axpby each, coefficients on the host.  Step i
+// writes buffer (i + 2 - degree) mod 3 of {work_0, work_1, Y}: the last step
+// lands in Y, and a step's output is neither of its two inputs (step 2 reads X
+// in Y_0's place).  No host synchronisation.
+template <typename T>
+static int cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val,
+                      int b, const lz_cheb &f, const T *X, T *Y, T *work)
+{
+    const double e = 0.5 * (f.hi - f.lo), c0 = 0.5 * (f.hi + f.lo), s1 = e / (f.ref - c0);
+    T *buf[3] = {work, work + n * b, Y};
+    const bool fused = ax3_fused();
+    auto out = [&](int i) { return buf[((i + 2 - f.degree) % 3 + 3) % 3]; };
+    LZ_TRY(spmm_axpby<T>(h, n, nnz, rp, col, val, b, T(s1 / e), X, T(-c0 * s1 / e), T(0), nullptr, out(1), fused));
+    double sg = s1;
+    for (int i = 2; i <= f.degree; ++i) {
+        const double sn = 1.0 / (2.0 / s1 - sg);
+        LZ_TRY(spmm_axpby<T>(h, n, nnz, rp, col, val, b, T(2.0 * sn / e), out(i - 1), T(-2.0 * sn * c0 / e),
+                             T(-sg * sn), i == 2 ? X : out(i - 2), out(i), fused));
+        sg = sn;
+    }
+    return LZ_OK;
+}
+
+// W = A Q, or (f != nullptr) W = p(A) Q: the operator line of the kept-basis solves
+template <typename T>
+static int reorth_op(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                     const T *Q, T *W, const lz_cheb *f, T *work)
+{
+    if (!f) return spmm_rm<T>(h, n, nnz, rp, col, val, b, Q, b, n, W, b);
+    return cheb_apply<T>(h, n, nnz, rp, col, val, b, *f, Q, W, work);
+}
+
 // Steps j0 .. m - 1 (j0 >= 1; block j0 - 1 holds Q_{j0-1}, W the residual of
 // step j0 - 1), then beta_m of the final residual: the part a first cycle and
 // a resumed one share.
 template <typename T>
 static int reorth_steps(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val,
                         int b, int j0, int m, int64_t lc, T *q, T *alpha, T *beta, T *V, int64_t vstride, T *W,
-                        int passes)
+                        int passes, const lz_cheb *f, T *work)
 {
     const int64_t bb = (int64_t)b * b;
     T *binv = reinterpret_cast<T *>(h->scratch + 4 * kMaxB * kMaxB);
@@ -221,7 +272,7 @@ static int reorth_steps(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp,
         LZ_TRY(gram_partials<T>(h, n, b, W, W, b, &P));
         LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, bj, binv, nullptr));     // beta_j = sqrtm(W'W)
         LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), W, binv, Qj, b));           // Q_j = W beta_j^-1
-        LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, Qj, b, n, W, b)); // W = A Q_j
+        LZ_TRY(reorth_op<T>(h, n, nnz, rp, col, val, b, Qj, W, f, work)); // W = A Q_j (or p(A) Q_j)
         LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qp, bj, W, b));            // W -= Q_{j-1} beta_j
         LZ_TRY(gram_partials<T>(h, n, b, W, Qj, b, &P));
         LZ_TRY(gram_finish<T>(h, b, P, 1, aj));                         // alpha_j
@@ -237,7 +288,7 @@ static int reorth_steps(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp,
 template <typename T>
 static int block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
                                 const T *val, int b, int m, int64_t lc, const T *B, T *q, T *alpha, T *beta, T *V,
-                                int64_t vstride, T *W, int passes)
+                                int64_t vstride, T *W, int passes, const lz_cheb *f, T *work)
 {
     T *binv = reinterpret_cast<T *>(h->scratch + 4 * kMaxB * kMaxB);
     LZ_TRY(reorth_reserve<T>(h, n, b, m, passes));
@@ -247,12 +298,12 @@ static int block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int6
     LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, beta, binv, nullptr));      // beta_0 = sqrtm(B'B)
     LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), B, binv, Qj, b));               // Q_0 = B beta_0^-1
     LZ_TRY(copy_row<T>(h, b, Qj, b, 0, lc, q));
-    LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, Qj, b, n, W, b));     // W = A Q_0
+    LZ_TRY(reorth_op<T>(h, n, nnz, rp, col, val, b, Qj, W, f, work));   // W = A Q_0
     LZ_TRY(gram_partials<T>(h, n, b, W, Qj, b, &P));
     LZ_TRY(gram_finish<T>(h, b, P, 1, alpha));                          // alpha_0
     LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qj, alpha, W, b));             // W -= Q_0 alpha_0
     LZ_TRY(reorth_rounds<T>(h, n, b, 1, V, vstride, W, passes));
-    return reorth_steps<T>(h, n, nnz, rp, col, val, b, 1, m, lc, q, alpha, beta, V, vstride, W, passes);
+    return reorth_steps<T>(h, n, nnz, rp, col, val, b, 1, m, lc, q, alpha, beta, V, vstride, W, passes, f, work);
 }
 
 // A cycle on a thick-restarted basis (lz_block_lanczos_reorth_resume): blocks
@@ -264,7 +315,8 @@ static int block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int6
 template <typename T>
 static int block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
                                        const T *val, int b, int r, int m, int64_t lc, const T *sigma, T *q,
-                                       T *alpha, T *beta, T *V, int64_t vstride, T *W, int passes)
+                                       T *alpha, T *beta, T *V, int64_t vstride, T *W, int passes, const lz_cheb *f,
+                                       T *work)
 {
     const int64_t bb = (int64_t)b * b;
     T *binv = reinterpret_cast<T *>(h->scratch + 4 * kMaxB * kMaxB);
@@ -274,14 +326,15 @@ static int block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, con
     LZ_TRY(gram_partials<T>(h, n, b, W, W, b, &P));
     LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, br, binv, nullptr));         // beta_r = sqrtm(W'W)
     LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), W, binv, Qr, b));               // Q_r = W beta_r^-1
-    LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, Qr, b, n, W, b));     // W = A Q_r
+    LZ_TRY(reorth_op<T>(h, n, nnz, rp, col, val, b, Qr, W, f, work));   // W = A Q_r
     LZ_TRY(panel_apply<T>(h, n, b, r, 1.0, -1.0, V, vstride, sigma, W)); // W -= sum_i Y_i S_i
     LZ_TRY(gram_partials<T>(h, n, b, W, Qr, b, &P));
     LZ_TRY(gram_finish<T>(h, b, P, 1, ar));                             // alpha_r
     LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qr, ar, W, b));                // W -= Q_r alpha_r
     LZ_TRY(reorth_rounds<T>(h, n, b, r + 1, V, vstride, W, passes));
     LZ_TRY(copy_row<T>(h, b, Qr, b, 0, lc, q + (int64_t)r * b));
-    return reorth_steps<T>(h, n, nnz, rp, col, val, b, r + 1, m, lc, q, alpha, beta, V, vstride, W, passes);
+    return reorth_steps<T>(h, n, nnz, rp, col, val, b, r + 1, m, lc, q, alpha, beta, V, vstride, W, passes, f,
+                           work);
 }
 
 // Fused device-resident iteration, b = 16 fp64 (lz_fused.hip), Q-free: the
@@ -1787,9 +1840,78 @@ int lz_panel_apply(lz_handle *h, int64_t n, int b, int k, lz_dtype dtype, double
     return panel_apply<float>(h, n, b, k, beta, alpha, (const float *)V, vstride, (const float *)S, (float *)W);
 }
 
+// n x b blocks at p and q (es bytes per element) do not overlap
+static bool blocks_apart(const void *p, int64_t np, const void *q, int64_t nq, int64_t es)
+{
+    const char *a = (const char *)p, *c = (const char *)q;
+    return a + np * es <= c || c + nq * es <= a;
+}
+
+// the filter and its workspace of a solve on p(A): work (2 n b) apart from W, B (may be null) and the panel
+static int cheb_solve_args(const lz_cheb *f, const void *work, int64_t n, int b, int m, lz_dtype dtype,
+                           const void *V, int64_t vstride, const void *W, const void *B)
+{
+    if (!f) return LZ_OK;
+    LZ_TRY(cheb_args(f));
+    LZ_ARG_CHECK(work != nullptr, "work is NULL");
+    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
+    LZ_ARG_CHECK(reinterpret_cast<uintptr_t>(work) % 16 == 0, "work must be on 16 bytes");
+    LZ_ARG_CHECK(blocks_apart(work, 2 * nb, W, nb, es) && (!B || blocks_apart(work, 2 * nb, B, nb, es)) &&
+                     blocks_apart(work, 2 * nb, V, (int64_t)(m - 1) * vstride + nb, es),
+                 "work must not overlap B, W or the panel V");
+    return LZ_OK;
+}
+
+int lz_csr_spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                      lz_dtype dtype, int b, double a, const void *X, double c, double d, const void *Z, void *Y)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(b >= 1 && b <= kMaxB, "b in [1,64]");
+    LZ_ARG_CHECK(X && Y && (Z || d == 0.0), "X/Y NULL, or Z NULL with d != 0");
+    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
+    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && (d == 0.0 || (blocks_apart(Z, nb, Y, nb, es) && Z != X)),
+                 "X, Z and Y must be pairwise distinct (no in-place form)");
+    if (dtype == LZ_F64)
+        return spmm_axpby<double>(h, n, nnz, rp, col, (const double *)val, b, a, (const double *)X, c, d,
+                                  (const double *)Z, (double *)Y, ax3_fused());
+    return spmm_axpby<float>(h, n, nnz, rp, col, (const float *)val, b, (float)a, (const float *)X, (float)c, (float)d,
+                             (const float *)Z, (float *)Y, ax3_fused());
+}
+
+int lz_cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                  lz_dtype dtype, int b, const lz_cheb *f, const void *X, void *Y, void *work)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= kMaxB, "n >= 1, b in [1,64]");
+    LZ_ARG_CHECK(f && X && Y && work, "f/X/Y/work NULL");
+    LZ_TRY(cheb_args(f));
+    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
+    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && blocks_apart(work, 2 * nb, X, nb, es) &&
+                     blocks_apart(work, 2 * nb, Y, nb, es),
+                 "X, Y and work must be pairwise distinct");
+    if (dtype == LZ_F64)
+        return cheb_apply<double>(h, n, nnz, rp, col, (const double *)val, b, *f, (const double *)X, (double *)Y,
+                                  (double *)work);
+    return cheb_apply<float>(h, n, nnz, rp, col, (const float *)val, b, *f, (const float *)X, (float *)Y,
+                             (float *)work);
+}
+
 int lz_block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
                             const void *val, lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q,
                             void *alpha, void *beta, void *V, int64_t vstride, void *W, int passes)
+{
+    return lz_block_lanczos_reorth_cheb(h, n, nnz, rp, col, val, dtype, b, m, lc, B, q, alpha, beta, V, vstride, W,
+                                        passes, nullptr, nullptr);
+}
+
+int lz_block_lanczos_reorth_cheb(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                                 const void *val, lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q,
+                                 void *alpha, void *beta, void *V, int64_t vstride, void *W, int passes,
+                                 const lz_cheb *f, void *work)
 {
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(n, nnz, rp, col, val));
@@ -1805,13 +1927,14 @@ int lz_block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t 
         LZ_ARG_CHECK((w0 + n * b * es <= v0 || w0 >= v1) && (b0 + n * b * es <= v0 || b0 >= v1) && B != W,
                      "B, W and the panel V must be distinct buffers");
     }
+    LZ_TRY(cheb_solve_args(f, work, n, b, m, dtype, V, vstride, W, B));
     if (dtype == LZ_F64)
         return block_lanczos_reorth<double>(h, n, nnz, rp, col, (const double *)val, b, m, lc, (const double *)B,
                                             (double *)q, (double *)alpha, (double *)beta, (double *)V, vstride,
-                                            (double *)W, passes);
+                                            (double *)W, passes, f, (double *)work);
     return block_lanczos_reorth<float>(h, n, nnz, rp, col, (const float *)val, b, m, lc, (const float *)B,
                                        (float *)q, (float *)alpha, (float *)beta, (float *)V, vstride, (float *)W,
-                                       passes);
+                                       passes, f, (float *)work);
 }
 
 int lz_panel_compress(lz_handle *h, int64_t n, int b, int k, int r, lz_dtype dtype, void *V, int64_t vstride,
@@ -1831,6 +1954,15 @@ int lz_block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, const i
                                    const void *sigma, void *q, void *alpha, void *beta, void *V, int64_t vstride,
                                    void *W, int passes)
 {
+    return lz_block_lanczos_reorth_resume_cheb(h, n, nnz, rp, col, val, dtype, b, r, m, lc, sigma, q, alpha, beta, V,
+                                               vstride, W, passes, nullptr, nullptr);
+}
+
+int lz_block_lanczos_reorth_resume_cheb(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                                        const void *val, lz_dtype dtype, int b, int r, int m, int64_t lc,
+                                        const void *sigma, void *q, void *alpha, void *beta, void *V, int64_t vstride,
+                                        void *W, int passes, const lz_cheb *f, void *work)
+{
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(n, nnz, rp, col, val));
     LZ_ARG_CHECK(m >= 1 && m <= kPanelMaxK, "the kept basis holds 1 <= m <= 64 blocks");
@@ -1846,13 +1978,15 @@ int lz_block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, const i
         const char *w0 = (const char *)W;
         LZ_ARG_CHECK(w0 + n * b * es <= v0 || w0 >= v1, "W and the panel V must be distinct buffers");
     }
+    LZ_TRY(cheb_solve_args(f, work, n, b, m, dtype, V, vstride, W, nullptr));
     if (dtype == LZ_F64)
         return block_lanczos_reorth_resume<double>(h, n, nnz, rp, col, (const double *)val, b, r, m, lc,
                                                    (const double *)sigma, (double *)q, (double *)alpha,
-                                                   (double *)beta, (double *)V, vstride, (double *)W, passes);
+                                                   (double *)beta, (double *)V, vstride, (double *)W, passes, f,
+                                                   (double *)work);
     return block_lanczos_reorth_resume<float>(h, n, nnz, rp, col, (const float *)val, b, r, m, lc,
                                               (const float *)sigma, (float *)q, (float *)alpha, (float *)beta,
-                                              (float *)V, vstride, (float *)W, passes);
+                                              (float *)V, vstride, (float *)W, passes, f, (float *)work);
 }
 
 int lz_vector_lanczos(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,

@@ -631,6 +631,25 @@ int lzh_restart_coeffs(int m, int b, int r, const double *T, const double *bm, i
     return 0;
 }
 
+int lzh_gershgorin(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val, double out[2])
+{
+    if (n < 1 || !row_ptr || !out || (row_ptr[n] > 0 && (!col || !val))) return -1;
+    double lo = INFINITY, hi = -INFINITY;
+#pragma omp parallel for reduction(min : lo) reduction(max : hi) schedule(static)
+    for (int64_t r = 0; r < n; ++r) {
+        double d = 0.0, rad = 0.0;  // (duplicates of the diagonal add up, as they do in the product)
+        for (int64_t k = row_ptr[r]; k < row_ptr[r + 1]; ++k) {
+            if (col[k] == r) d += val[k];
+            else rad += std::fabs(val[k]);
+        }
+        lo = std::min(lo, d - rad);
+        hi = std::max(hi, d + rad);
+    }
+    out[0] = lo;
+    out[1] = hi;
+    return 0;
+}
+
 int lzh_restart_fill(int r, int m, int b, const double *alpha, const double *beta, double *T_next)
 {
     const int k = m * b;

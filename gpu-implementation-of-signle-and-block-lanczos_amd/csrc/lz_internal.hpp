@@ -9,6 +9,13 @@ template <typename T>
 int spmm_rm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
             const T *X, int64_t ldx, int64_t nx, T *Y, int64_t ldy,
             bool ycm = false);  // nx: rows of X; ycm: Y column-major (leading dimension ldy), b >= 2
+// Y = a A X + c X + d Z, square operator, X / Z / Y n x b row-major with ld = b and
+// pairwise distinct; d == 0 never reads Z.  128-B rows under 2 GiB: fused into
+// k_spmm_seg's store (last_kernel | LZ_K_AX3); else, or fused = false: spmm_rm,
+// then one row-local kernel
+template <typename T>
+int spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+               T a, const T *X, T c, T d, const T *Z, T *Y, bool fused = true);
 template <typename T>
 int spmm_cm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
             const T *X, int64_t ldx, int64_t nx, T *Y, int64_t ldy);  // nx: rows of X

@@ -386,6 +386,28 @@ __device__ __forceinline__ Vec<T, VEC> epi_piece(Vec<T, VEC> y, const T *__restr
     return y;
 }
 
+// Three-term row piece (AX3, lz_csr_spmm_axpby): from the finished SpMM piece s
+// of a row, a s + c x + d z with x, z the lane's own 16-B pieces of X[row] and
+// Z[row] (zrow == nullptr: d == 0, Z is never read).  X[row] is the piece the
+// diagonal entry gathered, so it usually comes from cache; Z is streamed once:
+// a non-temporal load, as epi_piece loads W.
+template <typename T, int VEC>
+__device__ __forceinline__ Vec<T, VEC> ax3_piece(Vec<T, VEC> s, const T *__restrict__ xrow,
+                                                 const T *__restrict__ zrow, T a, T c, T d)
+{
+    static_assert(sizeof(T) * VEC == 16, "128-B rows: 16-B pieces");
+    const Vec<T, VEC> x = ldv<T, VEC>(xrow);
+    Vec<T, VEC> z;
+    if (zrow) {
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 u = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(zrow));
+        __builtin_memcpy(&z, &u, 16);
+    }
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) s.v[i] = fma(a, s.v[i], fma(c, x.v[i], zrow ? d * z.v[i] : T(0)));
+    return s;
+}
+
 // ---- CU-partitioned SpMM (LZ_SPMM_PF, diagnostic build only: measured and
 // dropped in round 6, DESIGN.md 4 SpMM "Round 6") ----
 // The tile kernel runs on a stream masked to most of each XCD's CUs; a
@@ -407,15 +429,19 @@ __device__ __forceinline__ int xcc_id()
     return (int)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 7u);  // HW_REG_XCC_ID
 }
 
-template <typename T, int B, int TR, int CAP, bool WIN, int MODE, bool YCM = false, bool EPI = false, bool PF = false>
+template <typename T, int B, int TR, int CAP, bool WIN, int MODE, bool YCM = false, bool EPI = false, bool PF = false,
+          bool AX3 = false>
 __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__restrict__ rp,
                                                   const int32_t *__restrict__ col,
                                                   const T *__restrict__ val,
                                                   const T *__restrict__ X, int64_t ldx, int64_t nx,
                                                   T *__restrict__ Y, int64_t ldy, int *__restrict__ longq,
                                                   int parity, const T *__restrict__ Wp, const T *__restrict__ Mm,
-                                                  int diag, int *__restrict__ pfc)
+                                                  int diag, int *__restrict__ pfc, T ca, T cc, T cd)
 {
+    // AX3 (lz_csr_spmm_axpby; square operator, ldx = ldy = B): the stored row is
+    // ca Y + cc X[row] + cd Wp[row] (Wp: Z, nullptr when cd == 0), ax3_piece at
+    // both store sites; ca, cc, cd are unused otherwise.
     // MODE 0: tiles whose run exceeds the stage (or, WIN, whose columns exceed
     //         the window) are queued (longq[0] = count, longq[1..] = tile ids)
     //         for MODE 1, so their code path costs the main kernel no registers;
@@ -561,6 +587,9 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
                     Vec<T, VEC> y = yt[idx / LPR][idx % LPR];
                     if constexpr (EPI)
                         if (epi) y = epi_piece<T, B, VEC>(y, Wp + (r0 + idx / LPR) * B, Ms, idx % LPR);
+                    if constexpr (AX3)
+                        y = ax3_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC,
+                                              Wp ? Wp + (r0 + idx / LPR) * B + (idx % LPR) * VEC : nullptr, ca, cc, cd);
                     stv<T, VEC>(Y + (r0 + idx / LPR) * ldy + (idx % LPR) * VEC, y);
                 }
             }
@@ -779,6 +808,9 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
         Vec<T, VEC> y = yt[idx / LPR][idx % LPR];
         if constexpr (EPI)
             if (epi) y = epi_piece<T, B, VEC>(y, Wp + (r0 + idx / LPR) * B, Ms, idx % LPR);
+        if constexpr (AX3)
+            y = ax3_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC,
+                                  Wp ? Wp + (r0 + idx / LPR) * B + (idx % LPR) * VEC : nullptr, ca, cc, cd);
         if constexpr (sizeof(T) * VEC == 16) {
             typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
             u32x4 u;
@@ -1402,7 +1434,8 @@ static int launch_seg_pf(lz_handle *h, int64_t n, const int64_t *rp, const int32
     // the tile kernel first (the two masked streams have queues of their own:
     // profiles/r06h_pf_trace.csv shows both kernels running at once)
     hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, false, 0, false, false, true>), dim3((unsigned)st), dim3(256), 0,
-                       h->pf_sg, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, nullptr, nullptr, 0, h->pf_ctl);
+                       h->pf_sg, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, nullptr, nullptr, 0, h->pf_ctl,
+                       T(0), T(0), T(0));
     // C = 0: the tile kernel alone on its CUs (the masked launch's own cost);
     // 8 blocks per prefetching CU (4 k CUs per XCD); a band wider than `span`
     // rows gets no X prefetch
@@ -1413,7 +1446,7 @@ static int launch_seg_pf(lz_handle *h, int64_t n, const int64_t *rp, const int32
                            (int64_t)h->pf_band);
     const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>(st, (int64_t)h->n_cu * 4));
     hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, false, 1>), dim3(g2), dim3(256), 0, h->pf_sg, n, rp, col, val, X, ldx,
-                       nx, Y, ldy, h->longq, parity, nullptr, nullptr, 0, nullptr);
+                       nx, Y, ldy, h->longq, parity, nullptr, nullptr, 0, nullptr, T(0), T(0), T(0));
     LZ_HIP_TRY(hipEventRecord(h->ev_pfg, h->pf_sg));
     LZ_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_pfg, 0));
     if (k > 0) {
@@ -1431,16 +1464,16 @@ static int launch_seg_pf(lz_handle *h, int64_t n, const int64_t *rp, const int32
 // (count slot plan_slot, *slot_out of that call, or a list spmm_b2_plan made
 // up front) -- the long-tile pass runs
 // first, on its own stream, beside the main kernel, which then only skips them.
-template <typename T, int B, int TR, int CAP, bool WIN, bool YCM = false, bool EPI = false>
+template <typename T, int B, int TR, int CAP, bool WIN, bool YCM = false, bool EPI = false, bool AX3 = false>
 static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, const T *val, const T *X,
                       int64_t ldx, int64_t nx, T *Y, int64_t ldy, const T *Wp = nullptr, const T *Mm = nullptr,
-                      int plan_slot = -1, int *slot_out = nullptr)
+                      int plan_slot = -1, int *slot_out = nullptr, T ca = T(0), T cc = T(0), T cd = T(0))
 {
     const int64_t st = ceil_div(n, (int64_t)TR);
     LZ_ARG_CHECK(st < (1LL << 31), "too many row tiles");
     LZ_TRY(ensure_longq(h, st));
     h->last_kernel[0] = (CAP == 768 ? LZ_K_SEG768 : CAP == 1024 ? LZ_K_SEG1024 : LZ_K_SEG1536) | (WIN ? LZ_K_WIN : 0) |
-                        (YCM ? LZ_K_YCM : 0) | (EPI ? LZ_K_EPI : 0);
+                        (YCM ? LZ_K_YCM : 0) | (EPI ? LZ_K_EPI : 0) | (AX3 ? LZ_K_AX3 : 0);
     if (plan_slot >= 0) {
         LZ_ARG_CHECK(plan_slot <= 1 && (size_t)st + 2 <= h->longq_cap, "planned SpMM: no earlier queue");
         if (!h->lstream) {
@@ -1451,16 +1484,18 @@ static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t 
         const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>(st, (int64_t)h->n_cu * 4));
         LZ_HIP_TRY(hipEventRecord(h->ev_lfork, h->stream));
         LZ_HIP_TRY(hipStreamWaitEvent(h->lstream, h->ev_lfork, 0));
-        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI>), dim3(g2), dim3(256), 0, h->lstream, n, rp,
-                           col, val, X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, Wp, Mm, 0, nullptr);
+        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI, false, AX3>), dim3(g2), dim3(256), 0,
+                           h->lstream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, Wp, Mm, 0, nullptr,
+                           ca, cc, cd);
         LZ_HIP_TRY(hipEventRecord(h->ev_ljoin, h->lstream));
-        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI>), dim3((unsigned)st), dim3(256), 0, h->stream,
-                           n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, Wp, Mm, 0, nullptr);
+        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI, false, AX3>), dim3((unsigned)st), dim3(256), 0,
+                           h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, Wp, Mm, 0, nullptr,
+                           ca, cc, cd);
         LZ_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_ljoin, 0));
         return LZ_OK;
     }
 #ifdef LZ_DIAG
-    if constexpr (!WIN && !YCM && !EPI) {
+    if constexpr (!WIN && !YCM && !EPI && !AX3) {
         int k = 0, C = 8, D = 96, span = 65536;
         if (pf_config(&k, &C, &D, &span) && (k > 0 || C == 0))
             return launch_seg_pf<T, B, TR, CAP>(h, n, rp, col, val, X, ldx, nx, Y, ldy, k, C, D, span);
@@ -1488,11 +1523,12 @@ static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t 
 #else
     constexpr int diag = 0;
 #endif
-    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI>), dim3((unsigned)st), dim3(256), 0, h->stream, n, rp,
-                       col, val, X, ldx, nx, Y, ldy, h->longq, parity, Wp, Mm, diag, nullptr);
+    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI, false, AX3>), dim3((unsigned)st), dim3(256), 0,
+                       h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, Wp, Mm, diag, nullptr, ca, cc,
+                       cd);
     const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>(st, (int64_t)h->n_cu * 4));
-    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI>), dim3(g2), dim3(256), 0, h->stream, n, rp, col, val,
-                       X, ldx, nx, Y, ldy, h->longq, parity, Wp, Mm, 0, nullptr);
+    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI, false, AX3>), dim3(g2), dim3(256), 0, h->stream, n,
+                       rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, Wp, Mm, 0, nullptr, ca, cc, cd);
     return LZ_OK;
 }
 
@@ -1689,6 +1725,59 @@ int spmm_rm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32
     }
     }
 }
+
+// The row-local pass of the two-launch three-term step: Y = a Y + c X + d Z over
+// nb = n b contiguous elements (ld = b), 64-bit indices; Z == nullptr: d == 0,
+// Z is never read.  The arithmetic of ax3_piece on the stored SpMM row.
+template <typename T>
+__global__ __launch_bounds__(256) void k_ax3_rows(int64_t nb, T a, T c, T d, const T *__restrict__ X,
+                                                  const T *__restrict__ Z, T *__restrict__ Y)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nb; i += (int64_t)gridDim.x * 256)
+        Y[i] = fma(a, Y[i], fma(c, X[i], Z ? d * Z[i] : T(0)));
+}
+
+// Y = a A X + c X + d Z (lz_csr_spmm_axpby): square operator, ld = b everywhere.
+// Fused into k_spmm_seg's store (AX3) under the conditions launch_spmm_rm picks
+// launch_seg<..., false> for: 128-B rows, X under 2 GiB / 2^24 rows, 16-B
+// aligned blocks.  fused = false (measurement, scripts/cheb_bench.py's two-launch
+// side) or any other shape: spmm_rm, then k_ax3_rows.
+template <typename T>
+int spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+               T a, const T *X, T c, T d, const T *Z, T *Y, bool fused)
+{
+    if (n <= 0) return LZ_OK;
+    if (d == T(0)) Z = nullptr;
+    const bool rows128 = (int64_t)b * (int64_t)sizeof(T) == 128;
+    const bool buf_ok = n * b * (int64_t)sizeof(T) < (1LL << 31) && n < (1 << 24);
+    const bool al16 = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) |
+                        reinterpret_cast<uintptr_t>(Z)) & 15) == 0;
+    const char *fz = getenv("LZ_SPMM_FNZ");  // (the fixed-nnz experiment has no fused store)
+    if (fused && rows128 && buf_ok && al16 && !(fz && fz[0] == '1')) {
+        constexpr int B = 128 / (int)sizeof(T);
+        const bool wide = (double)nnz > 13.0 * (double)n;
+        const int ev = prof_begin(h, PROF_SPMM);
+        const int rc = wide ? launch_seg<T, B, 48, 1536, false, false, false, true>(h, n, rp, col, val, X, B, n, Y, B,
+                                                                                    Z, nullptr, -1, nullptr, a, c, d)
+                            : launch_seg<T, B, 48, 768, false, false, false, true>(h, n, rp, col, val, X, B, n, Y, B, Z,
+                                                                                   nullptr, -1, nullptr, a, c, d);
+        prof_end(h, ev);
+        LZ_TRY(rc);
+        LZ_LAUNCH_CHECK();
+        return LZ_OK;
+    }
+    LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, X, b, n, Y, b));
+    const int64_t nb = n * b;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(nb, (int64_t)256), (int64_t)h->n_cu * 16));
+    hipLaunchKernelGGL((k_ax3_rows<T>), dim3(grid), dim3(256), 0, h->stream, nb, a, c, d, X, Z, Y);
+    LZ_LAUNCH_CHECK();
+    return LZ_OK;
+}
+
+template int spmm_axpby<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *, int,
+                                double, const double *, double, double, const double *, double *, bool);
+template int spmm_axpby<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
+                               float, const float *, float, float, const float *, float *, bool);
 
 // Column-major block (b columns, leading dimension ld) -> row-major (ld = b),
 // kCmRows rows per workgroup through LDS: the column reads and the row writes

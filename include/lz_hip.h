@@ -274,6 +274,54 @@ int lz_block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, const i
                                    int64_t lc, const void *sigma, void *q, void *alpha, void *beta, void *V,
                                    int64_t vstride, void *W, int passes);
 
+/* ------------------------------------ Chebyshev filter (no reference counterpart)
+ * Y = a (A X) + c X + d Z for a square operator: the three-term step of a
+ * polynomial recurrence in one call.  X, Z, Y: n x b row-major with ld = b,
+ * pairwise distinct (no in-place form), 1 <= b <= 64.  d == 0 never reads Z,
+ * which may then be NULL.  a, c, d are converted once to the solve's dtype and
+ * the stored row is fma(a, s, fma(c, x, d*z)) with s the finished SpMM row.
+ * 128-byte rows (b = 16 fp64, b = 32 fp32) with X under 2 GiB / 2^24 rows and
+ * 16-byte aligned blocks fuse the two extra terms into the SpMM's store
+ * (lz_debug_last_kernel: the SpMM id | LZ_K_AX3): one extra read of Z and of
+ * the row's own X piece.  Every other shape runs lz_csr_spmm into Y and then
+ * one row-local kernel over Y, X and Z (no flag). */
+int lz_csr_spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                      const void *val, lz_dtype dtype, int b, double a, const void *X, double c, double d,
+                      const void *Z, void *Y);
+
+/* The Zhou-Saad scaled Chebyshev filter p of degree `degree` on A: |p| <=
+ * 1 / |T_degree((ref - c0) / e)| on the damped interval [lo, hi] (c0 its
+ * centre, e its half width), p(ref) = 1, and p grows monotonically from the
+ * interval's edge towards ref and beyond.  1 <= degree <= 256, lo < hi, ref
+ * outside [lo, hi]; anything else is LZ_E_ARG.  [lo, hi] must enclose the whole
+ * unwanted part of the spectrum: p is unbounded outside it, on both sides. */
+typedef struct {
+    int degree;
+    double lo, hi, ref;
+} lz_cheb;
+/* Y = p(A) X in `degree` lz_csr_spmm_axpby calls: with sigma_1 = e / (ref - c0),
+ *   Y_1 = (sigma_1 / e) (A X - c0 X),
+ *   Y_i = (2 s' / e) (A Y_{i-1} - c0 Y_{i-1}) - s s' Y_{i-2},  s' = 1 / (2 / sigma_1 - s),
+ * the coefficients host doubles.  X (read only), Y: n x b row-major, ld = b;
+ * work: 2 n b elements (not read on entry); X, Y and work pairwise distinct.
+ * The three buffers {work_0, work_1, Y} rotate so that the last step lands in
+ * Y.  No host synchronisation. */
+int lz_cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                  const void *val, lz_dtype dtype, int b, const lz_cheb *f, const void *X, void *Y, void *work);
+/* lz_block_lanczos_reorth / lz_block_lanczos_reorth_resume on the operator
+ * p(A): every W = A Q_j of the solve becomes lz_cheb_apply (f, work as there;
+ * work distinct from B, W and the panel).  alpha, beta and the projected
+ * matrix are those of p(A); take eigenvalues of A back by Rayleigh-Ritz on A.
+ * f == NULL: exactly the launches of the unfiltered entry point (work unused). */
+int lz_block_lanczos_reorth_cheb(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr,
+                                 const int32_t *col, const void *val, lz_dtype dtype, int b, int m,
+                                 int64_t lc, const void *B, void *q, void *alpha, void *beta, void *V,
+                                 int64_t vstride, void *W, int passes, const lz_cheb *f, void *work);
+int lz_block_lanczos_reorth_resume_cheb(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr,
+                                        const int32_t *col, const void *val, lz_dtype dtype, int b, int r, int m,
+                                        int64_t lc, const void *sigma, void *q, void *alpha, void *beta, void *V,
+                                        int64_t vstride, void *W, int passes, const lz_cheb *f, void *work);
+
 /* Single-vector Lanczos.  Replaces vector_lanczos<T>(A, b, m, lc, q, alpha,
  * beta, q0, q1, w) (methods/vector_lanczos.hpp:8-67; the correct variant -- the
  * BLAS variant's axpy at :116 is a reference bug not reproduced).  alpha[m],
@@ -342,7 +390,7 @@ int lz_debug_last_wf(lz_handle *h, int out[2]);
  * b = 32 fp32 or generic-b solve), out[1]: its last Gram / tall-skinny-product
  * launch (lz_gram, lz_sym_cross_gram, lz_tsmm and the solves that call them);
  * 0: none yet.  SpMM ids: a kernel in the low byte, or-ed with the LZ_K_WIN /
- * LZ_K_YCM / LZ_K_EPI flags; LZ_K_SPMV carries its lanes per row in bits 16+. */
+ * LZ_K_YCM / LZ_K_EPI / LZ_K_AX3 flags; LZ_K_SPMV carries its lanes per row in bits 16+. */
 enum {
     LZ_K_SEG768 = 1,    /* nnz-split tiles, 768-entry stage (128-B rows, <= 13 nnz/row) */
     LZ_K_SEG1536 = 2,   /* ... 1536-entry stage (> 13 nnz/row) */
@@ -356,6 +404,7 @@ enum {
     LZ_K_WIN = 0x100,   /* windowed gather (X past 2 GiB / 2^24 rows) */
     LZ_K_YCM = 0x200,   /* column-major Y store */
     LZ_K_EPI = 0x400,   /* the beta^2 step's epilogue U = A X - Wp M */
+    LZ_K_AX3 = 0x800,   /* lz_csr_spmm_axpby's fused three-term store a A X + c X + d Z */
     LZ_K_GRAM16 = 1,    /* dense ids: b = 16 MFMA Gram (fp64 and fp32) */
     LZ_K_GRAM32F = 2,   /* b = 32 fp32 MFMA Gram */
     LZ_K_GRAM_GEN = 3,  /* any b, any pitch */

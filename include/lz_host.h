@@ -121,6 +121,13 @@ int lzh_ritz_pairs_dense(int m, int b, const double *T, const double *beta_m, in
 int lzh_restart_coeffs(int m, int b, int r, const double *T, const double *beta_m, int which,
                        double *theta_k, double *Z, double *sigma, double *T_next);
 int lzh_restart_fill(int r, int m, int b, const double *alpha, const double *beta, double *T_next);
+/* The Gershgorin enclosure of a square CSR operator's spectrum (symmetric: real):
+ * out[0] = min_i (a_ii - R_i), out[1] = max_i (a_ii + R_i), R_i the sum of
+ * |a_ij| over the row's off-diagonal entries; an empty row's disc is [0, 0].
+ * Guaranteed, unlike a Lanczos estimate of the far end: the bound a polynomial
+ * filter (lz_cheb in lz_hip.h) needs for the end of its damped interval.  fp64
+ * values; n >= 1.  Returns 0, or -1 on a bad argument. */
+int lzh_gershgorin(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val, double out[2]);
 /* solution = (expm(T_end T)[:, :b] beta_0)^T q  (test_lanczos.cu:272-286) */
 int lzh_block_solution(int m, int b, double T_end, const double *alpha, const double *beta,
                        const double *q, double *solution);
