@@ -28,20 +28,76 @@ int prof_begin(lz_handle *h, int cls)
     return idx;
 }
 
-int ensure_partials(lz_handle *h, size_t doubles)
-{
-    if (doubles <= h->partials_cap) return LZ_OK;
-    LZ_HIP_TRY(hipStreamSynchronize(h->stream));
-    LZ_HIP_TRY(hipFree(h->partials));
-    h->partials = nullptr;
-    LZ_HIP_TRY(hipMalloc(&h->partials, doubles * sizeof(double)));
-    h->partials_cap = doubles;
-    return LZ_OK;
-}
-
 void prof_end(lz_handle *h, int idx)
 {
     if (idx >= 0) (void)hipEventRecord(h->ev_pool[idx + 1], h->stream);
+}
+
+int grow_ws(lz_handle *h, void **buf, size_t *cap_bytes, size_t bytes)
+{
+    if (bytes <= *cap_bytes) return LZ_OK;
+    LZ_HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->xstream) LZ_HIP_TRY(hipStreamSynchronize(h->xstream));
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap_bytes = 0;
+    LZ_HIP_TRY(hipMalloc(buf, bytes));
+    *cap_bytes = bytes;
+    return LZ_OK;
+}
+
+int ensure_partials(lz_handle *h, size_t doubles)
+{
+    return grow_ws(h, &h->partials, &h->partials_cap, doubles * sizeof(double));
+}
+
+// Points h->stream at another stream for the scope's lifetime (the launch
+// wrappers all launch on h->stream) and restores it on every exit, an early
+// LZ_TRY return included.  prof_off: also no event brackets meanwhile (a
+// stream capture).
+struct StreamScope {
+    lz_handle *h;
+    hipStream_t saved;
+    bool prof;
+    StreamScope(lz_handle *h_, hipStream_t s, bool prof_off = false) : h(h_), saved(h_->stream), prof(h_->prof)
+    {
+        h->stream = s;
+        if (prof_off) h->prof = false;
+    }
+    ~StreamScope() { h->stream = saved, h->prof = prof; }
+    StreamScope(const StreamScope &) = delete;
+};
+
+// `other` continues behind what h->stream holds so far
+static int stream_fork(lz_handle *h, hipEvent_t ev, hipStream_t other)
+{
+    LZ_HIP_TRY(hipEventRecord(ev, h->stream));
+    LZ_HIP_TRY(hipStreamWaitEvent(other, ev, 0));
+    return LZ_OK;
+}
+
+// h->stream continues behind what `other` holds so far
+static int stream_join(lz_handle *h, hipEvent_t ev, hipStream_t other)
+{
+    LZ_HIP_TRY(hipEventRecord(ev, other));
+    LZ_HIP_TRY(hipStreamWaitEvent(h->stream, ev, 0));
+    return LZ_OK;
+}
+
+// Every return from the scope leaves the main stream behind the side stream's
+// last recorded h->ev_join (an early error return too: what the side stream
+// still runs must not race a later call).
+struct JoinSide {
+    lz_handle *h;
+    ~JoinSide() { (void)hipStreamWaitEvent(h->stream, h->ev_join, 0); }
+};
+
+// f(T{}) with T = double for LZ_F64 and float for every other dtype (entry
+// points that accept only the two check before they dispatch)
+template <typename F>
+static int by_dtype(lz_dtype dtype, F &&f)
+{
+    return dtype == LZ_F64 ? f(double{}) : f(float{});
 }
 
 void set_error(const char *fmt, ...)
@@ -182,16 +238,7 @@ static int reorth_reserve(lz_handle *h, int64_t n, int b, int m, int passes)
 {
     if (passes <= 0) return LZ_OK;
     LZ_TRY(panel_gram_reserve(h, n, b, m, std::is_same<T, double>::value));
-    const size_t need = sizeof(T) * (size_t)m * b * b;
-    if (need > h->coef_cap) {
-        LZ_HIP_TRY(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->coef);
-        h->coef = nullptr;
-        h->coef_cap = 0;
-        LZ_HIP_TRY(hipMalloc(&h->coef, need));
-        h->coef_cap = need;
-    }
-    return LZ_OK;
+    return grow_ws(h, &h->coef, &h->coef_cap, sizeof(T) * (size_t)m * b * b);
 }
 
 // `passes` rounds of classical Gram-Schmidt of W against the first k blocks
@@ -264,7 +311,7 @@ static int reorth_steps(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp,
                         int passes, const lz_cheb *f, T *work)
 {
     const int64_t bb = (int64_t)b * b;
-    T *binv = reinterpret_cast<T *>(h->scratch + 4 * kMaxB * kMaxB);
+    T *binv = ScratchT<T>(h, b).binv[0];
     int P = 0;
     for (int j = j0; j < m; ++j) {
         T *bj = beta + j * bb, *aj = alpha + j * bb;
@@ -290,7 +337,7 @@ static int block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int6
                                 const T *val, int b, int m, int64_t lc, const T *B, T *q, T *alpha, T *beta, T *V,
                                 int64_t vstride, T *W, int passes, const lz_cheb *f, T *work)
 {
-    T *binv = reinterpret_cast<T *>(h->scratch + 4 * kMaxB * kMaxB);
+    T *binv = ScratchT<T>(h, b).binv[0];
     LZ_TRY(reorth_reserve<T>(h, n, b, m, passes));
     int P = 0;
     T *Qj = V;
@@ -319,7 +366,7 @@ static int block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, con
                                        T *work)
 {
     const int64_t bb = (int64_t)b * b;
-    T *binv = reinterpret_cast<T *>(h->scratch + 4 * kMaxB * kMaxB);
+    T *binv = ScratchT<T>(h, b).binv[0];
     LZ_TRY(reorth_reserve<T>(h, n, b, m, passes));
     int P = 0;
     T *br = beta + r * bb, *ar = alpha + r * bb, *Qr = V + (int64_t)r * vstride;
@@ -370,22 +417,50 @@ static int pass1_plan(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, c
     return LZ_OK;
 }
 
-struct QfreeBufs {
-    double *binv[2], *P;
-    explicit QfreeBufs(lz_handle *h) : binv{h->scratch + 4 * 256, h->scratch + 5 * 256}, P(h->scratch + 6 * 256) {}
+// ---- pieces the step loops share
+// The Q-free loops' residual buffers: W_0 = B (read only); step j's output
+// goes to r0 at j = 0, r1 at j = 1 and from then on in place over W_{j-1}.
+// {r0, r1} = {W, Q1} for odd m, {Q1, W} for even m (residual_order), so the
+// last residual W_m lands in W.
+template <typename T>
+struct ResidualRing {
+    const T *in, *prev = nullptr;  // W_j, W_{j-1}
+    T *r0, *r1;
+    ResidualRing(const T *B, int m, T *W, T *Q1) : in(B), r0((m & 1) ? W : Q1), r1((m & 1) ? Q1 : W) {}
+    T *out(int j) const { return j == 0 ? r0 : j == 1 ? r1 : const_cast<T *>(prev); }
+    void advance(T *out) { prev = in, in = out; }
 };
+
+// beta[m] = the last step's inverse square root, as the reference's
+template <typename T>
+static int store_beta_m(lz_handle *h, T *beta, int m, int64_t bb, T *const binv[2])
+{
+    LZ_HIP_TRY(hipMemcpyAsync(beta + m * bb, binv[(m - 1) & 1], sizeof(T) * bb, hipMemcpyDeviceToDevice, h->stream));
+    return LZ_OK;
+}
+
+// the wavefront step's alpha products from the folded [S1 | S2 | G] at slab (lc: a local row, or -1)
+static WfAlpha wf_alpha(const double *slab, double *alpha, double *P2, const double *V, int64_t lc, double *qrow)
+{
+    return WfAlpha{slab, 1, alpha, P2, V, lc, qrow};
+}
+
+// fold one launch's P slab sets at h->partials2 into slab
+static int wf_fold_launch(lz_handle *h, int P, double *slab)
+{
+    WfSlabs sl;
+    sl.add(h->partials2, P);
+    return wf_fold16(h, sl, slab);
+}
 
 // B^T B's per-block slabs (b = 16 fp64) on the handle's side stream, forked
 // from the main stream; h->ev_join is recorded behind them (the caller waits on
 // it before the slabs are folded).
 static int gram_beside(lz_handle *h, int64_t n, const double *B, int *P)
 {
-    LZ_HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
-    LZ_HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-    std::swap(h->stream, h->side);  // gram_partials launches on h->stream
-    const int rc = gram_partials<double>(h, n, 16, B, B, 16, P);
-    std::swap(h->stream, h->side);
-    LZ_TRY(rc);
+    LZ_TRY(stream_fork(h, h->ev_fork, h->side));
+    StreamScope on_side(h, h->side);
+    LZ_TRY(gram_partials<double>(h, n, 16, B, B, 16, P));
     LZ_HIP_TRY(hipEventRecord(h->ev_join, h->side));
     return LZ_OK;
 }
@@ -401,9 +476,10 @@ static int block_lanczos_wf16(lz_handle *h, int64_t n, int64_t nnz, const int64_
 {
     constexpr int64_t bb = 256;
     (void)nnz;
-    double *binv[2] = {h->scratch + 4 * 256, h->scratch + 5 * 256};
-    double *P1 = h->scratch + 6 * 256, *P2 = h->scratch + 7 * 256;
-    double *slab = h->scratch + 8 * 256;  // [S1 | S2 | G], 768
+    const Scratch16 sc(h);
+    double *const *binv = sc.binv;
+    double *P1 = sc.P1, *P2 = sc.P2, *slab = sc.slab;  // slab: [S1 | S2 | G], 768
+    const int64_t lcl = (lc >= 0 && lc < n) ? lc : -1;
     int P = 0;
     const bool g0 = Pg < 0;  // beta_0's Gram from the first launch (wf_first_gram)
     // else B^T B's slabs (Pg of them) were made beside the plan (gram_beside)
@@ -413,17 +489,8 @@ static int block_lanczos_wf16(lz_handle *h, int64_t n, int64_t nnz, const int64_
     LZ_TRY(wf_step16(h, n, rp, col, pl.col16, val, pl.pairs, wp, nullptr, nullptr, g0 ? B : nullptr, nullptr,
                      nullptr, nullptr, nullptr, B, Q0, 0, &P));
     if (g0) {  // beta_0, its inverse, alpha_0, P2 and q_0 in one kernel, as every later step's
-        WfSlabs sl;
-        sl.add(h->partials2, P);
-        LZ_TRY(wf_fold16(h, sl, slab));
-        WfAlpha wa;
-        wa.part = slab;
-        wa.P = 1;
-        wa.alpha = alpha;
-        wa.P2 = P2;
-        wa.V = B;
-        wa.lc = (lc >= 0 && lc < n) ? lc : -1;
-        wa.qrow = q;
+        LZ_TRY(wf_fold_launch(h, P, slab));
+        const WfAlpha wa = wf_alpha(slab, alpha, P2, B, lcl, q);
         LZ_TRY(sqrtm_pair<double>(h, 16, nullptr, 1, beta, binv[0], nullptr, slab + 512, nullptr, nullptr, &wa));
     } else {
         LZ_TRY(alpha_wf16(h, h->partials2, P, binv[0], nullptr, alpha, P2, B, lc, n, q));
@@ -436,24 +503,14 @@ static int block_lanczos_wf16(lz_handle *h, int64_t n, int64_t nnz, const int64_
         // the block slabs folded by 12 workgroups (one workgroup reading all
         // 1.5 MB took ~20 us), then beta_{j+1}, its inverse and P1 = beta_j^-1
         // beta_{j+1} from G, and (same launch) alpha_{j+1}, P2 and the row probe
-        WfSlabs sl;
-        sl.add(h->partials2, P);
-        LZ_TRY(wf_fold16(h, sl, slab));
-        WfAlpha wa;
-        wa.part = slab;
-        wa.P = 1;
-        wa.alpha = alpha + (j + 1) * bb;
-        wa.P2 = P2;
-        wa.V = Vn;
-        wa.lc = (lc >= 0 && lc < n) ? lc : -1;
-        wa.qrow = q + (j + 1) * 16;
+        LZ_TRY(wf_fold_launch(h, P, slab));
+        const WfAlpha wa = wf_alpha(slab, alpha + (j + 1) * bb, P2, Vn, lcl, q + (j + 1) * 16);
         LZ_TRY(sqrtm_pair<double>(h, 16, nullptr, 1, beta + (j + 1) * bb, binv[(j + 1) & 1], nullptr, slab + 512,
                                   binv[j & 1], P1, &wa));
         Vm1 = V0;
         V0 = Vn;
     }
-    LZ_HIP_TRY(hipMemcpyAsync(beta + m * bb, binv[(m - 1) & 1], sizeof(double) * bb, hipMemcpyDeviceToDevice,
-                              h->stream));
+    LZ_TRY(store_beta_m<double>(h, beta, m, bb, binv));
     // the reference's post-call state: W_m = Y_{m-1} beta^-1 - V_{m-2} P1 -
     // V_{m-1} P2 (the pass 2 a further step would run), Q0 = Q1 = V_{m-1} beta^-1
     // (Q1 untouched at m = 1, as the reference's).  The default shape: one
@@ -479,7 +536,8 @@ static int block_lanczos_fused16(lz_handle *h, int64_t n, int64_t nnz, const int
 {
     constexpr int64_t bb = 256;
     (void)Q0;
-    QfreeBufs qb(h);
+    const Scratch16 qb(h);
+    double *const qP = qb.P1;  // P1 = beta_{j-1}^-1 beta_j, then (pass 1 has consumed it) P2 = beta_j^-1 alpha_j
     int P = 0;
     Pass1Plan pl;
     // B^T B (beta_0's Gram): where the wavefront step will run with a shape
@@ -489,12 +547,8 @@ static int block_lanczos_fused16(lz_handle *h, int64_t n, int64_t nnz, const int
     // its sqrtm
     const bool g0 = wf_first_gram(n, nnz);
     if (!g0) LZ_TRY(gram_beside(h, n, B, &P));
-    // every return from here on leaves the main stream behind the Gram (an early
-    // error return too: the side stream's slabs must not race a later call)
-    struct JoinSide {
-        lz_handle *h;
-        ~JoinSide() { (void)hipStreamWaitEvent(h->stream, h->ev_join, 0); }
-    } join_side{h};
+    // every return from here on leaves the main stream behind the Gram
+    JoinSide join_side{h};
     {
         WfPlan wp;
         LZ_TRY(wf_plan16(h, n, nnz, rp, col, &wp));  // n < 2^24 only
@@ -512,27 +566,24 @@ static int block_lanczos_fused16(lz_handle *h, int64_t n, int64_t nnz, const int
     LZ_TRY(pass1_plan(h, n, nnz, rp, col, n, 0, &pl));
     LZ_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
     LZ_TRY(sqrtm_pair<double>(h, 16, nullptr, P, beta, qb.binv[0], nullptr));
-    const double *in = B, *prev = nullptr;
-    double *r0 = (m & 1) ? W : Q1, *r1 = (m & 1) ? Q1 : W;  // W_m lands in W (residual_order)
+    ResidualRing<double> r(B, m, W, Q1);
     for (int j = 0; j < m; ++j) {
-        double *out = j == 0 ? r0 : j == 1 ? r1 : const_cast<double *>(prev);
+        double *out = r.out(j);
         const double *bi = qb.binv[j & 1];
-        LZ_TRY(fused_spmm16(h, n, rp, col, val, in, n, in, prev, out, bi, j ? qb.P : nullptr, lc, q + j * 16, &P,
+        LZ_TRY(fused_spmm16(h, n, rp, col, val, r.in, n, r.in, r.prev, out, bi, j ? qP : nullptr, lc, q + j * 16, &P,
                             pl.pairs, nnz, 0, pl.win, 0, pl.col16));
         // alpha_j and P2 = beta_j^-1 alpha_j in one kernel (P1 of this step is consumed)
-        LZ_TRY(gram_finish<double>(h, 16, P, 1, alpha + j * bb, h->partials2, bi, qb.P));
-        LZ_TRY(fused_update16(h, n, out, in, qb.P, &P));
+        LZ_TRY(gram_finish<double>(h, 16, P, 1, alpha + j * bb, h->partials2, bi, qP));
+        LZ_TRY(fused_update16(h, n, out, r.in, qP, &P));
         if (j + 1 < m)  // beta_{j+1}, its inverse and P1 = beta_j^-1 beta_{j+1}
             LZ_TRY(sqrtm_pair<double>(h, 16, nullptr, P, beta + (j + 1) * bb, qb.binv[(j + 1) & 1], nullptr,
-                                      nullptr, bi, qb.P));
-        prev = in;
-        in = out;
+                                      nullptr, bi, qP));
+        r.advance(out);
     }
-    LZ_HIP_TRY(hipMemcpyAsync(beta + m * bb, qb.binv[(m - 1) & 1], sizeof(double) * bb, hipMemcpyDeviceToDevice,
-                              h->stream));
+    LZ_TRY(store_beta_m<double>(h, beta, m, bb, qb.binv));
     if (h->final_state)  // W = W_m (in), Q0 = Q1 = W_{m-1} beta^-1 (prev)
-        LZ_TRY(final_state<double>(h, n, 16, nullptr, nullptr, prev, in, qb.binv[(m - 1) & 1], nullptr, nullptr, W,
-                                   Q0, m >= 2 ? Q1 : nullptr));
+        LZ_TRY(final_state<double>(h, n, 16, nullptr, nullptr, r.prev, r.in, qb.binv[(m - 1) & 1], nullptr, nullptr,
+                                   W, Q0, m >= 2 ? Q1 : nullptr));
     return LZ_OK;
 }
 
@@ -558,17 +609,15 @@ static int block_lanczos_b2_32(lz_handle *h, int64_t n, int64_t nnz, const int64
 {
     constexpr int b = 32;
     const int64_t bb = (int64_t)b * b;
-    float *sc = reinterpret_cast<float *>(h->scratch + 4 * kMaxB * kMaxB);
-    float *binv[2] = {sc, sc + bb}, *P2 = sc + 2 * bb, *M = sc + 3 * bb;
+    const ScratchT<float> sc(h, b);
+    float *const *binv = sc.binv;
+    float *P2 = sc.P, *M = sc.P3;
     float *U = Q0;
     // every return leaves the handle's stream behind the side stream's sqrtm
-    // of the next step's G: an early error return too.  (beta_0's Gram and
+    // of the next step's G.  (beta_0's Gram and
     // sqrtm beside step 0's SpMM measured a wash: the SpMM paid the Gram's
     // bandwidth, profiles/r05zzs_c5_gram0_beside_ab.log)
-    struct JoinSide {
-        lz_handle *h;
-        ~JoinSide() { (void)hipStreamWaitEvent(h->stream, h->ev_join, 0); }
-    } join_side{h};
+    JoinSide join_side{h};
     int np = 0, cap = 768, lslot = -1;
     LZ_TRY(spmm_b2_stage(h, n, rp, &cap));  // (the solve's one host sync, before any of its work)
 #ifndef LZ_B2_STEP0_QUEUES  // (measurement build: step 0 queues the list itself, as before round 5's end)
@@ -576,11 +625,11 @@ static int block_lanczos_b2_32(lz_handle *h, int64_t n, int64_t nnz, const int64
 #endif
     LZ_TRY(gram_partials<float>(h, n, b, B, B, b, &np));
     LZ_TRY(sqrtm_pair<float>(h, b, nullptr, np, beta, binv[0], nullptr));
-    const float *in = B, *prev = nullptr;
-    float *r0 = (m & 1) ? W : Q1, *r1 = (m & 1) ? Q1 : W;  // W_m lands in W (residual_order)
+    ResidualRing<float> r(B, m, W, Q1);
     for (int j = 0; j < m; ++j) {
-        float *out = j == 0 ? r0 : j == 1 ? r1 : const_cast<float *>(prev);
+        float *out = r.out(j);
         const float *bi = binv[j & 1];
+        const float *in = r.in, *prev = r.prev;
         // the long-tile pass beside the tile pass, over the solve's list (from
         // step 1 on: C5 step 4.401-4.411 -> 4.381-4.385 ms; step 0 too since
         // the list is made up front; each tile computed as before)
@@ -604,22 +653,17 @@ static int block_lanczos_b2_32(lz_handle *h, int64_t n, int64_t nnz, const int64
         if (j + 1 < m) {
             const int ng = fold_slabs_g(h, h->partials, np, (int)bb, 32);
             LZ_TRY(m_b2(h, h->partials2, ng, bi, M));  // M_{j+1} = beta_j^-1 G_{j+1}
-            LZ_HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
-            LZ_HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-            hipStream_t main = h->stream;
-            h->stream = h->side;
+            LZ_TRY(stream_fork(h, h->ev_fork, h->side));
+            StreamScope on_side(h, h->side);
             // (from the 32 folded slabs m_b2 read: the same G bits, and the
             // one-workgroup kernel pulls 256 KB instead of the passes' 8 MB)
-            const int rc = sqrtm_pair<float>(h, b, nullptr, ng, beta + (j + 1) * bb, binv[(j + 1) & 1], nullptr,
-                                             h->partials2);
-            h->stream = main;
-            LZ_TRY(rc);
+            LZ_TRY(sqrtm_pair<float>(h, b, nullptr, ng, beta + (j + 1) * bb, binv[(j + 1) & 1], nullptr,
+                                     h->partials2));
             LZ_HIP_TRY(hipEventRecord(h->ev_join, h->side));
         }
-        prev = in;
-        in = out;
+        r.advance(out);
     }
-    LZ_HIP_TRY(hipMemcpyAsync(beta + m * bb, binv[(m - 1) & 1], sizeof(float) * bb, hipMemcpyDeviceToDevice, h->stream));
+    LZ_TRY(store_beta_m<float>(h, beta, m, bb, binv));
     // (the post-call state: W = W_m is the last pass UB's output, in W by the
     // residual order, and that pass also wrote Q0 = Q1 = W_{m-1} beta^-1)
     return LZ_OK;
@@ -636,17 +680,18 @@ static int block_lanczos_sep(lz_handle *h, int64_t n, int64_t nnz, const int64_t
             return block_lanczos_b2_32(h, n, nnz, rp, col, val, m, lc, B, q, alpha, beta, Q0, Q1, W);
     }
     const int64_t bb = (int64_t)b * b;
-    T *sc = reinterpret_cast<T *>(h->scratch + 4 * kMaxB * kMaxB);
-    T *binv[2] = {sc, sc + bb}, *P = sc + 2 * bb;
+    const ScratchT<T> sc(h, b);
+    T *const *binv = sc.binv;
+    T *P = sc.P;
     T *Y = Q0;
     int np = 0;
     LZ_TRY(gram_partials<T>(h, n, b, B, B, b, &np));
     LZ_TRY(sqrtm_pair<T>(h, b, nullptr, np, beta, binv[0], nullptr));
-    const T *in = B, *prev = nullptr;
-    T *r0 = (m & 1) ? W : Q1, *r1 = (m & 1) ? Q1 : W;  // W_m lands in W (residual_order)
+    ResidualRing<T> r(B, m, W, Q1);
     for (int j = 0; j < m; ++j) {
-        T *out = j == 0 ? r0 : j == 1 ? r1 : const_cast<T *>(prev);
+        T *out = r.out(j);
         const T *bi = binv[j & 1];
+        const T *in = r.in, *prev = r.prev;
         // the SpMM gathers the unnormalised W_j: it needs no beta, so step j-1's
         // sqrtm runs beside it on the side stream; pass E waits for it
         LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, in, b, n, Y, b));
@@ -656,22 +701,16 @@ static int block_lanczos_sep(lz_handle *h, int64_t n, int64_t nnz, const int64_t
         LZ_TRY(gram_finish<T>(h, b, np, 1, alpha + j * bb, h->partials, bi, P));
         LZ_TRY(fused_u_sep<T>(h, n, b, out, in, P, &np));
         if (j + 1 < m) {  // beta_{j+1}, its inverse and P1 = beta_j^-1 beta_{j+1}, on the side stream
-            LZ_HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
-            LZ_HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-            hipStream_t main = h->stream;
-            h->stream = h->side;
-            const int rc = sqrtm_pair<T>(h, b, nullptr, np, beta + (j + 1) * bb, binv[(j + 1) & 1], nullptr, nullptr,
-                                         bi, P);
-            h->stream = main;
-            LZ_TRY(rc);
+            LZ_TRY(stream_fork(h, h->ev_fork, h->side));
+            StreamScope on_side(h, h->side);
+            LZ_TRY(sqrtm_pair<T>(h, b, nullptr, np, beta + (j + 1) * bb, binv[(j + 1) & 1], nullptr, nullptr, bi, P));
             LZ_HIP_TRY(hipEventRecord(h->ev_join, h->side));
         }
-        prev = in;
-        in = out;
+        r.advance(out);
     }
-    LZ_HIP_TRY(hipMemcpyAsync(beta + m * bb, binv[(m - 1) & 1], sizeof(T) * bb, hipMemcpyDeviceToDevice, h->stream));
+    LZ_TRY(store_beta_m<T>(h, beta, m, bb, binv));
     if (h->final_state)  // W = W_m (in), Q0 = Q1 = W_{m-1} beta^-1 (prev)
-        LZ_TRY(final_state<T>(h, n, b, nullptr, nullptr, prev, in, binv[(m - 1) & 1], nullptr, nullptr, W, Q0,
+        LZ_TRY(final_state<T>(h, n, b, nullptr, nullptr, r.prev, r.in, binv[(m - 1) & 1], nullptr, nullptr, W, Q0,
                               m >= 2 ? Q1 : nullptr));
     return LZ_OK;
 }
@@ -718,17 +757,14 @@ static int fdtd_block(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, c
     if (use_graph && steps - s >= 2 * kFdtdGraph) {
         hipStream_t cap = nullptr;
         LZ_HIP_TRY(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
-        const hipStream_t orig = h->stream;
-        const bool prof = h->prof;
-        h->stream = cap;
-        h->prof = false;
-        int rc = LZ_OK;
+        int rc = LZ_OK;  // (kept: the graph, its exec and the stream are destroyed on every path)
         hipGraph_t g = nullptr;
         hipGraphExec_t ge = nullptr;
         if (hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal) != hipSuccess) {
             set_error("fdtd: hipStreamBeginCapture failed");
             rc = LZ_E_HIP;
         } else {
+            StreamScope capturing(h, cap, true);  // no event brackets inside a capture
             for (int64_t k = 0; k < kFdtdGraph && rc == LZ_OK; ++k) rc = step();
             const hipError_t e = hipStreamEndCapture(cap, &g);
             if (rc == LZ_OK && e != hipSuccess) {
@@ -736,14 +772,12 @@ static int fdtd_block(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, c
                 rc = LZ_E_HIP;
             }
         }
-        h->stream = orig;
-        h->prof = prof;
         if (rc == LZ_OK && hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) {
             set_error("fdtd: hipGraphInstantiate failed");
             rc = LZ_E_HIP;
         }
         for (; rc == LZ_OK && steps - s >= kFdtdGraph; s += kFdtdGraph)
-            if (hipGraphLaunch(ge, orig) != hipSuccess) {
+            if (hipGraphLaunch(ge, h->stream) != hipSuccess) {
                 set_error("fdtd: hipGraphLaunch failed");
                 rc = LZ_E_HIP;
             }
@@ -834,20 +868,6 @@ static void detach_comm(lz_handle *h)
     h->nranks = 1;
     h->rank = 0;
     h->grid_cap = 0;
-}
-
-// grow a device workspace; never inside the steps (it synchronises)
-static int grow_ws(lz_handle *h, void **buf, size_t *cap, size_t bytes)
-{
-    if (bytes <= *cap) return LZ_OK;
-    LZ_HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->xstream) LZ_HIP_TRY(hipStreamSynchronize(h->xstream));
-    (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    LZ_HIP_TRY(hipMalloc(buf, bytes));
-    *cap = bytes;
-    return LZ_OK;
 }
 
 // rows idx[i] of X (rowb bytes each) packed one after another, V-sized pieces
@@ -944,7 +964,7 @@ static int split_plan(lz_handle *h, int64_t n, const int64_t *rp, const int32_t 
     sp->on = false;
     const char *e = getenv("LZ_DIST_OVERLAP");  // "0": exchange, then the whole pass (A/B)
     if ((e && e[0] == '0') || !h->comm || h->nranks < 2 || n < 64) return LZ_OK;
-    unsigned long long *d = reinterpret_cast<unsigned long long *>(h->scratch + 7 * kMaxB * kMaxB);
+    unsigned long long *d = ScratchSplit(h).words;
     hipLaunchKernelGGL(k_span_init, dim3(1), dim3(1), 0, h->stream, n, d);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, (int64_t)256), (int64_t)h->n_cu * 8));
     hipLaunchKernelGGL(k_local_span, dim3(grid), dim3(256), 0, h->stream, n, rp, col, lo, hi, d);
@@ -962,12 +982,41 @@ static int split_plan(lz_handle *h, int64_t n, const int64_t *rp, const int32_t 
     return LZ_OK;
 }
 
+// lz_debug_last_split
+static void record_split(lz_handle *h, const SplitPlan &sp)
+{
+    h->last_split[0] = sp.on ? sp.i0 : -1;
+    h->last_split[1] = sp.on ? sp.i1 : -1;
+}
+
 enum { kFormHalo = 0, kFormAllgather = 1 };
 
-static int dist_solve_wf16(lz_handle *h, int form, HaloPlan *hp, int64_t n, int64_t n_pad, int64_t nnz,
-                           const int64_t *rp, const int32_t *col, const double *val, int m, int64_t lc,
-                           const double *B, double *q, double *alpha, double *beta, double *X0, double *X1,
-                           const WfPlan &wp, const SplitPlan &sp, bool g0);
+// What both step forms of a distributed solve need of it, made once in dist_solve_impl.
+struct DistCtx {
+    lz_handle *h;
+    Comm *cm;
+    int form;
+    HaloPlan *hp;
+    int64_t n, n_pad;
+    int64_t nx;       // rows of the gather source
+    int64_t own_off;  // its row of local row 0 (the all-gather form's slot)
+    size_t rowb;      // bytes per row
+    double *slab;     // the reduced slab (ScratchT::slab), all-reduced in place
+    bool reduce;      // the sums cross ranks
+    bool ag() const { return form == kFormAllgather; }
+    int allreduce(size_t count) const { return reduce ? cm->allreduce_sum(slab, count, h->stream) : LZ_OK; }
+    // completes the gather source X on stream s: its halo rows from their
+    // owners, or (all-gather form, X = X_full) the peers' slots
+    int exchange(void *X, hipStream_t s) const
+    {
+        if (ag()) return cm ? cm->allgather(static_cast<char *>(X) + own_off * rowb, X, (size_t)n_pad * rowb, s) : LZ_OK;
+        return hp ? halo_exchange(h, *hp, X, rowb, s) : LZ_OK;
+    }
+};
+
+static int dist_solve_wf16(const DistCtx &cx, const int64_t *rp, const int32_t *col, const double *val, int m,
+                           int64_t lc, const double *B, double *q, double *alpha, double *beta, double *X0, double *X1,
+                           const WfPlan &wp, const SplitPlan &sp, bool g0, const uint64_t *pairs);
 
 // The distributed iteration, both exchange forms, any b <= 32, fp64 / fp32.
 //   b = 16 fp64: the fused Q-free passes of block_lanczos_fused16 (pass 1 =
@@ -999,10 +1048,12 @@ static int dist_solve_impl(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
     const size_t rowb = sizeof(T) * (size_t)b;
     const int64_t nx = ag ? n_pad * h->nranks : n + (hp ? hp->n_halo : 0);
     const int64_t own_off = ag ? (int64_t)h->rank * n_pad : 0;
-    double *slab = h->scratch;  // the reduced b x b slab (fp64), all-reduced in place
-    T *sc = reinterpret_cast<T *>(h->scratch + 4 * kMaxB * kMaxB);
-    T *binv[2] = {sc, sc + bb}, *P = sc + 2 * bb;
+    const ScratchT<T> sc(h, b);
+    double *slab = sc.slab;  // the reduced b x b slab (fp64), all-reduced in place
+    T *const *binv = sc.binv;
+    T *P = sc.P;
     T *own = X0 + own_off * b;  // allgather: this rank's slot of X_full
+    DistCtx cx{h, cm, form, hp, n, n_pad, nx, own_off, rowb, slab, cm && h->nranks > 1};
     // ---- once per solve (before any step: these may synchronise).  Every
     // set-up step that can fail runs before the solve's first collective, the
     // ranks' vote below: a rank whose set-up failed still joins it, with
@@ -1011,11 +1062,9 @@ static int dist_solve_impl(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
     int prc = h->dbg_setup_fail;  // lz_debug_fail_next_setup (test support), consumed here
     h->dbg_setup_fail = 0;
     if (prc != LZ_OK) set_error("set-up failure forced by lz_debug_fail_next_setup");
-    T *Y = nullptr;
-    if (prc == LZ_OK && !f16) {
-        prc = grow_ws(h, &h->ybuf, &h->ybuf_cap, (size_t)std::max<int64_t>(n, 1) * rowb);
-        Y = static_cast<T *>(h->ybuf);
-    }
+    // the local SpMM result (the b = 16 fp64 two-pass form has none)
+    auto reserve_y = [&]() -> int { return grow_ws(h, &h->ybuf, &h->ybuf_cap, (size_t)std::max<int64_t>(n, 1) * rowb); };
+    if (prc == LZ_OK && !f16) prc = reserve_y();
     if (prc == LZ_OK && !ag && hp && cm && h->nranks > 1)
         prc = grow_ws(h, &hp->sendbuf, &hp->send_cap, (size_t)std::max<int64_t>(hp->n_send, 1) * rowb);
     // the wavefront step when it applies (LZ_PASS_WF=0: the two passes).  The
@@ -1044,6 +1093,12 @@ static int dist_solve_impl(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
         return LZ_OK;
     };
     bool planned_twopass = false;
+    // the wavefront form's own set-up, before the vote like every step that can
+    // fail: its Y (if peers then vote the form down, ybuf was grown and goes
+    // unused) and the strips' row orders
+    const uint64_t *wf_pairs = nullptr;
+    if (prc == LZ_OK && try_wf && wp.ok) prc = reserve_y();
+    if (prc == LZ_OK && try_wf && wp.ok) prc = strip_pairs(h, n, rp, &wf_pairs);
     if (prc == LZ_OK && try_wf && wp.ok) prc = split_plan(h, n, rp, col, own_off, own_off + n, &sp);
     if (prc == LZ_OK && !(try_wf && wp.ok)) {
         prc = plan_twopass();
@@ -1076,20 +1131,18 @@ static int dist_solve_impl(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
             h->last_wf = wp.ok ? 1 : 0;
             h->last_wf_pre = 0;
             if (wp.ok) {
-                h->last_split[0] = sp.on ? sp.i0 : -1;
-                h->last_split[1] = sp.on ? sp.i1 : -1;
-                return dist_solve_wf16(h, form, hp, n, n_pad, nnz, rp, col, val, m, lc, B, q, alpha, beta, X0, X1,
-                                       wp, sp, g0);
+                record_split(h, sp);
+                return dist_solve_wf16(cx, rp, col, val, m, lc, B, q, alpha, beta, X0, X1, wp, sp, g0, wf_pairs);
             }
         }
     }
     h->last_wf = h->last_wf_pre = 0;
     // (only where a peer turned the wavefront form down after this rank planned it)
     if (!planned_twopass) LZ_TRY(plan_twopass());
-    h->last_split[0] = sp.on ? sp.i0 : -1;
-    h->last_split[1] = sp.on ? sp.i1 : -1;
-    const bool reduce = cm && (ag || h->nranks > 1);
-    auto allreduce = [&]() -> int { return reduce ? cm->allreduce_sum(slab, (size_t)bb, h->stream) : LZ_OK; };
+    record_split(h, sp);
+    T *Y = f16 ? nullptr : static_cast<T *>(h->ybuf);
+    cx.reduce = cm && (ag || h->nranks > 1);  // (the two-pass all-gather form all-reduces at one rank too)
+    auto allreduce = [&]() -> int { return cx.allreduce((size_t)bb); };
     // step jj's buffers
     auto gsrc = [&](int jj) -> T * { return ag ? X0 : (jj & 1 ? X1 : X0); };       // gather source, W_jj in own rows
     auto wj = [&](int jj) -> T * { return ag ? own : gsrc(jj); };                   // W_jj's own rows
@@ -1113,10 +1166,7 @@ static int dist_solve_impl(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
         return LZ_OK;
     };
     // the exchange that completes step jj's gather source (W_jj in own rows)
-    auto exchange = [&](int jj, hipStream_t s) -> int {
-        if (ag) return cm->allgather(own, X0, (size_t)n_pad * rowb, s);
-        return hp ? halo_exchange(h, *hp, gsrc(jj), rowb, s) : LZ_OK;
-    };
+    auto exchange = [&](int jj, hipStream_t s) -> int { return cx.exchange(gsrc(jj), s); };
     // ---- beta_0 from the global Gram of B, W_0 = B into the gather source
     int np = 0;
     LZ_TRY(gram_partials<T>(h, n, b, B, B, b, &np));
@@ -1167,8 +1217,7 @@ static int dist_solve_impl(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
             // beta_{j+1}, its inverse and P1 = beta_j^-1 beta_{j+1}
             LZ_TRY(sqrtm_pair<T>(h, b, nullptr, 1, beta + (j + 1) * bb, binv[(j + 1) & 1], nullptr, slab, bi, P));
             if (sp.on) {
-                LZ_HIP_TRY(hipEventRecord(h->ev_cx, h->stream));
-                LZ_HIP_TRY(hipStreamWaitEvent(h->xstream, h->ev_cx, 0));
+                LZ_TRY(stream_fork(h, h->ev_cx, h->xstream));
                 LZ_TRY(exchange(j + 1, h->xstream));
                 LZ_HIP_TRY(hipEventRecord(h->ev_xd, h->xstream));
                 nslab = 0;
@@ -1179,7 +1228,7 @@ static int dist_solve_impl(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
             }
         }
     }
-    LZ_HIP_TRY(hipMemcpyAsync(beta + m * bb, binv[(m - 1) & 1], sizeof(T) * bb, hipMemcpyDeviceToDevice, h->stream));
+    LZ_TRY(store_beta_m<T>(h, beta, m, bb, binv));
     if (cm) LZ_TRY(cm->fence(h->stream));  // no peer reads this rank's buffers after the call
     return LZ_OK;
 }
@@ -1202,28 +1251,29 @@ static int dist_solve_impl(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
 // n_pad holds V_j; X1 = W (n_pad rows) holds V_{j-1}: the step launch's pass 2
 // writes V_{j+1} into the slot and V_j into W (SW), then the in-place
 // all-gather, then the boundary tiles.
-static int dist_solve_wf16(lz_handle *h, int form, HaloPlan *hp, int64_t n, int64_t n_pad, int64_t nnz,
-                           const int64_t *rp, const int32_t *col, const double *val, int m, int64_t lc,
-                           const double *B, double *q, double *alpha, double *beta, double *X0, double *X1,
-                           const WfPlan &wp, const SplitPlan &sp, bool g0)
+// Y and the strips' row orders (pairs) are the caller's, made before the ranks'
+// vote: nothing here allocates or synchronises the host before the first
+// collective.
+static int dist_solve_wf16(const DistCtx &cx, const int64_t *rp, const int32_t *col, const double *val, int m,
+                           int64_t lc, const double *B, double *q, double *alpha, double *beta, double *X0, double *X1,
+                           const WfPlan &wp, const SplitPlan &sp, bool g0, const uint64_t *pairs)
 {
-    Comm *cm = h->comm;
+    lz_handle *h = cx.h;
+    Comm *cm = cx.cm;
+    HaloPlan *hp = cx.hp;
     constexpr int64_t bb = 256;
-    const size_t rowb = 128;
-    const bool ag = form == kFormAllgather;
-    const int64_t nx = ag ? n_pad * h->nranks : n + (hp ? hp->n_halo : 0);
-    const int64_t own_off = ag ? (int64_t)h->rank * n_pad : 0;
+    const bool ag = cx.ag();
+    const int64_t n = cx.n, nx = cx.nx;
+    const size_t rowb = cx.rowb;
     const int64_t T = ceil_div(n, (int64_t)wp.tr);
-    double *slab = h->scratch;  // [S1 | S2 | G], all-reduced in place
-    double *sc = h->scratch + 4 * kMaxB * kMaxB;
-    double *binv[2] = {sc, sc + bb}, *P1 = sc + 2 * bb, *P2 = sc + 3 * bb;
-    (void)nnz;
-    LZ_ARG_CHECK(wp.xoff == own_off, "wavefront plan for another slot (internal)");
-    LZ_TRY(grow_ws(h, &h->ybuf, &h->ybuf_cap, (size_t)std::max<int64_t>(n, 1) * rowb));
+    const ScratchT<double> sc(h, 16);
+    double *slab = sc.slab;  // [S1 | S2 | G], all-reduced in place
+    double *const *binv = sc.binv;
+    double *P1 = sc.P, *P2 = sc.P3;
+    LZ_ARG_CHECK(wp.xoff == cx.own_off, "wavefront plan for another slot (internal)");
+    LZ_ARG_CHECK(rowb == 128 && h->ybuf_cap >= (size_t)n * rowb && pairs, "wavefront form: set-up missing (internal)");
     double *Y = static_cast<double *>(h->ybuf);
-    const uint64_t *pairs = nullptr;
-    LZ_TRY(strip_pairs(h, n, rp, &pairs));
-    double *slot = X0 + own_off * 16;  // all-gather: this rank's rows of X_full
+    double *slot = X0 + cx.own_off * 16;  // all-gather: this rank's rows of X_full
     // interior pass-1 tiles: inside the split plan's interior rows (every tile
     // when no column leaves the rank's rows)
     const bool exch = h->nranks > 1 && (ag || (hp && hp->n_halo > 0));
@@ -1246,12 +1296,6 @@ static int dist_solve_wf16(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
         pre = st - sh >= T / 4;
     }
     h->last_wf_pre = pre ? 1 : 0;
-    const bool reduce = cm && h->nranks > 1;
-    auto allreduce = [&](size_t cnt) -> int { return reduce ? cm->allreduce_sum(slab, cnt, h->stream) : LZ_OK; };
-    auto exchange = [&](double *X, hipStream_t s) -> int {
-        if (ag) return cm ? cm->allgather(slot, X0, (size_t)n_pad * rowb, s) : LZ_OK;
-        return hp ? halo_exchange(h, *hp, X, rowb, s) : LZ_OK;
-    };
     const int64_t lcl = (lc >= 0 && lc < n) ? lc : -1;
     // ---- beta_0 from the global Gram of B: g0 (every rank on the default
     // shape), summed by the first launch's consumers
@@ -1262,36 +1306,25 @@ static int dist_solve_wf16(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
         int np = 0;
         LZ_TRY(gram_partials<double>(h, n, 16, B, B, 16, &np));
         LZ_TRY(gram_finish<double>(h, 16, np, 0, slab));
-        LZ_TRY(allreduce(bb));
+        LZ_TRY(cx.allreduce(bb));
         LZ_TRY(sqrtm_pair<double>(h, 16, nullptr, 1, beta, binv[0], nullptr, slab));
     }
     if (ag) {
-        if (cm) LZ_TRY(cm->allgather(B, X0, (size_t)n_pad * rowb, h->stream));
+        if (cm) LZ_TRY(cm->allgather(B, X0, (size_t)cx.n_pad * rowb, h->stream));
         else LZ_HIP_TRY(hipMemcpyAsync(slot, B, (size_t)n * rowb, hipMemcpyDeviceToDevice, h->stream));
     } else {
         LZ_HIP_TRY(hipMemcpyAsync(X0, B, (size_t)n * rowb, hipMemcpyDeviceToDevice, h->stream));
-        LZ_TRY(exchange(X0, h->stream));
+        LZ_TRY(cx.exchange(X0, h->stream));
     }
     LZ_TRY(wf_reset16(h, n, wp));
     // ---- Y_0 = A V_0 (pass 1 only, every tile; g0: and G_0), alpha_0
     int G = 0;
     LZ_TRY(wf_step16(h, n, rp, col, wp.col16, val, pairs, wp, nullptr, nullptr, g0 ? X0 : nullptr, nullptr, nullptr,
                      nullptr, nullptr, X0, Y, 0, &G, nx, 0, T, h->partials2));
-    {
-        WfSlabs sl;
-        sl.add(h->partials2, G);
-        LZ_TRY(wf_fold16(h, sl, slab));
-    }
-    LZ_TRY(allreduce(3 * bb));
+    LZ_TRY(wf_fold_launch(h, G, slab));
+    LZ_TRY(cx.allreduce(3 * bb));
     if (g0) {  // beta_0, its inverse, alpha_0, P2 and q_0 in one kernel
-        WfAlpha wa;
-        wa.part = slab;
-        wa.P = 1;
-        wa.alpha = alpha;
-        wa.P2 = P2;
-        wa.V = ag ? slot : X0;
-        wa.lc = lcl;
-        wa.qrow = q;
+        const WfAlpha wa = wf_alpha(slab, alpha, P2, ag ? slot : X0, lcl, q);
         LZ_TRY(sqrtm_pair<double>(h, 16, nullptr, 1, beta, binv[0], nullptr, slab + 2 * bb, nullptr, nullptr, &wa));
     } else {
         LZ_TRY(alpha_wf16(h, slab, 1, binv[0], nullptr, alpha, P2, ag ? slot : X0, lcl, n, q));
@@ -1316,9 +1349,8 @@ static int dist_solve_wf16(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
                              j ? P1 : nullptr, P2, Vg, Y, j + 1, &Gp, nx, 0, 0, part, qa, Vsave));
             sl.add(part, Gp);
             part += 3 * (int64_t)Gp * 256;
-            LZ_HIP_TRY(hipEventRecord(h->ev_cx, h->stream));
-            LZ_HIP_TRY(hipStreamWaitEvent(h->xstream, h->ev_cx, 0));
-            LZ_TRY(exchange(Vn, h->xstream));
+            LZ_TRY(stream_fork(h, h->ev_cx, h->xstream));
+            LZ_TRY(cx.exchange(Vg, h->xstream));
             LZ_HIP_TRY(hipEventRecord(h->ev_xd, h->xstream));
         }
         // the step launch: pass 2 (the other tiles) + pass 1 of the interior tiles
@@ -1334,22 +1366,20 @@ static int dist_solve_wf16(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
             // with no waits inside: run one after the other they cost a launch
             // ramp and tail more per step)
             if (pre) LZ_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_xd, 0));
-            else LZ_TRY(exchange(Vn, h->stream));
+            else LZ_TRY(cx.exchange(Vg, h->stream));
             const bool two = t0 > 0 && t1 < T;
-            if (two) LZ_HIP_TRY(hipEventRecord(h->ev_cx, h->stream));
+            if (two) LZ_TRY(stream_fork(h, h->ev_cx, h->xstream));
             LZ_TRY(wf_step16(h, n, rp, col, wp.col16, val, pairs, wp, nullptr, nullptr, nullptr, nullptr, nullptr,
                              nullptr, nullptr, Vg, Y, 0, &G1, nx, 0, t0, part));
             sl.add(part, G1);
             part += 3 * (int64_t)G1 * 256;
             if (two) {
-                LZ_HIP_TRY(hipStreamWaitEvent(h->xstream, h->ev_cx, 0));
-                std::swap(h->stream, h->xstream);  // wf_step16 launches on h->stream
-                const int rc = wf_step16(h, n, rp, col, wp.col16, val, pairs, wp, nullptr, nullptr, nullptr, nullptr,
-                                         nullptr, nullptr, nullptr, Vg, Y, 0, &G2, nx, t1, T, part);
-                std::swap(h->stream, h->xstream);
-                LZ_TRY(rc);
-                LZ_HIP_TRY(hipEventRecord(h->ev_bd, h->xstream));
-                LZ_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_bd, 0));
+                {
+                    StreamScope on_x(h, h->xstream);
+                    LZ_TRY(wf_step16(h, n, rp, col, wp.col16, val, pairs, wp, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr, nullptr, nullptr, Vg, Y, 0, &G2, nx, t1, T, part));
+                }
+                LZ_TRY(stream_join(h, h->ev_bd, h->xstream));
             } else {
                 LZ_TRY(wf_step16(h, n, rp, col, wp.col16, val, pairs, wp, nullptr, nullptr, nullptr, nullptr, nullptr,
                                  nullptr, nullptr, Vg, Y, 0, &G2, nx, t1, T, part));
@@ -1357,22 +1387,14 @@ static int dist_solve_wf16(lz_handle *h, int form, HaloPlan *hp, int64_t n, int6
             sl.add(part, G2);
         }
         LZ_TRY(wf_fold16(h, sl, slab));
-        LZ_TRY(allreduce(3 * bb));
-        WfAlpha wa;
-        wa.part = slab;
-        wa.P = 1;
-        wa.alpha = alpha + (j + 1) * bb;
-        wa.P2 = P2;
-        wa.V = Vn;
-        wa.lc = lcl;
-        wa.qrow = q + (j + 1) * 16;
+        LZ_TRY(cx.allreduce(3 * bb));
+        const WfAlpha wa = wf_alpha(slab, alpha + (j + 1) * bb, P2, Vn, lcl, q + (j + 1) * 16);
         LZ_TRY(sqrtm_pair<double>(h, 16, nullptr, 1, beta + (j + 1) * bb, binv[(j + 1) & 1], nullptr, slab + 2 * bb,
                                   binv[j & 1], P1, &wa));
         Vm1 = V0;
         V0 = Vn;
     }
-    LZ_HIP_TRY(hipMemcpyAsync(beta + m * bb, binv[(m - 1) & 1], sizeof(double) * bb, hipMemcpyDeviceToDevice,
-                              h->stream));
+    LZ_TRY(store_beta_m<double>(h, beta, m, bb, binv));
     if (cm) LZ_TRY(cm->fence(h->stream));  // no peer reads this rank's buffers after the call
     return LZ_OK;
 }
@@ -1455,22 +1477,21 @@ static int init_handle(lz_handle *h, int device)
         return LZ_E_HIP;
     }
     h->n_cu = prop.multiProcessorCount;
-    h->partials_cap = (size_t)kMaxPartials * kMaxB * kMaxB;
-    LZ_HIP_TRY(hipMalloc(&h->partials, sizeof(double) * h->partials_cap));
-    LZ_HIP_TRY(hipMalloc(&h->partials2, sizeof(double) * (256 * kMaxB * kMaxB + 4096 * 256)));
-    LZ_HIP_TRY(hipMalloc(&h->scratch, sizeof(double) * 8 * kMaxB * kMaxB));
-    LZ_HIP_TRY(hipMalloc(&h->err_flag, 64));
+    LZ_TRY(ensure_partials(h, (size_t)kMaxPartials * kMaxB * kMaxB));
+    LZ_HIP_TRY(hipMalloc(&h->partials2, sizeof(double) * kPartials2Doubles));
+    LZ_HIP_TRY(hipMalloc(&h->scratch, sizeof(double) * kScratchDoubles));
+    LZ_HIP_TRY(hipMalloc(&h->err_flag, sizeof(int) * kFlagWords));
     // (every fill below is stream-ordered and waited for here: later work runs
     // on whatever stream lz_set_stream names, which need not order against the
     // null stream a plain hipMemset uses)
-    LZ_HIP_TRY(hipMemsetAsync(h->err_flag, 0, 64, h->stream));
+    LZ_HIP_TRY(hipMemsetAsync(h->err_flag, 0, sizeof(int) * kFlagWords, h->stream));
     LZ_HIP_TRY(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
     LZ_HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     LZ_HIP_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     if (const char *pz = getenv("LZ_POISON"); pz && pz[0] == '1') {  // test support: NaN-filled workspaces
-        LZ_HIP_TRY(hipMemsetAsync(h->partials, 0xFF, sizeof(double) * h->partials_cap, h->stream));
-        LZ_HIP_TRY(hipMemsetAsync(h->partials2, 0xFF, sizeof(double) * (256 * kMaxB * kMaxB + 4096 * 256), h->stream));
-        LZ_HIP_TRY(hipMemsetAsync(h->scratch, 0xFF, sizeof(double) * 8 * kMaxB * kMaxB, h->stream));
+        LZ_HIP_TRY(hipMemsetAsync(h->partials, 0xFF, h->partials_cap, h->stream));
+        LZ_HIP_TRY(hipMemsetAsync(h->partials2, 0xFF, sizeof(double) * kPartials2Doubles, h->stream));
+        LZ_HIP_TRY(hipMemsetAsync(h->scratch, 0xFF, sizeof(double) * kScratchDoubles, h->stream));
     }
     LZ_HIP_TRY(hipStreamSynchronize(h->stream));
     return LZ_OK;
@@ -1575,9 +1596,9 @@ int lz_debug_poison_lds(lz_handle *h, uint32_t pattern)
     LZ_LAUNCH_CHECK();
     // and the handle's slab / scratch workspaces (nothing may read them before writing)
     const int byte = (int)(pattern & 0xFF);
-    LZ_HIP_TRY(hipMemsetAsync(h->partials, byte, sizeof(double) * h->partials_cap, h->stream));
-    LZ_HIP_TRY(hipMemsetAsync(h->partials2, byte, sizeof(double) * (256 * kMaxB * kMaxB + 4096 * 256), h->stream));
-    LZ_HIP_TRY(hipMemsetAsync(h->scratch, byte, sizeof(double) * 8 * kMaxB * kMaxB, h->stream));
+    LZ_HIP_TRY(hipMemsetAsync(h->partials, byte, h->partials_cap, h->stream));
+    LZ_HIP_TRY(hipMemsetAsync(h->partials2, byte, sizeof(double) * kPartials2Doubles, h->stream));
+    LZ_HIP_TRY(hipMemsetAsync(h->scratch, byte, sizeof(double) * kScratchDoubles, h->stream));
     return LZ_OK;
 }
 
@@ -1639,34 +1660,35 @@ int lz_csr_spmm(lz_handle *h, int64_t n_rows, int64_t n_cols, int64_t nnz, const
     LZ_ARG_CHECK(X && Y, "X/Y NULL");
     if (layout == LZ_ROW_MAJOR) {
         LZ_ARG_CHECK(ldx >= b && ldy >= b, "row-major ld >= b");
-        if (dtype == LZ_F64)
-            return spmm_rm<double>(h, n_rows, nnz, rp, col, (const double *)val, b, (const double *)X,
-                                   ldx, n_cols, (double *)Y, ldy);
-        return spmm_rm<float>(h, n_rows, nnz, rp, col, (const float *)val, b, (const float *)X, ldx,
-                              n_cols, (float *)Y, ldy);
+    } else {
+        LZ_ARG_CHECK(ldx >= n_cols && ldy >= n_rows, "column-major ld >= rows");
     }
-    LZ_ARG_CHECK(ldx >= n_cols && ldy >= n_rows, "column-major ld >= rows");
-    if (dtype == LZ_F64)
-        return spmm_cm<double>(h, n_rows, nnz, rp, col, (const double *)val, b, (const double *)X, ldx, n_cols,
-                               (double *)Y, ldy);
-    return spmm_cm<float>(h, n_rows, nnz, rp, col, (const float *)val, b, (const float *)X, ldx, n_cols,
-                          (float *)Y, ldy);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const T *v = (const T *)val, *x = (const T *)X;
+        if (layout == LZ_ROW_MAJOR) return spmm_rm<T>(h, n_rows, nnz, rp, col, v, b, x, ldx, n_cols, (T *)Y, ldy);
+        return spmm_cm<T>(h, n_rows, nnz, rp, col, v, b, x, ldx, n_cols, (T *)Y, ldy);
+    });
 }
 
 int lz_to_row_major(lz_handle *h, int64_t rows, int b, lz_dtype dtype, const void *X, int64_t ldx, void *Y)
 {
     LZ_HANDLE_CHECK(h);
     LZ_ARG_CHECK(X && Y && X != Y, "to_row_major: X, Y distinct, not NULL");
-    if (dtype == LZ_F64) return to_row_major<double>(h, rows, b, (const double *)X, ldx, (double *)Y);
-    return to_row_major<float>(h, rows, b, (const float *)X, ldx, (float *)Y);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return to_row_major<T>(h, rows, b, (const T *)X, ldx, (T *)Y);
+    });
 }
 
 int lz_to_col_major(lz_handle *h, int64_t rows, int b, lz_dtype dtype, const void *X, void *Y, int64_t ldy)
 {
     LZ_HANDLE_CHECK(h);
     LZ_ARG_CHECK(X && Y && X != Y, "to_col_major: X, Y distinct, not NULL");
-    if (dtype == LZ_F64) return to_col_major<double>(h, rows, b, (const double *)X, ldy, (double *)Y);
-    return to_col_major<float>(h, rows, b, (const float *)X, ldy, (float *)Y);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return to_col_major<T>(h, rows, b, (const T *)X, ldy, (T *)Y);
+    });
 }
 
 int lz_csr_spmv(lz_handle *h, int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t *rp,
@@ -1676,23 +1698,22 @@ int lz_csr_spmv(lz_handle *h, int64_t n_rows, int64_t n_cols, int64_t nnz, const
     LZ_TRY(check_csr(n_rows, nnz, rp, col, val));
     LZ_ARG_CHECK(x && y, "x/y NULL");
     (void)n_cols;
-    if (dtype == LZ_F64)
-        return spmv<double>(h, n_rows, rp, col, (const double *)val, (const double *)x,
-                            (double *)y, nnz);
-    return spmv<float>(h, n_rows, rp, col, (const float *)val, (const float *)x, (float *)y, nnz);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return spmv<T>(h, n_rows, rp, col, (const T *)val, (const T *)x, (T *)y, nnz);
+    });
 }
 
 int lz_gram(lz_handle *h, int64_t n, int b, lz_dtype dtype, const void *W, int64_t ld, void *R)
 {
     LZ_HANDLE_CHECK(h);
     LZ_ARG_CHECK(W && R && b >= 1 && b <= kMaxB && ld >= b && n >= 0, "gram args");
-    int P = 0;
-    if (dtype == LZ_F64) {
-        LZ_TRY(gram_partials<double>(h, n, b, (const double *)W, (const double *)W, ld, &P));
-        return gram_finish<double>(h, b, P, 0, (double *)R);
-    }
-    LZ_TRY(gram_partials<float>(h, n, b, (const float *)W, (const float *)W, ld, &P));
-    return gram_finish<float>(h, b, P, 0, (float *)R);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        int P = 0;
+        LZ_TRY(gram_partials<T>(h, n, b, (const T *)W, (const T *)W, ld, &P));
+        return gram_finish<T>(h, b, P, 0, (T *)R);
+    });
 }
 
 int lz_sym_cross_gram(lz_handle *h, int64_t n, int b, lz_dtype dtype, const void *W, const void *Q,
@@ -1700,13 +1721,12 @@ int lz_sym_cross_gram(lz_handle *h, int64_t n, int b, lz_dtype dtype, const void
 {
     LZ_HANDLE_CHECK(h);
     LZ_ARG_CHECK(W && Q && R && b >= 1 && b <= kMaxB && ld >= b && n >= 0, "cross gram args");
-    int P = 0;
-    if (dtype == LZ_F64) {
-        LZ_TRY(gram_partials<double>(h, n, b, (const double *)W, (const double *)Q, ld, &P));
-        return gram_finish<double>(h, b, P, 1, (double *)R);
-    }
-    LZ_TRY(gram_partials<float>(h, n, b, (const float *)W, (const float *)Q, ld, &P));
-    return gram_finish<float>(h, b, P, 1, (float *)R);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        int P = 0;
+        LZ_TRY(gram_partials<T>(h, n, b, (const T *)W, (const T *)Q, ld, &P));
+        return gram_finish<T>(h, b, P, 1, (T *)R);
+    });
 }
 
 int lz_tsmm(lz_handle *h, int64_t n, int b, lz_dtype dtype, double beta, double alpha,
@@ -1714,11 +1734,10 @@ int lz_tsmm(lz_handle *h, int64_t n, int b, lz_dtype dtype, double beta, double 
 {
     LZ_HANDLE_CHECK(h);
     LZ_ARG_CHECK(Q && S && W && Q != W, "tsmm pointers (Q must not alias W)");
-    if (dtype == LZ_F64)
-        return tsmm<double>(h, n, b, beta, alpha, (const double *)Q, (const double *)S,
-                            (double *)W, ld);
-    return tsmm<float>(h, n, b, (float)beta, (float)alpha, (const float *)Q, (const float *)S,
-                       (float *)W, ld);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return tsmm<T>(h, n, b, (T)beta, (T)alpha, (const T *)Q, (const T *)S, (T *)W, ld);
+    });
 }
 
 int lz_sqrtm_pair(lz_handle *h, int b, lz_dtype dtype, const void *G, void *beta, void *beta_inv,
@@ -1726,11 +1745,10 @@ int lz_sqrtm_pair(lz_handle *h, int b, lz_dtype dtype, const void *G, void *beta
 {
     LZ_HANDLE_CHECK(h);
     LZ_ARG_CHECK(G && b >= 1 && b <= 32, "sqrtm args");
-    if (dtype == LZ_F64)
-        return sqrtm_pair<double>(h, b, (const double *)G, 0, (double *)beta, (double *)beta_inv,
-                                  (double *)eigval);
-    return sqrtm_pair<float>(h, b, (const float *)G, 0, (float *)beta, (float *)beta_inv,
-                             (float *)eigval);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return sqrtm_pair<T>(h, b, (const T *)G, 0, (T *)beta, (T *)beta_inv, (T *)eigval);
+    });
 }
 
 int lz_copy_row(lz_handle *h, int b, lz_dtype dtype, const void *Q, int64_t ld, lz_layout layout,
@@ -1738,11 +1756,10 @@ int lz_copy_row(lz_handle *h, int b, lz_dtype dtype, const void *Q, int64_t ld, 
 {
     LZ_HANDLE_CHECK(h);
     LZ_ARG_CHECK(Q && q && b >= 1 && b <= kMaxB && lc >= 0, "copy_row args");
-    if (dtype == LZ_F64)
-        return copy_row<double>(h, b, (const double *)Q, ld, layout == LZ_COL_MAJOR, lc,
-                                (double *)q + start);
-    return copy_row<float>(h, b, (const float *)Q, ld, layout == LZ_COL_MAJOR, lc,
-                           (float *)q + start);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return copy_row<T>(h, b, (const T *)Q, ld, layout == LZ_COL_MAJOR, lc, (T *)q + start);
+    });
 }
 
 static int block_args(int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
@@ -1767,14 +1784,11 @@ int lz_block_lanczos_unfused(lz_handle *h, int64_t n, int64_t nnz, const int64_t
 {
     LZ_HANDLE_CHECK(h);
     LZ_TRY(block_args(n, nnz, rp, col, val, b, m, lc, B, q, alpha, beta, Q0, Q1, W));
-    if (dtype == LZ_F64)
-        return block_lanczos_unfused<double>(h, n, nnz, rp, col, (const double *)val, b, m, lc,
-                                             (const double *)B, (double *)q, (double *)alpha,
-                                             (double *)beta, (double *)Q0, (double *)Q1,
-                                             (double *)W);
-    return block_lanczos_unfused<float>(h, n, nnz, rp, col, (const float *)val, b, m, lc,
-                                        (const float *)B, (float *)q, (float *)alpha,
-                                        (float *)beta, (float *)Q0, (float *)Q1, (float *)W);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return block_lanczos_unfused<T>(h, n, nnz, rp, col, (const T *)val, b, m, lc, (const T *)B, (T *)q,
+                                        (T *)alpha, (T *)beta, (T *)Q0, (T *)Q1, (T *)W);
+    });
 }
 
 int lz_block_lanczos(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
@@ -1783,18 +1797,19 @@ int lz_block_lanczos(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, co
 {
     LZ_HANDLE_CHECK(h);
     LZ_TRY(block_args(n, nnz, rp, col, val, b, m, lc, B, q, alpha, beta, Q0, Q1, W));
-    if (dtype == LZ_F64 && b == 16) {
-        LZ_TRY(solve_begin(h));
-        LZ_TRY(block_lanczos_fused16(h, n, nnz, rp, col, (const double *)val, m, lc, (const double *)B, (double *)q,
-                                     (double *)alpha, (double *)beta, (double *)Q0, (double *)Q1, (double *)W));
-        return solve_status(h);
-    }
-    if (dtype == LZ_F64)
-        return block_lanczos_sep<double>(h, n, nnz, rp, col, (const double *)val, b, m, lc, (const double *)B,
-                                         (double *)q, (double *)alpha, (double *)beta, (double *)Q0, (double *)Q1,
-                                         (double *)W);
-    return block_lanczos_sep<float>(h, n, nnz, rp, col, (const float *)val, b, m, lc, (const float *)B, (float *)q,
-                                    (float *)alpha, (float *)beta, (float *)Q0, (float *)Q1, (float *)W);
+    return by_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        const T *v = (const T *)val, *Bt = (const T *)B;
+        T *qt = (T *)q, *at = (T *)alpha, *bt = (T *)beta, *q0 = (T *)Q0, *q1 = (T *)Q1, *w = (T *)W;
+        if constexpr (std::is_same<T, double>::value) {
+            if (b == 16) {
+                LZ_TRY(solve_begin(h));
+                LZ_TRY(block_lanczos_fused16(h, n, nnz, rp, col, v, m, lc, Bt, qt, at, bt, q0, q1, w));
+                return solve_status(h);
+            }
+        }
+        return block_lanczos_sep<T>(h, n, nnz, rp, col, v, b, m, lc, Bt, qt, at, bt, q0, q1, w);
+    });
 }
 
 static int panel_args(int64_t n, int b, int k, lz_dtype dtype, const void *V, int64_t vstride)
@@ -1817,9 +1832,10 @@ int lz_panel_gram(lz_handle *h, int64_t n, int b, int k, lz_dtype dtype, const v
     LZ_HANDLE_CHECK(h);
     LZ_TRY(panel_args(n, b, k, dtype, V, vstride));
     LZ_ARG_CHECK(W && C, "W/C NULL");
-    if (dtype == LZ_F64)
-        return panel_gram<double>(h, n, b, k, (const double *)V, vstride, (const double *)W, (double *)C);
-    return panel_gram<float>(h, n, b, k, (const float *)V, vstride, (const float *)W, (float *)C);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return panel_gram<T>(h, n, b, k, (const T *)V, vstride, (const T *)W, (T *)C);
+    });
 }
 
 int lz_panel_apply(lz_handle *h, int64_t n, int b, int k, lz_dtype dtype, double beta, double alpha, const void *V,
@@ -1834,10 +1850,10 @@ int lz_panel_apply(lz_handle *h, int64_t n, int b, int k, lz_dtype dtype, double
         LZ_ARG_CHECK(w0 + n * b * es <= v0 || w0 >= v0 + ((int64_t)(k - 1) * vstride + n * b) * es,
                      "W must not overlap the panel");
     }
-    if (dtype == LZ_F64)
-        return panel_apply<double>(h, n, b, k, beta, alpha, (const double *)V, vstride, (const double *)S,
-                                   (double *)W);
-    return panel_apply<float>(h, n, b, k, beta, alpha, (const float *)V, vstride, (const float *)S, (float *)W);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return panel_apply<T>(h, n, b, k, beta, alpha, (const T *)V, vstride, (const T *)S, (T *)W);
+    });
 }
 
 // n x b blocks at p and q (es bytes per element) do not overlap
@@ -1873,11 +1889,11 @@ int lz_csr_spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, c
     const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
     LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && (d == 0.0 || (blocks_apart(Z, nb, Y, nb, es) && Z != X)),
                  "X, Z and Y must be pairwise distinct (no in-place form)");
-    if (dtype == LZ_F64)
-        return spmm_axpby<double>(h, n, nnz, rp, col, (const double *)val, b, a, (const double *)X, c, d,
-                                  (const double *)Z, (double *)Y, ax3_fused());
-    return spmm_axpby<float>(h, n, nnz, rp, col, (const float *)val, b, (float)a, (const float *)X, (float)c, (float)d,
-                             (const float *)Z, (float *)Y, ax3_fused());
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return spmm_axpby<T>(h, n, nnz, rp, col, (const T *)val, b, (T)a, (const T *)X, (T)c, (T)d, (const T *)Z,
+                             (T *)Y, ax3_fused());
+    });
 }
 
 int lz_cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
@@ -1893,11 +1909,10 @@ int lz_cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const
     LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && blocks_apart(work, 2 * nb, X, nb, es) &&
                      blocks_apart(work, 2 * nb, Y, nb, es),
                  "X, Y and work must be pairwise distinct");
-    if (dtype == LZ_F64)
-        return cheb_apply<double>(h, n, nnz, rp, col, (const double *)val, b, *f, (const double *)X, (double *)Y,
-                                  (double *)work);
-    return cheb_apply<float>(h, n, nnz, rp, col, (const float *)val, b, *f, (const float *)X, (float *)Y,
-                             (float *)work);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return cheb_apply<T>(h, n, nnz, rp, col, (const T *)val, b, *f, (const T *)X, (T *)Y, (T *)work);
+    });
 }
 
 int lz_block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
@@ -1928,13 +1943,11 @@ int lz_block_lanczos_reorth_cheb(lz_handle *h, int64_t n, int64_t nnz, const int
                      "B, W and the panel V must be distinct buffers");
     }
     LZ_TRY(cheb_solve_args(f, work, n, b, m, dtype, V, vstride, W, B));
-    if (dtype == LZ_F64)
-        return block_lanczos_reorth<double>(h, n, nnz, rp, col, (const double *)val, b, m, lc, (const double *)B,
-                                            (double *)q, (double *)alpha, (double *)beta, (double *)V, vstride,
-                                            (double *)W, passes, f, (double *)work);
-    return block_lanczos_reorth<float>(h, n, nnz, rp, col, (const float *)val, b, m, lc, (const float *)B,
-                                       (float *)q, (float *)alpha, (float *)beta, (float *)V, vstride, (float *)W,
-                                       passes, f, (float *)work);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return block_lanczos_reorth<T>(h, n, nnz, rp, col, (const T *)val, b, m, lc, (const T *)B, (T *)q, (T *)alpha,
+                                       (T *)beta, (T *)V, vstride, (T *)W, passes, f, (T *)work);
+    });
 }
 
 int lz_panel_compress(lz_handle *h, int64_t n, int b, int k, int r, lz_dtype dtype, void *V, int64_t vstride,
@@ -1945,8 +1958,10 @@ int lz_panel_compress(lz_handle *h, int64_t n, int b, int k, int r, lz_dtype dty
     LZ_ARG_CHECK(r >= 1 && r <= k, "panel_compress keeps 1 <= r <= k blocks");
     LZ_ARG_CHECK(r <= kPanelMaxKeep, "panel_compress keeps at most LZ_PANEL_MAX_KEEP = 16 blocks");
     LZ_ARG_CHECK(Z != nullptr, "Z is NULL");
-    if (dtype == LZ_F64) return panel_compress<double>(h, n, b, k, r, (double *)V, vstride, (const double *)Z);
-    return panel_compress<float>(h, n, b, k, r, (float *)V, vstride, (const float *)Z);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return panel_compress<T>(h, n, b, k, r, (T *)V, vstride, (const T *)Z);
+    });
 }
 
 int lz_block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
@@ -1979,14 +1994,12 @@ int lz_block_lanczos_reorth_resume_cheb(lz_handle *h, int64_t n, int64_t nnz, co
         LZ_ARG_CHECK(w0 + n * b * es <= v0 || w0 >= v1, "W and the panel V must be distinct buffers");
     }
     LZ_TRY(cheb_solve_args(f, work, n, b, m, dtype, V, vstride, W, nullptr));
-    if (dtype == LZ_F64)
-        return block_lanczos_reorth_resume<double>(h, n, nnz, rp, col, (const double *)val, b, r, m, lc,
-                                                   (const double *)sigma, (double *)q, (double *)alpha,
-                                                   (double *)beta, (double *)V, vstride, (double *)W, passes, f,
-                                                   (double *)work);
-    return block_lanczos_reorth_resume<float>(h, n, nnz, rp, col, (const float *)val, b, r, m, lc,
-                                              (const float *)sigma, (float *)q, (float *)alpha, (float *)beta,
-                                              (float *)V, vstride, (float *)W, passes, f, (float *)work);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return block_lanczos_reorth_resume<T>(h, n, nnz, rp, col, (const T *)val, b, r, m, lc, (const T *)sigma,
+                                              (T *)q, (T *)alpha, (T *)beta, (T *)V, vstride, (T *)W, passes, f,
+                                              (T *)work);
+    });
 }
 
 int lz_vector_lanczos(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
@@ -1999,13 +2012,11 @@ int lz_vector_lanczos(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, c
     LZ_ARG_CHECK(bvec && q && alpha && beta && q0 && q1 && w, "NULL buffer");
     LZ_ARG_CHECK(bvec != q0 && bvec != q1 && bvec != w && q0 != q1 && q0 != w && q1 != w,
                  "b, q0, q1, w must be distinct buffers");
-    if (dtype == LZ_F64)
-        return vector_lanczos_dev<double>(h, n, nnz, rp, col, (const double *)val, m, lc,
-                                          (const double *)bvec, (double *)q, (double *)alpha,
-                                          (double *)beta, (double *)q0, (double *)q1, (double *)w);
-    return vector_lanczos_dev<float>(h, n, nnz, rp, col, (const float *)val, m, lc, (const float *)bvec,
-                                     (float *)q, (float *)alpha, (float *)beta, (float *)q0, (float *)q1,
-                                     (float *)w);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return vector_lanczos_dev<T>(h, n, nnz, rp, col, (const T *)val, m, lc, (const T *)bvec, (T *)q, (T *)alpha,
+                                     (T *)beta, (T *)q0, (T *)q1, (T *)w);
+    });
 }
 
 int lz_fdtd_block(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
@@ -2015,11 +2026,11 @@ int lz_fdtd_block(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(n, nnz, rp, col, val));
     LZ_ARG_CHECK(steps >= 1 && lc >= 0 && lc < n && U0 && U && D && out, "fdtd args");
-    if (dtype == LZ_F64)
-        return fdtd_block<double>(h, n, nnz, rp, col, (const double *)val, b, (const double *)U0, steps,
-                                  T_end, lc, (double *)U, (double *)D, (double *)out);
-    return fdtd_block<float>(h, n, nnz, rp, col, (const float *)val, b, (const float *)U0, steps,
-                             T_end, lc, (float *)U, (float *)D, (float *)out);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return fdtd_block<T>(h, n, nnz, rp, col, (const T *)val, b, (const T *)U0, steps, T_end, lc, (T *)U, (T *)D,
+                             (T *)out);
+    });
 }
 
 int lz_comm_init(lz_handle *h, int nranks, int rank, const unsigned char id[128])
@@ -2071,7 +2082,7 @@ int lz_debug_wf_plan(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_pt
     if (wp.planned && T > 0) {
         LZ_HIP_TRY(hipMemcpyAsync(deps_out, h->wf_deps, sizeof(int32_t) * 2 * (size_t)T, hipMemcpyDeviceToDevice,
                                   h->stream));
-        LZ_HIP_TRY(hipMemcpyAsync(sp, h->err_flag + 12, sizeof(sp), hipMemcpyDeviceToHost, h->stream));
+        LZ_HIP_TRY(hipMemcpyAsync(sp, flag_word(h, kFlagPlanStats), sizeof(sp), hipMemcpyDeviceToHost, h->stream));
     } else if (T > 0) {
         LZ_HIP_TRY(hipMemsetAsync(deps_out, 0, sizeof(int32_t) * 2 * (size_t)T, h->stream));
     }
@@ -2124,13 +2135,11 @@ static int lz_block_lanczos_dist_impl(lz_handle *h, int64_t n_local, int64_t n_p
     (void)Q0;
     (void)Q1;
     const int64_t lc = (lc_rank == h->rank) ? lc_local : -1;
-    if (dtype == LZ_F64)
-        return dist_solve<double>(h, kFormAllgather, nullptr, n_local, n_pad, nnz_local, rp, col, (const double *)val, b,
-                                  m, lc, (const double *)B_local, (double *)q, (double *)alpha, (double *)beta,
-                                  (double *)X_full, (double *)W);
-    return dist_solve<float>(h, kFormAllgather, nullptr, n_local, n_pad, nnz_local, rp, col, (const float *)val, b, m,
-                             lc, (const float *)B_local, (float *)q, (float *)alpha, (float *)beta, (float *)X_full,
-                             (float *)W);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return dist_solve<T>(h, kFormAllgather, nullptr, n_local, n_pad, nnz_local, rp, col, (const T *)val, b, m, lc,
+                             (const T *)B_local, (T *)q, (T *)alpha, (T *)beta, (T *)X_full, (T *)W);
+    });
 }
 
 int lz_block_lanczos_dist(lz_handle *h, int64_t n_local, int64_t n_pad, int64_t n_global,
@@ -2306,13 +2315,11 @@ static int lz_block_lanczos_halo_impl(lz_handle *h, int64_t n_local, int64_t nnz
     LZ_ARG_CHECK(n_local >= 1, "sizes");
     LZ_ARG_CHECK(B_local && q && alpha && beta && X0 && X1 && X0 != X1, "NULL / aliased buffer");
     const int64_t lc = (lc_rank == h->rank) ? lc_local : -1;
-    if (dtype == LZ_F64)
-        return dist_solve<double>(h, kFormHalo, &hp, n_local, n_local, nnz_local, rp, col, (const double *)val, b, m,
-                                  lc, (const double *)B_local, (double *)q, (double *)alpha, (double *)beta,
-                                  (double *)X0, (double *)X1);
-    return dist_solve<float>(h, kFormHalo, &hp, n_local, n_local, nnz_local, rp, col, (const float *)val, b, m, lc,
-                             (const float *)B_local, (float *)q, (float *)alpha, (float *)beta, (float *)X0,
-                             (float *)X1);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return dist_solve<T>(h, kFormHalo, &hp, n_local, n_local, nnz_local, rp, col, (const T *)val, b, m, lc,
+                             (const T *)B_local, (T *)q, (T *)alpha, (T *)beta, (T *)X0, (T *)X1);
+    });
 }
 
 int lz_block_lanczos_halo(lz_handle *h, int64_t n_local, int64_t nnz_local, const int64_t *rp,

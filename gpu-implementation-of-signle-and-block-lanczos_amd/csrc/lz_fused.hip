@@ -498,13 +498,7 @@ __global__ __launch_bounds__(256) void k_strip_pairs(int64_t n, const int64_t *_
 int strip_pairs(lz_handle *h, int64_t n, const int64_t *rp, const uint64_t **out)
 {
     const int64_t ns = ceil_div(n, (int64_t)16) + kPairPad;
-    if ((size_t)ns > h->pairs_cap) {
-        LZ_HIP_TRY(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->pairs);
-        h->pairs = nullptr;
-        LZ_HIP_TRY(hipMalloc(&h->pairs, sizeof(uint64_t) * (size_t)ns));
-        h->pairs_cap = (size_t)ns;
-    }
+    LZ_TRY(grow_ws(h, &h->pairs, &h->pairs_cap, sizeof(uint64_t) * (size_t)ns));
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(ns, (int64_t)256), (int64_t)h->n_cu * 4));
     hipLaunchKernelGGL(k_strip_pairs, dim3(grid), dim3(256), 0, h->stream, n, rp, h->pairs);
     LZ_LAUNCH_CHECK();
@@ -898,7 +892,7 @@ __global__ __launch_bounds__(256) void k_window_check(int64_t n, const int64_t *
 int gather_window_ok(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, int64_t nx, int64_t row_off,
                      bool *ok)
 {
-    int *flag = h->err_flag + 8;  // err_flag[0] is the device error word
+    int *flag = flag_word(h, kFlagWindow);
     LZ_HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), h->stream));
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, (int64_t)256), (int64_t)h->n_cu * 8));
     hipLaunchKernelGGL(k_window_check, dim3(grid), dim3(256), 0, h->stream, n, rp, col, nx, row_off, flag);
@@ -945,16 +939,8 @@ int col16_plan(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const in
     *out = nullptr;
     const char *e = getenv("LZ_PASS1_C16");  // "0": 32-bit columns (A/B); read per call
     if ((e && e[0] == '0') || n <= 0 || nnz <= 0) return LZ_OK;
-    const size_t bytes = (size_t)nnz * 2 + 16;  // + the dword the kernel's range may end in
-    if (bytes > h->c16_cap) {
-        LZ_HIP_TRY(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->c16buf);
-        h->c16buf = nullptr;
-        h->c16_cap = 0;
-        LZ_HIP_TRY(hipMalloc(&h->c16buf, bytes));
-        h->c16_cap = bytes;
-    }
-    int *flag = h->err_flag + 9;
+    LZ_TRY(c16_reserve(h, nnz));
+    int *flag = flag_word(h, kFlagCol16);
     LZ_HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), h->stream));
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, (int64_t)256), (int64_t)h->n_cu * 8));
     hipLaunchKernelGGL(k_col16, dim3(grid), dim3(256), 0, h->stream, n, rp, col, row_off,

@@ -1302,7 +1302,7 @@ static int fnz_prepare(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, 
     h->fnz_key[0] = 0;
     LZ_HIP_TRY(hipMalloc(&h->fnz_colf, sizeof(int32_t) * (size_t)nnz));
     LZ_HIP_TRY(hipMalloc(&h->fnz_trow, sizeof(int32_t) * (size_t)(ntiles + 1)));
-    int *stats = h->err_flag + 12;  // [0] max row length, [1] empty / negative, [2] max rows per tile
+    int *stats = flag_word(h, kFlagPlanStats);  // [0] max row length, [1] empty / negative, [2] max rows per tile
     LZ_HIP_TRY(hipMemsetAsync(stats, 0, 3 * sizeof(int), h->stream));
     const int g1 = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, (int64_t)256), (int64_t)h->n_cu * 8));
     hipLaunchKernelGGL(k_fnz_flags, dim3(g1), dim3(256), 0, h->stream, n, rp, col, h->fnz_colf, stats);
@@ -1334,18 +1334,15 @@ static int launch_fnz(lz_handle *h, int64_t nnz, const T *val, const T *X, int64
 // the long-tile queue for st tiles: count slots longq[0..1], then the list
 static int ensure_longq(lz_handle *h, int64_t st)
 {
-    if ((size_t)st + 2 > h->longq_cap) {
-        LZ_HIP_TRY(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->longq);
-        h->longq = nullptr;
-        LZ_HIP_TRY(hipMalloc(&h->longq, sizeof(int) * ((size_t)st + 2)));
+    const size_t cap0 = h->longq_cap;
+    LZ_TRY(grow_ws(h, &h->longq, &h->longq_cap, sizeof(int) * ((size_t)st + 2)));
+    if (h->longq_cap != cap0) {  // grown
         // both count slots, on the handle's stream: a plain hipMemset runs on the
         // null stream, which does not order against a non-blocking stream (a
         // torch pool stream, a virtual rank's), so the kernels below could read
         // the fresh allocation's garbage as a queue count (round 5: wrong tiles
         // recomputed by the long-tile pass, or an illegal address)
         LZ_HIP_TRY(hipMemsetAsync(h->longq, 0, 2 * sizeof(int), h->stream));
-        h->longq_cap = (size_t)st + 2;
         h->longq_parity = 0;
     }
     return LZ_OK;
@@ -1475,7 +1472,7 @@ static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t 
     h->last_kernel[0] = (CAP == 768 ? LZ_K_SEG768 : CAP == 1024 ? LZ_K_SEG1024 : LZ_K_SEG1536) | (WIN ? LZ_K_WIN : 0) |
                         (YCM ? LZ_K_YCM : 0) | (EPI ? LZ_K_EPI : 0) | (AX3 ? LZ_K_AX3 : 0);
     if (plan_slot >= 0) {
-        LZ_ARG_CHECK(plan_slot <= 1 && (size_t)st + 2 <= h->longq_cap, "planned SpMM: no earlier queue");
+        LZ_ARG_CHECK(plan_slot <= 1 && sizeof(int) * ((size_t)st + 2) <= h->longq_cap, "planned SpMM: no earlier queue");
         if (!h->lstream) {
             LZ_HIP_TRY(hipStreamCreateWithFlags(&h->lstream, hipStreamNonBlocking));
             LZ_HIP_TRY(hipEventCreateWithFlags(&h->ev_lfork, hipEventDisableTiming));
@@ -1621,10 +1618,9 @@ int spmm_b2_stage(lz_handle *h, int64_t n, const int64_t *rp, int *cap)
     *cap = 768;
     if (n <= 0) return LZ_OK;
     const int64_t tiles = ceil_div(n, (int64_t)48);
-    // a named slot of the handle's flag block ([0] the device error word, [8], [9]
-    // and [12..15] the plans' words), not a word of the scratch the solve's b x b
-    // matrices use
-    int *dcount = h->err_flag + 4;
+    // a named slot of the handle's flag block (lz::FlagWord), not a word of the
+    // scratch the solve's b x b matrices use
+    int *dcount = flag_word(h, kFlagLongTiles);
     LZ_HIP_TRY(hipMemsetAsync(dcount, 0, sizeof(int), h->stream));
     hipLaunchKernelGGL(k_tile_overflow, dim3((unsigned)ceil_div(tiles, (int64_t)256)), dim3(256), 0, h->stream, n, rp,
                        1024, dcount);
@@ -1855,15 +1851,7 @@ int spmm_cm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32
     // LZ_SPMM_CM=direct: the one-pass kernel.
     const char *cm_env = getenv("LZ_SPMM_CM");  // read per call (tests switch it)
     if (b >= 2 && (b & (b - 1)) == 0 && !(cm_env && cm_env[0] == 'd')) {  // the row-major kernel's b
-        const size_t need = sizeof(T) * (size_t)b * (size_t)nx;
-        if (need > h->cm_cap) {
-            LZ_HIP_TRY(hipStreamSynchronize(h->stream));
-            (void)hipFree(h->cm_buf);
-            h->cm_buf = nullptr;
-            h->cm_cap = 0;
-            LZ_HIP_TRY(hipMalloc(&h->cm_buf, need));
-            h->cm_cap = need;
-        }
+        LZ_TRY(grow_ws(h, &h->cm_buf, &h->cm_cap, sizeof(T) * (size_t)b * (size_t)nx));
         T *Xr = static_cast<T *>(h->cm_buf);
         const size_t lds = sizeof(T) * (size_t)b * (kCmRows + 1);
         hipLaunchKernelGGL((k_cm_transpose<T>), dim3((unsigned)ceil_div(nx, (int64_t)kCmRows)), dim3(256), lds,

@@ -813,33 +813,16 @@ int wf_plan16(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int
         (double)nnz > kWfWideRow * (double)n)
         return LZ_OK;
     const int64_t T = ceil_div(n, (int64_t)pl->tr);
-    if ((size_t)T + 64 > h->wf_cap) {
-        LZ_HIP_TRY(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->wf_deps);
-        (void)hipFree(h->wf_flags);
-        h->wf_deps = nullptr;
-        h->wf_flags = nullptr;
-        h->wf_cap = 0;
-        LZ_HIP_TRY(hipMalloc(&h->wf_deps, sizeof(int2) * (size_t)(T + 64)));
-        LZ_HIP_TRY(hipMalloc(&h->wf_flags, sizeof(int) * (size_t)(T + 64)));
-        h->wf_cap = (size_t)T + 64;
-    }
+    LZ_TRY(grow_ws(h, &h->wf_deps, &h->wf_deps_cap, sizeof(int2) * (size_t)(T + 64)));
+    LZ_TRY(grow_ws(h, &h->wf_flags, &h->wf_flags_cap, sizeof(int) * (size_t)(T + 64)));
     // pass 1's 16-bit columns in the same pass (col16_plan's buffer and encoding)
     const char *c = getenv("LZ_PASS1_C16");  // "0": 32-bit columns (A/B); read per call
     int16_t *c16 = nullptr;
     if (!(c && c[0] == '0') && nnz > 0) {
-        const size_t bytes = (size_t)nnz * 2 + 16;  // + the dword the kernel's range may end in
-        if (bytes > h->c16_cap) {
-            LZ_HIP_TRY(hipStreamSynchronize(h->stream));
-            (void)hipFree(h->c16buf);
-            h->c16buf = nullptr;
-            h->c16_cap = 0;
-            LZ_HIP_TRY(hipMalloc(&h->c16buf, bytes));
-            h->c16_cap = bytes;
-        }
+        LZ_TRY(c16_reserve(h, nnz));
         c16 = static_cast<int16_t *>(h->c16buf);
     }
-    int *spans = h->err_flag + 12;  // err_flag[0]: device error word; [8], [9]: other plans
+    int *spans = flag_word(h, kFlagPlanStats);
     LZ_HIP_TRY(hipMemsetAsync(spans, 0, 4 * sizeof(int), h->stream));
     // (one tile per block measured slower: its per-block atomics contend)
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)h->n_cu * 8));
@@ -1087,7 +1070,7 @@ int wf_fold16(lz_handle *h, const WfSlabs &sl, double *out)
 int wf_reset16(lz_handle *h, int64_t n, const WfPlan &pl)
 {
     const int64_t T = ceil_div(n, (int64_t)pl.tr);
-    LZ_ARG_CHECK((size_t)T <= h->wf_cap, "wf_plan16 first");
+    LZ_ARG_CHECK(sizeof(int) * (size_t)T <= h->wf_flags_cap, "wf_plan16 first");
     LZ_HIP_TRY(hipMemsetAsync(h->wf_flags, 0, sizeof(int) * (size_t)T, h->stream));
     return LZ_OK;
 }
