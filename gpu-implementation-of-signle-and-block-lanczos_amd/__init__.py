@@ -47,6 +47,10 @@ PANEL_GROUP_16, PANEL_GROUP_GEN = 16, 4
 PANEL_MAX_BLOCKS = 64
 LZ_K_PCOMP16, LZ_K_PCOMP_GEN = 11, 12
 PANEL_MAX_KEEP = 16  # most output blocks of one panel_compress (LZ_PANEL_MAX_KEEP)
+# lz_csr_transpose (csrc/lz_internal.hpp kTr*): an output row of up to TRANSPOSE_SHORT entries is
+# sorted by one lane group, up to TRANSPOSE_LDS by one workgroup through LDS, a longer one in
+# chunks of TRANSPOSE_LDS merged pairwise; the scan covers TRANSPOSE_SCAN_BLOCK counts per workgroup
+TRANSPOSE_SHORT, TRANSPOSE_LDS, TRANSPOSE_SCAN_BLOCK = 16, 4096, 2048
 
 _c_i64, _c_i32, _c_int, _c_dbl, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_double, ctypes.c_void_p
 _c_u32, _c_u64 = ctypes.c_uint32, ctypes.c_uint64
@@ -108,6 +112,15 @@ HIP_SYMBOLS = [
     ("lz_block_lanczos_reorth_resume_cheb", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int,
                                                      _c_int, _c_int, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                                      _c_i64, _c_vp, _c_int, _c_vp, _c_vp]),
+    ("lz_csr_transpose", _c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    ("lz_normal_apply", _c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int,
+                                 _c_int, _c_vp, _c_vp, _c_vp]),
+    ("lz_block_lanczos_reorth_normal", _c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                                _c_vp, _c_int, _c_int, _c_int, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp,
+                                                _c_vp, _c_i64, _c_vp, _c_int, _c_vp]),
+    ("lz_block_lanczos_reorth_resume_normal", _c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp,
+                                                       _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_vp,
+                                                       _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int, _c_vp]),
     ("lz_vector_lanczos", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_i64,
                                    _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_fdtd_block", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp,
@@ -593,6 +606,20 @@ class CsrDevice:
                          torch.from_numpy(A.col).to(device),
                          torch.from_numpy(A.val).to(device))
 
+    def transpose(self, handle: "Handle") -> "CsrDevice":
+        """The CSR of the transpose, built on the device (lz_csr_transpose): n and n_cols
+        swapped, row c holding this operator's entries of column c in the order of their
+        positions here.  Bitwise reproducible."""
+        torch = _torch()
+        dev = self.val.device
+        t_rp = torch.empty(self.n_cols + 1, dtype=torch.int64, device=dev)
+        t_col = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+        t_val = torch.empty(self.nnz, dtype=self.val.dtype, device=dev)
+        _check(handle.L.lz_csr_transpose(handle.ptr, self.n, self.n_cols, self.nnz, _ptr(self.row_ptr), _ptr(self.col),
+                                         _ptr(self.val), self.dtype, _ptr(t_rp), _ptr(t_col), _ptr(t_val)),
+               "lz_csr_transpose")
+        return CsrDevice(self.n_cols, self.n, t_rp, t_col, t_val)
+
 
 class Handle:
     """lz_handle on one device, bound to torch's current stream at each call."""
@@ -669,6 +696,30 @@ class Handle:
         f = _cheb(filt)
         _check(self.L.lz_cheb_apply(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
                                     ctypes.addressof(f), _ptr(X), _ptr(Y), _ptr(work)), "lz_cheb_apply")
+        return Y
+
+    def _normal(self, what: str, normal, n: int, b: int, like):
+        """(P, Pt, work) of a normal-operator call on n x b blocks: P (p, n), Pt (n, p) its
+        transpose, work flat with p*b elements of the blocks' dtype."""
+        P, Pt, work = normal
+        if P.n_cols != n or Pt.n != n or Pt.n_cols != P.n or P.nnz != Pt.nnz or P.val.dtype != like.dtype \
+                or Pt.val.dtype != like.dtype:
+            raise LanczosError(f"{what}: P (p, n) and Pt (n, p) its transpose, of the blocks' dtype, n the blocks' rows")
+        if work is None or work.dim() != 1 or not work.is_contiguous() or work.numel() < P.n * b \
+                or work.dtype != like.dtype:
+            raise LanczosError(f"{what}: work is a flat contiguous tensor of p*b elements of the solve's dtype")
+        return P, Pt, work
+
+    def normal_apply(self, P: CsrDevice, Pt: CsrDevice, X, Y, work):
+        """Y = Pt (P X) (lz_normal_apply): P (p, n), Pt = P.transpose(handle), X / Y (n, b)
+        contiguous and distinct, work flat with p*b elements.  X is only read."""
+        n, b = X.shape
+        if tuple(Y.shape) != (n, b) or not X.is_contiguous() or not Y.is_contiguous() or Y.dtype != X.dtype:
+            raise LanczosError("normal_apply: X and Y (n, b) contiguous (ld = b), one dtype")
+        self._normal("normal_apply", (P, Pt, work), n, b, X)
+        _check(self.L.lz_normal_apply(self.ptr, n, P.n, P.nnz, _ptr(P.row_ptr), _ptr(P.col), _ptr(P.val),
+                                      _ptr(Pt.row_ptr), _ptr(Pt.col), _ptr(Pt.val), P.dtype, b, _ptr(X), _ptr(Y),
+                                      _ptr(work)), "lz_normal_apply")
         return Y
 
     def to_row_major(self, Xcm, Y):
@@ -768,14 +819,27 @@ class Handle:
         return W
 
     def block_lanczos_reorth(self, A: CsrDevice, B, m: int, lc: int, q, alpha, beta, V, vstride: int, W,
-                             passes: int = 2, filt=None, work=None):
+                             passes: int = 2, filt=None, work=None, normal=None):
         """Block Lanczos on a kept basis with `passes` rounds of full reorthogonalisation
         per step (lz_block_lanczos_reorth).  q[m*b], alpha[m,b,b], beta[m+1,b,b] (beta[m]
         = the true beta_m), the panel V (m blocks) and W (the final residual) are written
         in place.  filt = (degree, lo, hi, ref) with work (flat, 2*n*b elements): the same
-        solve on the Chebyshev-filtered operator p(A) (lz_block_lanczos_reorth_cheb)."""
+        solve on the Chebyshev-filtered operator p(A) (lz_block_lanczos_reorth_cheb).
+        normal = (P, Pt, work) with P (p, n), Pt its transpose and work flat with p*b elements:
+        the same solve on G = P^T P (lz_block_lanczos_reorth_normal); A is not used then (None)
+        and filt must be None."""
         n, b = B.shape
         self._panel(V, vstride, n, b, max(m, 1))
+        if normal is not None:
+            if filt is not None:
+                raise LanczosError("block_lanczos_reorth: normal= and filt= are mutually exclusive")
+            P, Pt, nwork = self._normal("block_lanczos_reorth", normal, n, b, W)
+            _check(self.L.lz_block_lanczos_reorth_normal(self.ptr, n, P.n, P.nnz, _ptr(P.row_ptr), _ptr(P.col),
+                                                         _ptr(P.val), _ptr(Pt.row_ptr), _ptr(Pt.col), _ptr(Pt.val),
+                                                         P.dtype, b, m, lc, _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta),
+                                                         _ptr(V), vstride, _ptr(W), passes, _ptr(nwork)),
+                   "lz_block_lanczos_reorth_normal")
+            return
         if filt is None:
             _check(self.L.lz_block_lanczos_reorth(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val),
                                                   A.dtype, b, m, lc, _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta),
@@ -833,17 +897,28 @@ class Handle:
         return V
 
     def block_lanczos_reorth_resume(self, A: CsrDevice, r: int, m: int, lc: int, sigma, q, alpha, beta, V,
-                                    vstride: int, W, passes: int = 2, filt=None, work=None):
+                                    vstride: int, W, passes: int = 2, filt=None, work=None, normal=None):
         """Steps r .. m-1 of block_lanczos_reorth on a thick-restarted basis
         (lz_block_lanczos_reorth_resume): blocks 0 .. r-1 of V hold the kept Ritz blocks
         (panel_compress), W the previous cycle's residual, sigma (r, b, b) the device copy of
         restart_coeffs' sigma.  Writes alpha[r:], beta[r:], q[r*b:], blocks r .. m-1 and W.
-        filt, work: as block_lanczos_reorth (the same filter for every cycle of a solve)."""
+        filt, work, normal: as block_lanczos_reorth (the same operator for every cycle of a solve)."""
         n, b = W.shape
         self._panel(V, vstride, n, b, max(m, 1))
         if not sigma.is_contiguous() or sigma.numel() < max(r, 0) * b * b or sigma.dtype != W.dtype \
                 or V.dtype != W.dtype or not W.is_contiguous():
             raise LanczosError("block_lanczos_reorth_resume: W (n, b) and sigma (r, b, b) contiguous, one dtype")
+        if normal is not None:
+            if filt is not None:
+                raise LanczosError("block_lanczos_reorth_resume: normal= and filt= are mutually exclusive")
+            P, Pt, nwork = self._normal("block_lanczos_reorth_resume", normal, n, b, W)
+            _check(self.L.lz_block_lanczos_reorth_resume_normal(self.ptr, n, P.n, P.nnz, _ptr(P.row_ptr), _ptr(P.col),
+                                                                _ptr(P.val), _ptr(Pt.row_ptr), _ptr(Pt.col),
+                                                                _ptr(Pt.val), P.dtype, b, r, m, lc, _ptr(sigma),
+                                                                _ptr(q), _ptr(alpha), _ptr(beta), _ptr(V), vstride,
+                                                                _ptr(W), passes, _ptr(nwork)),
+                   "lz_block_lanczos_reorth_resume_normal")
+            return
         if filt is None:
             _check(self.L.lz_block_lanczos_reorth_resume(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col),
                                                          _ptr(A.val), A.dtype, b, r, m, lc, _ptr(sigma), _ptr(q),
@@ -950,6 +1025,117 @@ class Handle:
         self.panel_compress(V, vstride, m, nch, torch.from_numpy(Zx).to(**kw), n=n)
         return dict(theta=theta, resid=resid, V=V, vstride=vstride, cycles=cycles, n_spmm=n_spmm,
                     converged=converged, history=history, scale=scale)
+
+    def svds(self, A: CsrDevice, k: int, b: int = 16, m: Optional[int] = None, keep: Optional[int] = None,
+             tol: float = 1e-10, max_cycles: int = 100, B=None, lc: int = 0, passes: int = 2):
+        """The k largest singular triplets of the sparse R x C operator A by thick-restart block
+        Lanczos on G = P^T P, with P = A when C <= R and P = A^T otherwise, so that the Lanczos
+        dimension is n = min(R, C).  A is transposed once (CsrDevice.transpose; returned as At),
+        every operator line is Pt (P Q) (block_lanczos_reorth(normal=...)), and the loop is
+        eigsh's with which = "largest": the same defaults and limits for m and keep, the same
+        restart_coeffs, panel_compress, resume and restart_fill.  With theta the Ritz values of
+        G, sigma_i = sqrt(max(theta_i, 0)), sigma_max = sqrt(max|theta| over all of T) and est_i
+        the Ritz residual estimate on G, it stops when est_i <= tol * sigma_max * max(sigma_i,
+        sqrt(eps) * sigma_max) for the k wanted pairs (eps: the epsilon of A's dtype) -- the
+        estimate of ||A^T u_i - sigma_i v_i|| <= tol * ||A|| -- or after max_cycles cycles
+        (converged = False, no exception).  Singular values below sqrt(eps) * sigma_max cannot be
+        resolved through G (their squares drown in its rounding errors); the k smallest are
+        out of scope for the same reason.
+
+        The finish: one panel_compress leaves the k Ritz vectors x_i of G in the first ceil(k / b)
+        blocks of the panel; per block, y = P x with every column scaled by 1 / ||column|| (zero
+        columns stay zero) goes into a second panel of p-row blocks, and the measured residuals
+        ||Pt y_i - sigma_i x_i|| come from one more SpMM and the dense kernels.  B (n, b): the
+        start block, default uniform_B.  Returns a dict: s[k] descending; U, ustride, V, vstride
+        (the left / right singular vectors as block-major panels of ceil(k / b) blocks of R / C
+        rows, the last zero-padded); resid[k] measured; est[k]; cycles; n_spmm (every SpMM: two
+        per Lanczos step, two per block of the finish); converged; history (the largest wanted
+        est_i / (sigma_max * max(sigma_i, sqrt(eps) sigma_max)) of each cycle); At."""
+        torch = _torch()
+        tdt = A.val.dtype
+        want = -(-(k + b) // b)
+        if m is None:
+            m = min(PANEL_MAX_BLOCKS, max(4, 2 * want))
+        r = min(want, PANEL_MAX_KEEP, m - 1) if keep is None else keep
+        if k < 1 or r * b < k:
+            raise LanczosError(f"svds: keep * b = {r * b} < k = {k}")
+        if r >= m:
+            raise LanczosError(f"svds: keep = {r} >= m = {m}")
+        if r > PANEL_MAX_KEEP or m > PANEL_MAX_BLOCKS or r < 1:
+            raise LanczosError(f"svds: 1 <= keep <= {PANEL_MAX_KEEP} and m <= {PANEL_MAX_BLOCKS}")
+        At = A.transpose(self)
+        P, Pt = (A, At) if A.n_cols <= A.n else (At, A)
+        n, p = P.n_cols, P.n
+        per16 = 16 // A.val.element_size()
+        xstride, ystride = -(-n * b // per16) * per16, -(-p * b // per16) * per16
+        kw = dict(dtype=tdt, device=A.val.device)
+        npdt = np.float64 if tdt == torch.float64 else np.float32
+        eps = float(np.finfo(npdt).eps)
+        if B is None:
+            B = torch.from_numpy(uniform_B(n, b, dtype=npdt)).to(A.val.device)
+        X = torch.zeros(m * xstride, **kw)
+        W = torch.empty(n, b, **kw)
+        work = torch.empty(p * b, **kw)
+        normal = (P, Pt, work)
+        q, al, be = torch.zeros(m * b, **kw), torch.zeros(m, b, b, **kw), torch.zeros(m + 1, b, b, **kw)
+        self.block_lanczos_reorth(None, B, m, lc, q, al, be, X, xstride, W, passes=passes, normal=normal)
+        n_spmm, cycles, history, converged = 2 * m, 1, [], False
+        f64 = lambda t: t.cpu().numpy().astype(np.float64)
+        alpha, beta = f64(al), f64(be)
+        T = Assemble_T(m, b, alpha, beta[:m])
+        while True:
+            theta, S, est = ritz_pairs_dense(m, b, T, beta[m], m * b, "largest")
+            smax = float(np.sqrt(np.abs(theta).max()))
+            theta, S, est = theta[:k], S[:, :k], est[:k]
+            s = np.sqrt(np.maximum(theta, 0.0))
+            ratio = est / (smax * np.maximum(s, np.sqrt(eps) * smax))
+            history.append(float(ratio.max()))
+            converged = bool(ratio.max() <= tol)
+            if converged or cycles >= max_cycles:
+                break
+            _, Z, sigma, T = restart_coeffs(m, b, r, T, beta[m], "largest")
+            self.panel_compress(X, xstride, m, r, torch.from_numpy(Z).to(**kw), n=n)
+            Zk = Z.transpose(1, 2, 0, 3).reshape(m * b, r * b)
+            q[:r * b] = torch.from_numpy(f64(q) @ Zk).to(**kw)
+            self.block_lanczos_reorth_resume(None, r, m, lc, torch.from_numpy(sigma).to(**kw), q, al, be, X, xstride,
+                                             W, passes=passes, normal=normal)
+            alpha, beta = f64(al), f64(be)
+            restart_fill(r, m, b, alpha, beta, T)
+            n_spmm += 2 * (m - r)
+            cycles += 1
+        # the wanted Ritz vectors of G, in place, into the first ceil(k / b) blocks
+        nch = -(-k // b)
+        Zx = np.zeros((nch, m, b, b))
+        for c in range(nch):
+            w = min(b, k - c * b)
+            Zx[c, :, :, :w] = S[:, c * b:c * b + w].reshape(m, b, w)
+        self.panel_compress(X, xstride, m, nch, torch.from_numpy(Zx).to(**kw), n=n)
+        X = X[:nch * xstride]
+        # the other side: y = P x / ||P x||, and the measured residuals ||Pt y - sigma x||
+        Y = torch.zeros(nch * ystride, **kw)
+        Pw = work.view(p, b)
+        Gm, Dm = torch.empty(b, b, **kw), torch.empty(b, b, **kw)
+        resid = np.zeros(nch * b)
+        sp = np.zeros(nch * b)
+        sp[:k] = s
+        for c in range(nch):
+            Xc = X[c * xstride:c * xstride + n * b].view(n, b)
+            Yc = Y[c * ystride:c * ystride + p * b].view(p, b)
+            self.spmm(P, Xc, Pw)
+            self.mm_tt(Pw, Gm)
+            nrm = np.sqrt(np.maximum(np.diag(f64(Gm)), 0.0))
+            inv = np.divide(1.0, nrm, out=np.zeros_like(nrm), where=nrm > 0)
+            Dm.copy_(torch.from_numpy(np.diag(inv)).to(**kw))
+            self.mm_ts(0.0, 1.0, Pw, Dm, Yc)
+            self.spmm(Pt, Yc, W)
+            Dm.copy_(torch.from_numpy(np.diag(sp[c * b:(c + 1) * b])).to(**kw))
+            self.mm_ts(1.0, -1.0, Xc, Dm, W)
+            self.mm_tt(W, Gm)
+            resid[c * b:(c + 1) * b] = np.sqrt(np.maximum(np.diag(f64(Gm)), 0.0))
+            n_spmm += 2
+        U, ustride, Vv, vstride = (Y, ystride, X, xstride) if P is A else (X, xstride, Y, ystride)
+        return dict(s=s, U=U, ustride=ustride, V=Vv, vstride=vstride, resid=resid[:k], est=est, cycles=cycles,
+                    n_spmm=n_spmm, converged=converged, history=history, At=At)
 
     def _eigsh_cheb(self, A, nev, which, b, m, r, tol, max_cycles, B, lc, passes, degree, cut, V, vstride, W, q, al,
                     be):

@@ -293,22 +293,67 @@ static int cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, c
     return LZ_OK;
 }
 
-// W = A Q, or (f != nullptr) W = p(A) Q: the operator line of the kept-basis solves
+// The operator of a kept-basis solve, in one of three forms:
+//   A          f == nullptr, p == 0: the n x n CSR (rp, col, val)
+//   p(A)       f != nullptr: the Chebyshev filter on it, work 2 n b elements
+//   P^T (P Q)  p > 0: (rp, col, val) is P, p x n, and (trp, tcol, tval) its n x p
+//              transpose Pt; work p b elements
 template <typename T>
-static int reorth_op(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
-                     const T *Q, T *W, const lz_cheb *f, T *work)
+struct ReorthOp {
+    int64_t nnz;
+    const int64_t *rp;
+    const int32_t *col;
+    const T *val;
+    const lz_cheb *f = nullptr;
+    T *work = nullptr;
+    int64_t p = 0;
+    const int64_t *trp = nullptr;
+    const int32_t *tcol = nullptr;
+    const T *tval = nullptr;
+};
+
+// the normal-operator form of a kept-basis solve: P is the entry point's CSR (p x n), this its
+// transpose and the p b elements between the two SpMMs
+struct NormalArgs {
+    int64_t p;
+    const int64_t *t_rp;
+    const int32_t *t_col;
+    const void *t_val;
+    void *work;
+};
+
+template <typename T>
+static ReorthOp<T> make_op(int64_t nnz, const int64_t *rp, const int32_t *col, const void *val, const lz_cheb *f,
+                           void *work, const NormalArgs *nm)
 {
-    if (!f) return spmm_rm<T>(h, n, nnz, rp, col, val, b, Q, b, n, W, b);
-    return cheb_apply<T>(h, n, nnz, rp, col, val, b, *f, Q, W, work);
+    ReorthOp<T> op{nnz, rp, col, (const T *)val};
+    if (nm) {
+        op.p = nm->p, op.trp = nm->t_rp, op.tcol = nm->t_col, op.tval = (const T *)nm->t_val;
+        op.work = (T *)nm->work;
+    } else {
+        op.f = f, op.work = (T *)work;
+    }
+    return op;
+}
+
+// W = op Q: the operator line of the kept-basis solves
+template <typename T>
+static int reorth_op(lz_handle *h, int64_t n, int b, const ReorthOp<T> &op, const T *Q, T *W)
+{
+    if (op.p > 0) {
+        LZ_TRY(spmm_rm<T>(h, op.p, op.nnz, op.rp, op.col, op.val, b, Q, b, n, op.work, b));
+        return spmm_rm<T>(h, n, op.nnz, op.trp, op.tcol, op.tval, b, op.work, b, op.p, W, b);
+    }
+    if (!op.f) return spmm_rm<T>(h, n, op.nnz, op.rp, op.col, op.val, b, Q, b, n, W, b);
+    return cheb_apply<T>(h, n, op.nnz, op.rp, op.col, op.val, b, *op.f, Q, W, op.work);
 }
 
 // Steps j0 .. m - 1 (j0 >= 1; block j0 - 1 holds Q_{j0-1}, W the residual of
 // step j0 - 1), then beta_m of the final residual: the part a first cycle and
 // a resumed one share.
 template <typename T>
-static int reorth_steps(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val,
-                        int b, int j0, int m, int64_t lc, T *q, T *alpha, T *beta, T *V, int64_t vstride, T *W,
-                        int passes, const lz_cheb *f, T *work)
+static int reorth_steps(lz_handle *h, int64_t n, const ReorthOp<T> &op, int b, int j0, int m, int64_t lc, T *q,
+                        T *alpha, T *beta, T *V, int64_t vstride, T *W, int passes)
 {
     const int64_t bb = (int64_t)b * b;
     T *binv = ScratchT<T>(h, b).binv[0];
@@ -319,7 +364,7 @@ static int reorth_steps(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp,
         LZ_TRY(gram_partials<T>(h, n, b, W, W, b, &P));
         LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, bj, binv, nullptr));     // beta_j = sqrtm(W'W)
         LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), W, binv, Qj, b));           // Q_j = W beta_j^-1
-        LZ_TRY(reorth_op<T>(h, n, nnz, rp, col, val, b, Qj, W, f, work)); // W = A Q_j (or p(A) Q_j)
+        LZ_TRY(reorth_op<T>(h, n, b, op, Qj, W));                       // W = op Q_j
         LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qp, bj, W, b));            // W -= Q_{j-1} beta_j
         LZ_TRY(gram_partials<T>(h, n, b, W, Qj, b, &P));
         LZ_TRY(gram_finish<T>(h, b, P, 1, aj));                         // alpha_j
@@ -333,9 +378,8 @@ static int reorth_steps(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp,
 }
 
 template <typename T>
-static int block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
-                                const T *val, int b, int m, int64_t lc, const T *B, T *q, T *alpha, T *beta, T *V,
-                                int64_t vstride, T *W, int passes, const lz_cheb *f, T *work)
+static int block_lanczos_reorth(lz_handle *h, int64_t n, const ReorthOp<T> &op, int b, int m, int64_t lc, const T *B,
+                                T *q, T *alpha, T *beta, T *V, int64_t vstride, T *W, int passes)
 {
     T *binv = ScratchT<T>(h, b).binv[0];
     LZ_TRY(reorth_reserve<T>(h, n, b, m, passes));
@@ -345,12 +389,12 @@ static int block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int6
     LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, beta, binv, nullptr));      // beta_0 = sqrtm(B'B)
     LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), B, binv, Qj, b));               // Q_0 = B beta_0^-1
     LZ_TRY(copy_row<T>(h, b, Qj, b, 0, lc, q));
-    LZ_TRY(reorth_op<T>(h, n, nnz, rp, col, val, b, Qj, W, f, work));   // W = A Q_0
+    LZ_TRY(reorth_op<T>(h, n, b, op, Qj, W));                           // W = op Q_0
     LZ_TRY(gram_partials<T>(h, n, b, W, Qj, b, &P));
     LZ_TRY(gram_finish<T>(h, b, P, 1, alpha));                          // alpha_0
     LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qj, alpha, W, b));             // W -= Q_0 alpha_0
     LZ_TRY(reorth_rounds<T>(h, n, b, 1, V, vstride, W, passes));
-    return reorth_steps<T>(h, n, nnz, rp, col, val, b, 1, m, lc, q, alpha, beta, V, vstride, W, passes, f, work);
+    return reorth_steps<T>(h, n, op, b, 1, m, lc, q, alpha, beta, V, vstride, W, passes);
 }
 
 // A cycle on a thick-restarted basis (lz_block_lanczos_reorth_resume): blocks
@@ -360,10 +404,9 @@ static int block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int6
 // ordinary step subtracts Q_{j-1} beta_j; from step r + 1 on the recurrence is
 // the three-term one again.
 template <typename T>
-static int block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
-                                       const T *val, int b, int r, int m, int64_t lc, const T *sigma, T *q,
-                                       T *alpha, T *beta, T *V, int64_t vstride, T *W, int passes, const lz_cheb *f,
-                                       T *work)
+static int block_lanczos_reorth_resume(lz_handle *h, int64_t n, const ReorthOp<T> &op, int b, int r, int m, int64_t lc,
+                                       const T *sigma, T *q, T *alpha, T *beta, T *V, int64_t vstride, T *W,
+                                       int passes)
 {
     const int64_t bb = (int64_t)b * b;
     T *binv = ScratchT<T>(h, b).binv[0];
@@ -373,15 +416,14 @@ static int block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, con
     LZ_TRY(gram_partials<T>(h, n, b, W, W, b, &P));
     LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, br, binv, nullptr));         // beta_r = sqrtm(W'W)
     LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), W, binv, Qr, b));               // Q_r = W beta_r^-1
-    LZ_TRY(reorth_op<T>(h, n, nnz, rp, col, val, b, Qr, W, f, work));   // W = A Q_r
+    LZ_TRY(reorth_op<T>(h, n, b, op, Qr, W));                           // W = op Q_r
     LZ_TRY(panel_apply<T>(h, n, b, r, 1.0, -1.0, V, vstride, sigma, W)); // W -= sum_i Y_i S_i
     LZ_TRY(gram_partials<T>(h, n, b, W, Qr, b, &P));
     LZ_TRY(gram_finish<T>(h, b, P, 1, ar));                             // alpha_r
     LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qr, ar, W, b));                // W -= Q_r alpha_r
     LZ_TRY(reorth_rounds<T>(h, n, b, r + 1, V, vstride, W, passes));
     LZ_TRY(copy_row<T>(h, b, Qr, b, 0, lc, q + (int64_t)r * b));
-    return reorth_steps<T>(h, n, nnz, rp, col, val, b, r + 1, m, lc, q, alpha, beta, V, vstride, W, passes, f,
-                           work);
+    return reorth_steps<T>(h, n, op, b, r + 1, m, lc, q, alpha, beta, V, vstride, W, passes);
 }
 
 // Fused device-resident iteration, b = 16 fp64 (lz_fused.hip), Q-free: the
@@ -1525,6 +1567,7 @@ int lz_finalize(lz_handle *h)
     (void)hipFree(h->cm_buf);
     (void)hipFree(h->ybuf);
     (void)hipFree(h->coef);
+    (void)hipFree(h->tr_ws);
     (void)hipFree(h->c16buf);
     (void)hipFree(h->wf_deps);
     (void)hipFree(h->wf_flags);
@@ -1878,6 +1921,73 @@ static int cheb_solve_args(const lz_cheb *f, const void *work, int64_t n, int b,
     return LZ_OK;
 }
 
+// work (p b) apart from W, B (may be null) and the panel, as cheb_solve_args
+static int normal_solve_args(const NormalArgs *nm, int64_t n, int b, int m, lz_dtype dtype, const void *V,
+                             int64_t vstride, const void *W, const void *B)
+{
+    if (!nm) return LZ_OK;
+    LZ_ARG_CHECK(nm->p >= 1, "normal operator: p >= 1");
+    LZ_ARG_CHECK(nm->t_rp != nullptr, "normal operator: the transpose's row_ptr is NULL");
+    LZ_ARG_CHECK(nm->t_col != nullptr && nm->t_val != nullptr, "normal operator: the transpose's col/val NULL");
+    LZ_ARG_CHECK(nm->work != nullptr, "work is NULL");
+    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b, pb = nm->p * b;
+    LZ_ARG_CHECK(reinterpret_cast<uintptr_t>(nm->work) % 16 == 0, "work must be on 16 bytes");
+    LZ_ARG_CHECK(blocks_apart(nm->work, pb, W, nb, es) && (!B || blocks_apart(nm->work, pb, B, nb, es)) &&
+                     blocks_apart(nm->work, pb, V, (int64_t)(m - 1) * vstride + nb, es),
+                 "work must not overlap B, W or the panel V");
+    return LZ_OK;
+}
+
+int lz_csr_transpose(lz_handle *h, int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t *rp, const int32_t *col,
+                     const void *val, lz_dtype dtype, int64_t *t_rp, int32_t *t_col, void *t_val)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n_rows, nnz, rp, col, val));
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n_rows < (1LL << 31), "n_rows < 2^31 (t_col holds source rows)");
+    LZ_ARG_CHECK(n_cols >= 0 && n_cols < (1LL << 31), "0 <= n_cols < 2^31");
+    LZ_ARG_CHECK(nnz < (1LL << 32) - 1, "nnz < 2^32 - 1");
+    LZ_ARG_CHECK(nnz == 0 || n_rows >= 1, "entries without rows");
+    LZ_ARG_CHECK(t_rp != nullptr && (nnz == 0 || (t_col != nullptr && t_val != nullptr)), "output NULL");
+    {
+        const int64_t es = dtype == LZ_F64 ? 8 : 4;
+        struct R { const void *p; int64_t bytes; };
+        const R in[3] = {{rp, (n_rows + 1) * 8}, {col, nnz * 4}, {val, nnz * es}};
+        const R out[3] = {{t_rp, (n_cols + 1) * 8}, {t_col, nnz * 4}, {t_val, nnz * es}};
+        bool apart = true;
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) apart = apart && blocks_apart(out[i].p, out[i].bytes, in[j].p, in[j].bytes, 1);
+            for (int j = i + 1; j < 3; ++j) apart = apart && blocks_apart(out[i].p, out[i].bytes, out[j].p, out[j].bytes, 1);
+        }
+        LZ_ARG_CHECK(apart, "the outputs must be distinct from each other and from the inputs");
+    }
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return csr_transpose<T>(h, n_rows, n_cols, nnz, rp, col, (const T *)val, t_rp, t_col, (T *)t_val);
+    });
+}
+
+int lz_normal_apply(lz_handle *h, int64_t n, int64_t p, int64_t nnz, const int64_t *rp, const int32_t *col,
+                    const void *val, const int64_t *t_rp, const int32_t *t_col, const void *t_val, lz_dtype dtype, int b,
+                    const void *X, void *Y, void *work)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(p, nnz, rp, col, val));
+    LZ_TRY(check_csr(n, nnz, t_rp, t_col, t_val));
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n >= 1 && p >= 1 && b >= 1 && b <= kMaxB, "n, p >= 1, b in [1,64]");
+    LZ_ARG_CHECK(X && Y && work, "X/Y/work NULL");
+    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b, pb = p * b;
+    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && blocks_apart(work, pb, X, nb, es) &&
+                     blocks_apart(work, pb, Y, nb, es),
+                 "X, Y and work must be pairwise distinct");
+    const NormalArgs nm{p, t_rp, t_col, t_val, work};
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return reorth_op<T>(h, n, b, make_op<T>(nnz, rp, col, val, nullptr, nullptr, &nm), (const T *)X, (T *)Y);
+    });
+}
+
 int lz_csr_spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
                       lz_dtype dtype, int b, double a, const void *X, double c, double d, const void *Z, void *Y)
 {
@@ -1923,13 +2033,14 @@ int lz_block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t 
                                         passes, nullptr, nullptr);
 }
 
-int lz_block_lanczos_reorth_cheb(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
-                                 const void *val, lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q,
-                                 void *alpha, void *beta, void *V, int64_t vstride, void *W, int passes,
-                                 const lz_cheb *f, void *work)
+// lz_block_lanczos_reorth and its _cheb (f) and _normal (nm) forms
+static int reorth_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                        lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q, void *alpha, void *beta,
+                        void *V, int64_t vstride, void *W, int passes, const lz_cheb *f, void *work,
+                        const NormalArgs *nm)
 {
     LZ_HANDLE_CHECK(h);
-    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_TRY(check_csr(nm ? nm->p : n, nnz, rp, col, val));
     LZ_ARG_CHECK(m >= 1 && m <= kPanelMaxK, "the kept basis holds 1 <= m <= 64 blocks");
     LZ_TRY(panel_args(n, b, m, dtype, V, vstride));
     LZ_ARG_CHECK(passes >= 0 && passes <= 2, "passes in {0, 1, 2}");
@@ -1943,11 +2054,31 @@ int lz_block_lanczos_reorth_cheb(lz_handle *h, int64_t n, int64_t nnz, const int
                      "B, W and the panel V must be distinct buffers");
     }
     LZ_TRY(cheb_solve_args(f, work, n, b, m, dtype, V, vstride, W, B));
+    LZ_TRY(normal_solve_args(nm, n, b, m, dtype, V, vstride, W, B));
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        return block_lanczos_reorth<T>(h, n, nnz, rp, col, (const T *)val, b, m, lc, (const T *)B, (T *)q, (T *)alpha,
-                                       (T *)beta, (T *)V, vstride, (T *)W, passes, f, (T *)work);
+        return block_lanczos_reorth<T>(h, n, make_op<T>(nnz, rp, col, val, f, work, nm), b, m, lc, (const T *)B, (T *)q,
+                                       (T *)alpha, (T *)beta, (T *)V, vstride, (T *)W, passes);
     });
+}
+
+int lz_block_lanczos_reorth_cheb(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                                 const void *val, lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q,
+                                 void *alpha, void *beta, void *V, int64_t vstride, void *W, int passes,
+                                 const lz_cheb *f, void *work)
+{
+    return reorth_entry(h, n, nnz, rp, col, val, dtype, b, m, lc, B, q, alpha, beta, V, vstride, W, passes, f, work,
+                        nullptr);
+}
+
+int lz_block_lanczos_reorth_normal(lz_handle *h, int64_t n, int64_t p, int64_t nnz, const int64_t *rp,
+                                   const int32_t *col, const void *val, const int64_t *t_rp, const int32_t *t_col,
+                                   const void *t_val, lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q,
+                                   void *alpha, void *beta, void *V, int64_t vstride, void *W, int passes, void *work)
+{
+    const NormalArgs nm{p, t_rp, t_col, t_val, work};
+    return reorth_entry(h, n, nnz, rp, col, val, dtype, b, m, lc, B, q, alpha, beta, V, vstride, W, passes, nullptr,
+                        nullptr, &nm);
 }
 
 int lz_panel_compress(lz_handle *h, int64_t n, int b, int k, int r, lz_dtype dtype, void *V, int64_t vstride,
@@ -1973,13 +2104,14 @@ int lz_block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, const i
                                                vstride, W, passes, nullptr, nullptr);
 }
 
-int lz_block_lanczos_reorth_resume_cheb(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
-                                        const void *val, lz_dtype dtype, int b, int r, int m, int64_t lc,
-                                        const void *sigma, void *q, void *alpha, void *beta, void *V, int64_t vstride,
-                                        void *W, int passes, const lz_cheb *f, void *work)
+// lz_block_lanczos_reorth_resume and its _cheb (f) and _normal (nm) forms
+static int resume_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                        lz_dtype dtype, int b, int r, int m, int64_t lc, const void *sigma, void *q, void *alpha,
+                        void *beta, void *V, int64_t vstride, void *W, int passes, const lz_cheb *f, void *work,
+                        const NormalArgs *nm)
 {
     LZ_HANDLE_CHECK(h);
-    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_TRY(check_csr(nm ? nm->p : n, nnz, rp, col, val));
     LZ_ARG_CHECK(m >= 1 && m <= kPanelMaxK, "the kept basis holds 1 <= m <= 64 blocks");
     LZ_ARG_CHECK(r >= 1 && r < m, "a resumed solve keeps 1 <= r < m blocks");
     LZ_TRY(panel_args(n, b, m, dtype, V, vstride));
@@ -1994,12 +2126,33 @@ int lz_block_lanczos_reorth_resume_cheb(lz_handle *h, int64_t n, int64_t nnz, co
         LZ_ARG_CHECK(w0 + n * b * es <= v0 || w0 >= v1, "W and the panel V must be distinct buffers");
     }
     LZ_TRY(cheb_solve_args(f, work, n, b, m, dtype, V, vstride, W, nullptr));
+    LZ_TRY(normal_solve_args(nm, n, b, m, dtype, V, vstride, W, nullptr));
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        return block_lanczos_reorth_resume<T>(h, n, nnz, rp, col, (const T *)val, b, r, m, lc, (const T *)sigma,
-                                              (T *)q, (T *)alpha, (T *)beta, (T *)V, vstride, (T *)W, passes, f,
-                                              (T *)work);
+        return block_lanczos_reorth_resume<T>(h, n, make_op<T>(nnz, rp, col, val, f, work, nm), b, r, m, lc,
+                                              (const T *)sigma, (T *)q, (T *)alpha, (T *)beta, (T *)V, vstride,
+                                              (T *)W, passes);
     });
+}
+
+int lz_block_lanczos_reorth_resume_cheb(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                                        const void *val, lz_dtype dtype, int b, int r, int m, int64_t lc,
+                                        const void *sigma, void *q, void *alpha, void *beta, void *V, int64_t vstride,
+                                        void *W, int passes, const lz_cheb *f, void *work)
+{
+    return resume_entry(h, n, nnz, rp, col, val, dtype, b, r, m, lc, sigma, q, alpha, beta, V, vstride, W, passes, f,
+                        work, nullptr);
+}
+
+int lz_block_lanczos_reorth_resume_normal(lz_handle *h, int64_t n, int64_t p, int64_t nnz, const int64_t *rp,
+                                          const int32_t *col, const void *val, const int64_t *t_rp,
+                                          const int32_t *t_col, const void *t_val, lz_dtype dtype, int b, int r, int m,
+                                          int64_t lc, const void *sigma, void *q, void *alpha, void *beta, void *V,
+                                          int64_t vstride, void *W, int passes, void *work)
+{
+    const NormalArgs nm{p, t_rp, t_col, t_val, work};
+    return resume_entry(h, n, nnz, rp, col, val, dtype, b, r, m, lc, sigma, q, alpha, beta, V, vstride, W, passes,
+                        nullptr, nullptr, &nm);
 }
 
 int lz_vector_lanczos(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,

@@ -109,7 +109,9 @@ struct lz_handle {
     size_t ybuf_cap = 0;          // bytes
     void *coef = nullptr;         // lz_block_lanczos_reorth: the panel Gram's m b x b coefficients
     size_t coef_cap = 0;          // bytes
-    void *halo = nullptr;         // lz::HaloPlan when lz_halo_init was called
+    void *tr_ws = nullptr;        // lz_csr_transpose: keys, merge buffer / ranks, counts, block sums, class lists
+    size_t tr_cap = 0;            // bytes
+    void *halo = nullptr;        // lz::HaloPlan when lz_halo_init was called
     uint64_t *pairs = nullptr;    // per-16-row-strip row order by length (k_strip_pairs)
     int *longq = nullptr;         // k_spmm_seg long-tile queue: [0], [1] counts (alternate calls), [2..] tile ids
     size_t longq_cap = 0;         // bytes
@@ -175,6 +177,7 @@ enum FlagWord {
     kFlagLongTiles = 4,   // spmm_b2_stage: tiles over the small stage
     kFlagWindow = 8,      // gather_window_ok: a column outside its strip's window
     kFlagCol16 = 9,       // col16_plan: a column out of int16 reach
+    kFlagTrCol = 10,      // csr_transpose: a column outside [0, n_cols)
     // 4 words, shared by wf_plan16 (spans: [0] back, [1] forward, [2] max span,
     // [3] bits) and fnz_prepare (stats: [0] max row length, [1] empty /
     // negative, [2] max rows per tile).  Each owns them from its memset to its

@@ -26,6 +26,22 @@ template <typename T>
 int spmv(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, const T *val, const T *x,
          T *y, int64_t nnz_hint);
 
+// ---- CSR transpose (lz_transpose.hip): t_* = the CSR of A^T, output row c holding A's
+// entries of column c in the order of their positions in A's arrays (bitwise
+// deterministic).  Sort classes of an output row by its length len: len <= kTrShort one
+// lane group, len <= kTrLds one workgroup through LDS, longer rows chunks of kTrLds
+// through LDS and pairwise merges.  The scan covers kTrScanBlock counts per workgroup.
+// nnz < 2^32 - 1, n_rows < 2^31 (checked by the caller).  Synchronises the stream once
+// (the column range check), beside the grower of h->tr_ws.
+constexpr int kTrShort = 16;
+constexpr int kTrLds = 4096;
+constexpr int kTrScanThreads = 256, kTrScanPer = 8, kTrScanBlock = kTrScanThreads * kTrScanPer;
+constexpr int kTrSortThreads = 1024;
+static_assert((kTrLds & (kTrLds - 1)) == 0 && (kTrScanThreads & (kTrScanThreads - 1)) == 0, "powers of two");
+template <typename T>
+int csr_transpose(lz_handle *h, int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t *rp, const int32_t *col,
+                  const T *val, int64_t *t_rp, int32_t *t_col, T *t_val);
+
 // ---- dense (lz_dense.hip)
 // partial b x b products of X^T Y, one slab per workgroup, into h->partials;
 // returns the number of slabs in *nparts.

@@ -322,6 +322,47 @@ int lz_block_lanczos_reorth_resume_cheb(lz_handle *h, int64_t n, int64_t nnz, co
                                         int64_t lc, const void *sigma, void *q, void *alpha, void *beta, void *V,
                                         int64_t vstride, void *W, int passes, const lz_cheb *f, void *work);
 
+/* ------------------------- transpose and normal operator (no reference counterpart)
+ * The CSR of A^T, built on the device: output row c (c < n_cols) holds the
+ * entries of A whose column is c in the order of their positions in A's
+ * arrays -- ascending source row; duplicate (row, col) pairs keep their order;
+ * the columns within a source row need not be sorted.  t_row_ptr[n_cols + 1],
+ * t_col[nnz] (source rows), t_val[nnz]: caller-owned, distinct from each other
+ * and from the inputs.  Bitwise reproducible (integer atomics for the column
+ * histogram only, whose arrival order places the entries; every output row is
+ * then sorted by source position).  LZ_E_ARG: n_rows >= 2^31, nnz >= 2^32 - 1, a column
+ * outside [0, n_cols) (nothing is written then), overlapping arrays.  nnz = 0,
+ * empty rows and empty columns are valid.  Workspace on the handle: 16 nnz +
+ * 4 n_cols bytes and two short lists.  Synchronises the stream once, to read
+ * the column check's word (and when the workspace grows). */
+int lz_csr_transpose(lz_handle *h, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                     const int64_t *row_ptr, const int32_t *col, const void *val, lz_dtype dtype,
+                     int64_t *t_row_ptr, int32_t *t_col, void *t_val);
+
+/* Y = Pt (P X): the normal operator G = P^T P of a p x n CSR P, given together
+ * with its n x p transpose Pt (lz_csr_transpose), as two lz_csr_spmm.  X, Y:
+ * n x b row-major with ld = b, distinct; work: p b elements (P X), distinct from
+ * both; 1 <= b <= 64.  No host synchronisation. */
+int lz_normal_apply(lz_handle *h, int64_t n, int64_t p, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                    const void *val, const int64_t *t_row_ptr, const int32_t *t_col, const void *t_val,
+                    lz_dtype dtype, int b, const void *X, void *Y, void *work);
+/* lz_block_lanczos_reorth / lz_block_lanczos_reorth_resume on G = P^T P: every
+ * W = A Q_j of the solve becomes lz_normal_apply (work as there, on 16 bytes,
+ * distinct from B, W and the panel).  n: the Lanczos dimension (columns of P);
+ * passes, beta[m] and the row probe q (row lc of Q_j, lc < n) as in the plain
+ * entry points.  alpha, beta and the projected matrix are those of G: its
+ * eigenvalues are the squared singular values of P. */
+int lz_block_lanczos_reorth_normal(lz_handle *h, int64_t n, int64_t p, int64_t nnz, const int64_t *row_ptr,
+                                   const int32_t *col, const void *val, const int64_t *t_row_ptr,
+                                   const int32_t *t_col, const void *t_val, lz_dtype dtype, int b, int m, int64_t lc,
+                                   const void *B, void *q, void *alpha, void *beta, void *V, int64_t vstride, void *W,
+                                   int passes, void *work);
+int lz_block_lanczos_reorth_resume_normal(lz_handle *h, int64_t n, int64_t p, int64_t nnz, const int64_t *row_ptr,
+                                          const int32_t *col, const void *val, const int64_t *t_row_ptr,
+                                          const int32_t *t_col, const void *t_val, lz_dtype dtype, int b, int r, int m,
+                                          int64_t lc, const void *sigma, void *q, void *alpha, void *beta, void *V,
+                                          int64_t vstride, void *W, int passes, void *work);
+
 /* Single-vector Lanczos.  Replaces vector_lanczos<T>(A, b, m, lc, q, alpha,
  * beta, q0, q1, w) (methods/vector_lanczos.hpp:8-67; the correct variant -- the
  * BLAS variant's axpy at :116 is a reference bug not reproduced).  alpha[m],
