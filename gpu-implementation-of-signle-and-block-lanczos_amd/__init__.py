@@ -24,7 +24,7 @@ from __future__ import annotations
 import ctypes
 import os
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -621,6 +621,124 @@ class CsrDevice:
         return CsrDevice(self.n_cols, self.n, t_rp, t_col, t_val)
 
 
+class _ReorthOp(NamedTuple):
+    """What Handle._reorth_op makes of A / filt / work / normal: fn(handle, *head, b, ..., passes, *tail)."""
+    name: str                    # the ABI function
+    head: tuple                  # n [, P.n], nnz, the CSR pointers [and the transpose's], dtype
+    tail: tuple                  # nothing | &filt, work | work
+    filt: Optional[ChebFilter]   # the struct tail points to: alive as long as this description
+
+
+def _f64(t) -> np.ndarray:
+    """A device tensor copied back to the host, as fp64."""
+    return t.cpu().numpy().astype(np.float64)
+
+
+def _panel_stride(rows: int, b: int, like) -> int:
+    """The stride of a panel of (rows, b) blocks of like's dtype: every block on 16 bytes."""
+    per16 = 16 // like.element_size()
+    return -(-rows * b // per16) * per16
+
+
+def _pack_chunks(S: np.ndarray, m: int, b: int) -> np.ndarray:
+    """Host coefficients S (m*b, nev) in panel_compress's layout: (ceil(nev / b), m, b, b),
+    chunk c holding columns [c*b, (c+1)*b) of S, the last zero-padded."""
+    nev = S.shape[1]
+    nch = -(-nev // b)
+    Sp = np.zeros((nch, m, b, b))
+    for c in range(nch):
+        w = min(b, nev - c * b)
+        Sp[c, :, :, :w] = S[:, c * b:c * b + w].reshape(m, b, w)
+    return Sp
+
+
+def _restart_sizes(who: str, count: str, nev: int, b: int, m: Optional[int], keep: Optional[int]):
+    """(m, keep) of a thick-restart solve for nev pairs, with the defaults and limits of
+    eigsh's docstring; who and count name the caller and its nev in the errors."""
+    want = -(-(nev + b) // b)  # the smallest keep with keep * b >= nev + b
+    if m is None:
+        m = min(PANEL_MAX_BLOCKS, max(4, 2 * want))
+    r = min(want, PANEL_MAX_KEEP, m - 1) if keep is None else keep
+    if nev < 1 or r * b < nev:
+        raise LanczosError(f"{who}: keep * b = {r * b} < {count} = {nev}")
+    if r >= m:
+        raise LanczosError(f"{who}: keep = {r} >= m = {m}")
+    if r > PANEL_MAX_KEEP or m > PANEL_MAX_BLOCKS or r < 1:
+        raise LanczosError(f"{who}: 1 <= keep <= {PANEL_MAX_KEEP} and m <= {PANEL_MAX_BLOCKS}")
+    return m, r
+
+
+class _Restart:
+    """The thick-restart loop that eigsh, its filtered form and svds share, as steps: it owns
+    the panel V (m blocks of (n, b), vstride apart), W, q / al / be with their host copies
+    alpha / beta, the projected matrix T, the operator keywords op (filt + work, or normal:
+    one operator for every cycle of a solve) and the counters.
+
+        first(B)         block_lanczos_reorth from B, copy back, Assemble_T
+        ritz(which)      all m*b Ritz pairs of T: theta, S, resid, max|theta|
+        compress(which)  restart_coeffs, then panel_compress onto the keep*b kept pairs
+        resume()         row lc of the kept blocks into q, block_lanczos_reorth_resume,
+                         copy back, restart_fill
+        pack(S, nev)     panel_compress onto the Ritz vectors of S[:, :nev]; returns their blocks
+
+    One copy-back each of q, al and be per cycle; the callers keep the stop test."""
+
+    def __init__(self, h: "Handle", A, n: int, b: int, m: int, r: int, lc: int, passes: int, like, **op):
+        torch = _torch()
+        self.h, self.A, self.n, self.b, self.m, self.r = h, A, n, b, m, r
+        self.lc, self.passes, self.op = lc, passes, op
+        self.kw = kw = dict(dtype=like.dtype, device=like.device)
+        self.npdt = np.float64 if like.dtype == torch.float64 else np.float32
+        self.vstride = _panel_stride(n, b, like)
+        self.V = torch.zeros(m * self.vstride, **kw)
+        self.W = torch.empty(n, b, **kw)
+        self.q = torch.zeros(m * b, **kw)
+        self.al, self.be = torch.zeros(m, b, b, **kw), torch.zeros(m + 1, b, b, **kw)
+        self.steps = self.cycles = 0  # Lanczos steps of every solve on these buffers; cycles of the last first()
+
+    def start_block(self, B):
+        """B, or the default start block uniform_B(n, b) on the device."""
+        if B is not None:
+            return B
+        return _torch().from_numpy(uniform_B(self.n, self.b, dtype=self.npdt)).to(self.kw["device"])
+
+    def _dev(self, a: np.ndarray):
+        return _torch().from_numpy(a).to(**self.kw)
+
+    def first(self, B):
+        self.h.block_lanczos_reorth(self.A, B, self.m, self.lc, self.q, self.al, self.be, self.V, self.vstride, self.W,
+                                    passes=self.passes, **self.op)
+        self.steps += self.m
+        self.cycles = 1
+        self.alpha, self.beta = _f64(self.al), _f64(self.be)
+        self.T = Assemble_T(self.m, self.b, self.alpha, self.beta[:self.m])
+
+    def ritz(self, which: str):
+        theta, S, resid = ritz_pairs_dense(self.m, self.b, self.T, self.beta[self.m], self.m * self.b, which)
+        return theta, S, resid, float(np.abs(theta).max())
+
+    def compress(self, which: str):
+        _, self.Z, self.sigma, self.T = restart_coeffs(self.m, self.b, self.r, self.T, self.beta[self.m], which)
+        self.h.panel_compress(self.V, self.vstride, self.m, self.r, self._dev(self.Z), n=self.n)
+
+    def resume(self):
+        m, b, r = self.m, self.b, self.r
+        # row lc of Y = P Z_k
+        Zk = self.Z.transpose(1, 2, 0, 3).reshape(m * b, r * b)
+        self.q[:r * b] = self._dev(_f64(self.q) @ Zk)
+        self.h.block_lanczos_reorth_resume(self.A, r, m, self.lc, self._dev(self.sigma), self.q, self.al, self.be,
+                                           self.V, self.vstride, self.W, passes=self.passes, **self.op)
+        self.alpha, self.beta = _f64(self.al), _f64(self.be)
+        restart_fill(r, m, b, self.alpha, self.beta, self.T)
+        self.steps += m - r
+        self.cycles += 1
+
+    def pack(self, S: np.ndarray, nev: int) -> int:
+        Zx = _pack_chunks(S[:, :nev], self.m, self.b)
+        self.h.panel_compress(self.V, self.vstride, self.m, len(Zx), self._dev(Zx), n=self.n)
+        return len(Zx)
+
+
 class Handle:
     """lz_handle on one device, bound to torch's current stream at each call."""
 
@@ -709,6 +827,23 @@ class Handle:
                 or work.dtype != like.dtype:
             raise LanczosError(f"{what}: work is a flat contiguous tensor of p*b elements of the solve's dtype")
         return P, Pt, work
+
+    def _reorth_op(self, what: str, A, n: int, b: int, like, filt, work, normal) -> "_ReorthOp":
+        """The operator of a kept-basis solve (A, p(A) or Pt (P .): block_lanczos_reorth's
+        docstring), validated, as the ABI function lz_<what>[_cheb | _normal] with the
+        arguments that differ between the three."""
+        csr = lambda M: (_ptr(M.row_ptr), _ptr(M.col), _ptr(M.val))
+        if normal is not None:
+            if filt is not None:
+                raise LanczosError(f"{what}: normal= and filt= are mutually exclusive")
+            P, Pt, nwork = self._normal(what, normal, n, b, like)
+            return _ReorthOp(f"lz_{what}_normal", (n, P.n, P.nnz, *csr(P), *csr(Pt), P.dtype), (_ptr(nwork),), None)
+        head = (n, A.nnz, *csr(A), A.dtype)
+        if filt is None:
+            return _ReorthOp(f"lz_{what}", head, (), None)
+        self._work(what, work, n, b, like)
+        f = _cheb(filt)
+        return _ReorthOp(f"lz_{what}_cheb", head, (ctypes.addressof(f), _ptr(work)), f)
 
     def normal_apply(self, P: CsrDevice, Pt: CsrDevice, X, Y, work):
         """Y = Pt (P X) (lz_normal_apply): P (p, n), Pt = P.transpose(handle), X / Y (n, b)
@@ -830,27 +965,9 @@ class Handle:
         and filt must be None."""
         n, b = B.shape
         self._panel(V, vstride, n, b, max(m, 1))
-        if normal is not None:
-            if filt is not None:
-                raise LanczosError("block_lanczos_reorth: normal= and filt= are mutually exclusive")
-            P, Pt, nwork = self._normal("block_lanczos_reorth", normal, n, b, W)
-            _check(self.L.lz_block_lanczos_reorth_normal(self.ptr, n, P.n, P.nnz, _ptr(P.row_ptr), _ptr(P.col),
-                                                         _ptr(P.val), _ptr(Pt.row_ptr), _ptr(Pt.col), _ptr(Pt.val),
-                                                         P.dtype, b, m, lc, _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta),
-                                                         _ptr(V), vstride, _ptr(W), passes, _ptr(nwork)),
-                   "lz_block_lanczos_reorth_normal")
-            return
-        if filt is None:
-            _check(self.L.lz_block_lanczos_reorth(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val),
-                                                  A.dtype, b, m, lc, _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta),
-                                                  _ptr(V), vstride, _ptr(W), passes), "lz_block_lanczos_reorth")
-            return
-        self._work("block_lanczos_reorth", work, n, b, W)
-        f = _cheb(filt)
-        _check(self.L.lz_block_lanczos_reorth_cheb(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val),
-                                                   A.dtype, b, m, lc, _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta),
-                                                   _ptr(V), vstride, _ptr(W), passes, ctypes.addressof(f),
-                                                   _ptr(work)), "lz_block_lanczos_reorth_cheb")
+        op = self._reorth_op("block_lanczos_reorth", A, n, b, W, filt, work, normal)
+        _check(getattr(self.L, op.name)(self.ptr, *op.head, b, m, lc, _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta),
+                                        _ptr(V), vstride, _ptr(W), passes, *op.tail), op.name)
 
     def ritz_vectors(self, V, vstride: int, S, X, n: int, b: int):
         """X = [V_0 .. V_{m-1}] S: the Ritz vectors of host coefficients S ((m*b, nev),
@@ -870,11 +987,7 @@ class Handle:
         m, nch = mb // b, -(-nev // b)
         self._panel(V, vstride, n, b, m)
         self._panel(X, vstride, n, b, nch)
-        Sp = np.zeros((nch, m, b, b))
-        for c in range(nch):
-            w = min(b, nev - c * b)
-            Sp[c, :, :, :w] = S[:, c * b:c * b + w].reshape(m, b, w)
-        Sd = torch.from_numpy(Sp).to(device=V.device, dtype=V.dtype)
+        Sd = torch.from_numpy(_pack_chunks(S, m, b)).to(device=V.device, dtype=V.dtype)
         for c in range(nch):
             Xc = X[c * vstride:c * vstride + n * b].view(n, b)
             self.panel_apply(0.0, 1.0, V, vstride, m, Sd[c], Xc)
@@ -908,30 +1021,9 @@ class Handle:
         if not sigma.is_contiguous() or sigma.numel() < max(r, 0) * b * b or sigma.dtype != W.dtype \
                 or V.dtype != W.dtype or not W.is_contiguous():
             raise LanczosError("block_lanczos_reorth_resume: W (n, b) and sigma (r, b, b) contiguous, one dtype")
-        if normal is not None:
-            if filt is not None:
-                raise LanczosError("block_lanczos_reorth_resume: normal= and filt= are mutually exclusive")
-            P, Pt, nwork = self._normal("block_lanczos_reorth_resume", normal, n, b, W)
-            _check(self.L.lz_block_lanczos_reorth_resume_normal(self.ptr, n, P.n, P.nnz, _ptr(P.row_ptr), _ptr(P.col),
-                                                                _ptr(P.val), _ptr(Pt.row_ptr), _ptr(Pt.col),
-                                                                _ptr(Pt.val), P.dtype, b, r, m, lc, _ptr(sigma),
-                                                                _ptr(q), _ptr(alpha), _ptr(beta), _ptr(V), vstride,
-                                                                _ptr(W), passes, _ptr(nwork)),
-                   "lz_block_lanczos_reorth_resume_normal")
-            return
-        if filt is None:
-            _check(self.L.lz_block_lanczos_reorth_resume(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col),
-                                                         _ptr(A.val), A.dtype, b, r, m, lc, _ptr(sigma), _ptr(q),
-                                                         _ptr(alpha), _ptr(beta), _ptr(V), vstride, _ptr(W), passes),
-                   "lz_block_lanczos_reorth_resume")
-            return
-        self._work("block_lanczos_reorth_resume", work, n, b, W)
-        f = _cheb(filt)
-        _check(self.L.lz_block_lanczos_reorth_resume_cheb(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col),
-                                                          _ptr(A.val), A.dtype, b, r, m, lc, _ptr(sigma), _ptr(q),
-                                                          _ptr(alpha), _ptr(beta), _ptr(V), vstride, _ptr(W), passes,
-                                                          ctypes.addressof(f), _ptr(work)),
-               "lz_block_lanczos_reorth_resume_cheb")
+        op = self._reorth_op("block_lanczos_reorth_resume", A, n, b, W, filt, work, normal)
+        _check(getattr(self.L, op.name)(self.ptr, *op.head, b, r, m, lc, _ptr(sigma), _ptr(q), _ptr(alpha),
+                                        _ptr(beta), _ptr(V), vstride, _ptr(W), passes, *op.tail), op.name)
 
     def eigsh(self, A: CsrDevice, nev: int, which: str = "largest", b: int = 16, m: Optional[int] = None,
               keep: Optional[int] = None, tol: float = 1e-10, max_cycles: int = 100, B=None, lc: int = 0,
@@ -965,65 +1057,27 @@ class Handle:
         lo, hi, ref), n_steps (Lanczos steps, the unfiltered solve included); resid is the
         measured residual on A, cycles counts the filtered cycles, n_spmm every SpMM
         (bounds, filter steps and checks).  Needs 2 n b more elements of device memory."""
-        torch = _torch()
         _which(which)
         if filter_degree is not None and not 1 <= int(filter_degree) <= 256:
             raise LanczosError("eigsh: 1 <= filter_degree <= 256")
-        n = A.n
-        tdt = A.val.dtype
-        want = -(-(nev + b) // b)  # the smallest keep with keep * b >= nev + b
-        if m is None:
-            m = min(PANEL_MAX_BLOCKS, max(4, 2 * want))
-        r = min(want, PANEL_MAX_KEEP, m - 1) if keep is None else keep
-        if nev < 1 or r * b < nev:
-            raise LanczosError(f"eigsh: keep * b = {r * b} < nev = {nev}")
-        if r >= m:
-            raise LanczosError(f"eigsh: keep = {r} >= m = {m}")
-        if r > PANEL_MAX_KEEP or m > PANEL_MAX_BLOCKS or r < 1:
-            raise LanczosError(f"eigsh: 1 <= keep <= {PANEL_MAX_KEEP} and m <= {PANEL_MAX_BLOCKS}")
-        per16 = 16 // A.val.element_size()
-        vstride = -(-n * b // per16) * per16
-        kw = dict(dtype=tdt, device=A.val.device)
-        if B is None:
-            B = torch.from_numpy(uniform_B(n, b, dtype=np.float64 if tdt == torch.float64 else np.float32)).to(A.val.device)
-        V = torch.zeros(m * vstride, **kw)
-        W = torch.empty(n, b, **kw)
-        q, al, be = torch.zeros(m * b, **kw), torch.zeros(m, b, b, **kw), torch.zeros(m + 1, b, b, **kw)
+        m, r = _restart_sizes("eigsh", "nev", nev, b, m, keep)
+        d = _Restart(self, A, A.n, b, m, r, lc, passes, A.val)
+        B = d.start_block(B)
         if filter_degree is not None:
-            return self._eigsh_cheb(A, nev, which, b, m, r, tol, max_cycles, B, lc, passes, int(filter_degree), cut,
-                                    V, vstride, W, q, al, be)
-        self.block_lanczos_reorth(A, B, m, lc, q, al, be, V, vstride, W, passes=passes)
-        n_spmm, cycles, history, converged = m, 1, [], False
-        f64 = lambda t: t.cpu().numpy().astype(np.float64)
-        alpha, beta = f64(al), f64(be)
-        T = Assemble_T(m, b, alpha, beta[:m])
+            return self._eigsh_cheb(d, nev, which, tol, max_cycles, B, int(filter_degree), cut)
+        d.first(B)
+        history = []
         while True:
-            theta, S, resid = ritz_pairs_dense(m, b, T, beta[m], m * b, which)
-            scale = float(np.abs(theta).max())
+            theta, S, resid, scale = d.ritz(which)
             theta, S, resid = theta[:nev], S[:, :nev], resid[:nev]
             history.append(float(resid.max()))
             converged = bool(resid.max() <= tol * scale)
-            if converged or cycles >= max_cycles:
+            if converged or d.cycles >= max_cycles:
                 break
-            _, Z, sigma, T = restart_coeffs(m, b, r, T, beta[m], which)
-            self.panel_compress(V, vstride, m, r, torch.from_numpy(Z).to(**kw), n=n)
-            # row lc of Y = P Z_k
-            Zk = Z.transpose(1, 2, 0, 3).reshape(m * b, r * b)
-            q[:r * b] = torch.from_numpy(f64(q) @ Zk).to(**kw)
-            self.block_lanczos_reorth_resume(A, r, m, lc, torch.from_numpy(sigma).to(**kw), q, al, be, V, vstride,
-                                             W, passes=passes)
-            alpha, beta = f64(al), f64(be)
-            restart_fill(r, m, b, alpha, beta, T)
-            n_spmm += m - r
-            cycles += 1
-        # the wanted Ritz vectors, in place, into the first ceil(nev / b) blocks
-        nch = -(-nev // b)
-        Zx = np.zeros((nch, m, b, b))
-        for c in range(nch):
-            w = min(b, nev - c * b)
-            Zx[c, :, :, :w] = S[:, c * b:c * b + w].reshape(m, b, w)
-        self.panel_compress(V, vstride, m, nch, torch.from_numpy(Zx).to(**kw), n=n)
-        return dict(theta=theta, resid=resid, V=V, vstride=vstride, cycles=cycles, n_spmm=n_spmm,
+            d.compress(which)
+            d.resume()
+        d.pack(S, nev)  # the wanted Ritz vectors, in place, into the first ceil(nev / b) blocks
+        return dict(theta=theta, resid=resid, V=d.V, vstride=d.vstride, cycles=d.cycles, n_spmm=d.steps,
                     converged=converged, history=history, scale=scale)
 
     def svds(self, A: CsrDevice, k: int, b: int = 16, m: Optional[int] = None, keep: Optional[int] = None,
@@ -1052,65 +1106,30 @@ class Handle:
         per Lanczos step, two per block of the finish); converged; history (the largest wanted
         est_i / (sigma_max * max(sigma_i, sqrt(eps) sigma_max)) of each cycle); At."""
         torch = _torch()
-        tdt = A.val.dtype
-        want = -(-(k + b) // b)
-        if m is None:
-            m = min(PANEL_MAX_BLOCKS, max(4, 2 * want))
-        r = min(want, PANEL_MAX_KEEP, m - 1) if keep is None else keep
-        if k < 1 or r * b < k:
-            raise LanczosError(f"svds: keep * b = {r * b} < k = {k}")
-        if r >= m:
-            raise LanczosError(f"svds: keep = {r} >= m = {m}")
-        if r > PANEL_MAX_KEEP or m > PANEL_MAX_BLOCKS or r < 1:
-            raise LanczosError(f"svds: 1 <= keep <= {PANEL_MAX_KEEP} and m <= {PANEL_MAX_BLOCKS}")
+        m, r = _restart_sizes("svds", "k", k, b, m, keep)
         At = A.transpose(self)
         P, Pt = (A, At) if A.n_cols <= A.n else (At, A)
         n, p = P.n_cols, P.n
-        per16 = 16 // A.val.element_size()
-        xstride, ystride = -(-n * b // per16) * per16, -(-p * b // per16) * per16
-        kw = dict(dtype=tdt, device=A.val.device)
-        npdt = np.float64 if tdt == torch.float64 else np.float32
-        eps = float(np.finfo(npdt).eps)
-        if B is None:
-            B = torch.from_numpy(uniform_B(n, b, dtype=npdt)).to(A.val.device)
-        X = torch.zeros(m * xstride, **kw)
-        W = torch.empty(n, b, **kw)
-        work = torch.empty(p * b, **kw)
-        normal = (P, Pt, work)
-        q, al, be = torch.zeros(m * b, **kw), torch.zeros(m, b, b, **kw), torch.zeros(m + 1, b, b, **kw)
-        self.block_lanczos_reorth(None, B, m, lc, q, al, be, X, xstride, W, passes=passes, normal=normal)
-        n_spmm, cycles, history, converged = 2 * m, 1, [], False
-        f64 = lambda t: t.cpu().numpy().astype(np.float64)
-        alpha, beta = f64(al), f64(be)
-        T = Assemble_T(m, b, alpha, beta[:m])
+        work = torch.empty(p * b, dtype=A.val.dtype, device=A.val.device)
+        d = _Restart(self, None, n, b, m, r, lc, passes, A.val, normal=(P, Pt, work))
+        kw, W, xstride, ystride = d.kw, d.W, d.vstride, _panel_stride(p, b, A.val)
+        eps = float(np.finfo(d.npdt).eps)
+        d.first(d.start_block(B))
+        history = []
         while True:
-            theta, S, est = ritz_pairs_dense(m, b, T, beta[m], m * b, "largest")
-            smax = float(np.sqrt(np.abs(theta).max()))
+            theta, S, est, scale = d.ritz("largest")
+            smax = float(np.sqrt(scale))
             theta, S, est = theta[:k], S[:, :k], est[:k]
             s = np.sqrt(np.maximum(theta, 0.0))
             ratio = est / (smax * np.maximum(s, np.sqrt(eps) * smax))
             history.append(float(ratio.max()))
             converged = bool(ratio.max() <= tol)
-            if converged or cycles >= max_cycles:
+            if converged or d.cycles >= max_cycles:
                 break
-            _, Z, sigma, T = restart_coeffs(m, b, r, T, beta[m], "largest")
-            self.panel_compress(X, xstride, m, r, torch.from_numpy(Z).to(**kw), n=n)
-            Zk = Z.transpose(1, 2, 0, 3).reshape(m * b, r * b)
-            q[:r * b] = torch.from_numpy(f64(q) @ Zk).to(**kw)
-            self.block_lanczos_reorth_resume(None, r, m, lc, torch.from_numpy(sigma).to(**kw), q, al, be, X, xstride,
-                                             W, passes=passes, normal=normal)
-            alpha, beta = f64(al), f64(be)
-            restart_fill(r, m, b, alpha, beta, T)
-            n_spmm += 2 * (m - r)
-            cycles += 1
-        # the wanted Ritz vectors of G, in place, into the first ceil(k / b) blocks
-        nch = -(-k // b)
-        Zx = np.zeros((nch, m, b, b))
-        for c in range(nch):
-            w = min(b, k - c * b)
-            Zx[c, :, :, :w] = S[:, c * b:c * b + w].reshape(m, b, w)
-        self.panel_compress(X, xstride, m, nch, torch.from_numpy(Zx).to(**kw), n=n)
-        X = X[:nch * xstride]
+            d.compress("largest")
+            d.resume()
+        nch = d.pack(S, k)  # the wanted Ritz vectors of G, in place, into the first ceil(k / b) blocks
+        X = d.V[:nch * xstride]
         # the other side: y = P x / ||P x||, and the measured residuals ||Pt y - sigma x||
         Y = torch.zeros(nch * ystride, **kw)
         Pw = work.view(p, b)
@@ -1123,7 +1142,7 @@ class Handle:
             Yc = Y[c * ystride:c * ystride + p * b].view(p, b)
             self.spmm(P, Xc, Pw)
             self.mm_tt(Pw, Gm)
-            nrm = np.sqrt(np.maximum(np.diag(f64(Gm)), 0.0))
+            nrm = np.sqrt(np.maximum(np.diag(_f64(Gm)), 0.0))
             inv = np.divide(1.0, nrm, out=np.zeros_like(nrm), where=nrm > 0)
             Dm.copy_(torch.from_numpy(np.diag(inv)).to(**kw))
             self.mm_ts(0.0, 1.0, Pw, Dm, Yc)
@@ -1131,36 +1150,24 @@ class Handle:
             Dm.copy_(torch.from_numpy(np.diag(sp[c * b:(c + 1) * b])).to(**kw))
             self.mm_ts(1.0, -1.0, Xc, Dm, W)
             self.mm_tt(W, Gm)
-            resid[c * b:(c + 1) * b] = np.sqrt(np.maximum(np.diag(f64(Gm)), 0.0))
-            n_spmm += 2
+            resid[c * b:(c + 1) * b] = np.sqrt(np.maximum(np.diag(_f64(Gm)), 0.0))
         U, ustride, Vv, vstride = (Y, ystride, X, xstride) if P is A else (X, xstride, Y, ystride)
-        return dict(s=s, U=U, ustride=ustride, V=Vv, vstride=vstride, resid=resid[:k], est=est, cycles=cycles,
-                    n_spmm=n_spmm, converged=converged, history=history, At=At)
+        return dict(s=s, U=U, ustride=ustride, V=Vv, vstride=vstride, resid=resid[:k], est=est, cycles=d.cycles,
+                    n_spmm=2 * (d.steps + nch), converged=converged, history=history, At=At)
 
-    def _eigsh_cheb(self, A, nev, which, b, m, r, tol, max_cycles, B, lc, passes, degree, cut, V, vstride, W, q, al,
-                    be):
-        """eigsh(filter_degree=degree) on the buffers eigsh allocated (its docstring)."""
+    def _eigsh_cheb(self, d: _Restart, nev, which, tol, max_cycles, B, degree, cut):
+        """eigsh(filter_degree=degree) on the driver eigsh set up (its docstring)."""
         torch = _torch()
-        n = A.n
-        kw = dict(dtype=A.val.dtype, device=A.val.device)
-        f64 = lambda t: t.cpu().numpy().astype(np.float64)
+        A, V, vstride, kw, n, b, m, r = d.A, d.V, d.vstride, d.kw, d.n, d.b, d.m, d.r
         nch = -(-nev // b)
         # 1. bounds: one unfiltered solve; its Ritz values place the filter
-        self.block_lanczos_reorth(A, B, m, lc, q, al, be, V, vstride, W, passes=passes)
-        n_steps = n_spmm = m
-        alpha, beta = f64(al), f64(be)
-        T = Assemble_T(m, b, alpha, beta[:m])
-        theta, S, resid = ritz_pairs_dense(m, b, T, beta[m], m * b, which)
-        scale = float(np.abs(theta).max())
+        d.first(B)
+        theta, S, resid, scale = d.ritz(which)
         if resid[:nev].max() <= tol * scale:  # finished as the unfiltered eigsh finishes
-            Zx = np.zeros((nch, m, b, b))
-            for c in range(nch):
-                w = min(b, nev - c * b)
-                Zx[c, :, :, :w] = S[:, c * b:c * b + w].reshape(m, b, w)
-            self.panel_compress(V, vstride, m, nch, torch.from_numpy(Zx).to(**kw), n=n)
-            return dict(theta=theta[:nev], resid=resid[:nev], V=V, vstride=vstride, cycles=0, n_spmm=n_spmm,
+            d.pack(S, nev)
+            return dict(theta=theta[:nev], resid=resid[:nev], V=V, vstride=vstride, cycles=0, n_spmm=d.steps,
                         converged=True, history=[float(resid[:nev].max())], scale=scale, cols=np.arange(nev),
-                        filter=None, n_steps=n_steps)
+                        filter=None, n_steps=d.steps)
         # 2. the filter, fixed for the whole solve (the Lanczos relation across restarts needs
         # one operator).  The far end is Gershgorin's: a guaranteed enclosure, where a Lanczos
         # estimate that falls short would let p blow up.  theta_i >= lambda_i (Cauchy
@@ -1191,7 +1198,7 @@ class Handle:
                 self.mm_tt2(U, Yi, Th)
                 self.mm_ts(1.0, -1.0, Yi, Th, U)
                 self.mm_tt(U, G)
-                Thh, Gh = f64(Th), f64(G)
+                Thh, Gh = _f64(Th), _f64(G)
                 lm, C = np.linalg.eigh(0.5 * (Thh + Thh.T))
                 lam.append(lm)
                 res.append(np.sqrt(np.maximum(np.einsum("ij,ik,kj->j", C, 0.5 * (Gh + Gh.T), C), 0.0)))
@@ -1199,40 +1206,29 @@ class Handle:
             return np.concatenate(lam), np.concatenate(res), Cs
 
         # 3. thick restart on p(A) from the same B: eigsh's loop, the largest end of T
-        self.block_lanczos_reorth(A, B, m, lc, q, al, be, V, vstride, W, passes=passes, filt=filt, work=work)
-        n_steps += m
-        n_spmm += m * degree
-        cycles, history = 1, []
-        alpha, beta = f64(al), f64(be)
-        T = Assemble_T(m, b, alpha, beta[:m])
+        d.op = dict(filt=filt, work=work)
+        d.first(B)
+        history = []
         while True:
-            _, Z, sigma, T = restart_coeffs(m, b, r, T, beta[m], "largest")
-            self.panel_compress(V, vstride, m, r, torch.from_numpy(Z).to(**kw), n=n)
+            d.compress("largest")
             # 4. the true residuals on A of the first nch kept blocks
             lam, res, Cs = check()
-            n_spmm += nch
             # 5. the nev candidates at the wanted end
             sel = np.argsort(lam if which == "smallest" else -lam, kind="stable")[:nev]
             history.append(float(res[sel].max()))
             converged = bool(res[sel].max() <= tol * scale)
-            if converged or cycles >= max_cycles:
+            if converged or d.cycles >= max_cycles:
                 break
-            Zk = Z.transpose(1, 2, 0, 3).reshape(m * b, r * b)
-            q[:r * b] = torch.from_numpy(f64(q) @ Zk).to(**kw)
-            self.block_lanczos_reorth_resume(A, r, m, lc, torch.from_numpy(sigma).to(**kw), q, al, be, V, vstride, W,
-                                             passes=passes, filt=filt, work=work)
-            alpha, beta = f64(al), f64(be)
-            restart_fill(r, m, b, alpha, beta, T)
-            n_steps += m - r
-            n_spmm += (m - r) * degree
-            cycles += 1
+            d.resume()
         # block i <- Y_i C_i, in place: one compress over the nch blocks with a block-diagonal Z
         Zr = np.zeros((nch, nch, b, b))
         for i in range(nch):
             Zr[i, i] = Cs[i]
         self.panel_compress(V, vstride, nch, nch, torch.from_numpy(Zr).to(**kw), n=n)
-        return dict(theta=lam[sel], resid=res[sel], V=V, vstride=vstride, cycles=cycles, n_spmm=n_spmm,
-                    converged=converged, history=history, scale=scale, cols=sel, filter=filt, n_steps=n_steps)
+        # SpMMs: the unfiltered solve's m, degree per filtered step, nch per check (one a cycle)
+        return dict(theta=lam[sel], resid=res[sel], V=V, vstride=vstride, cycles=d.cycles,
+                    n_spmm=m + (d.steps - m) * degree + nch * d.cycles, converged=converged, history=history,
+                    scale=scale, cols=sel, filter=filt, n_steps=d.steps)
 
     def set_final_state(self, on: bool) -> None:
         """True (default): block_lanczos_blas leaves Q0 = Q1 = Q_{m-1} and W = the
