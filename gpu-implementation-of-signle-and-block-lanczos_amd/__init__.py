@@ -39,7 +39,7 @@ LZ_ROW_MAJOR, LZ_COL_MAJOR = 0, 1
 # lz_debug_last_kernel ids (include/lz_hip.h): SpMM kernels, their flags, dense kernels
 (LZ_K_SEG768, LZ_K_SEG1536, LZ_K_SEG1024, LZ_K_FNZ, LZ_K_BUF, LZ_K_LDS, LZ_K_ANY_B, LZ_K_CM_DIRECT,
  LZ_K_SPMV) = range(1, 10)
-LZ_K_WIN, LZ_K_YCM, LZ_K_EPI, LZ_K_AX3 = 0x100, 0x200, 0x400, 0x800
+LZ_K_WIN, LZ_K_YCM, LZ_K_EPI, LZ_K_AX3, LZ_K_DOT = 0x100, 0x200, 0x400, 0x800, 0x1000
 LZ_K_GRAM16, LZ_K_GRAM32F, LZ_K_GRAM_GEN, LZ_K_TSMM16, LZ_K_TSMM32F, LZ_K_TSMM_GEN = range(1, 7)
 LZ_K_PGRAM16, LZ_K_PGRAM_GEN, LZ_K_PAPPLY16, LZ_K_PAPPLY_GEN = range(7, 11)
 # blocks per group of the panel Gram kernels (W is re-read once per group): b = 16 fp64 MFMA, generic
@@ -106,6 +106,11 @@ HIP_SYMBOLS = [
                                    _c_dbl, _c_dbl, _c_vp, _c_vp]),
     ("lz_cheb_apply", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp,
                                _c_vp]),
+    ("lz_col_dots", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
+    ("lz_csr_spmm_axpby_dots", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp,
+                                        _c_dbl, _c_dbl, _c_vp, _c_vp, _c_vp]),
+    ("lz_cheb_moments", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_dbl, _c_int,
+                                 _c_vp, _c_vp, _c_vp]),
     ("lz_block_lanczos_reorth_cheb", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int,
                                               _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int,
                                               _c_vp, _c_vp]),
@@ -172,6 +177,10 @@ HOST_SYMBOLS = [
     ("lzh_restart_coeffs", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_restart_fill", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     ("lzh_gershgorin", _c_int, [_c_i64, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lzh_kpm_moments", _c_int, [_c_int, _c_int, _c_vp, _c_vp]),
+    ("lzh_jackson", _c_int, [_c_int, _c_vp]),
+    ("lzh_kpm_count", _c_int, [_c_int, _c_vp, _c_vp, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_vp]),
+    ("lzh_kpm_density", _c_int, [_c_int, _c_vp, _c_vp, _c_dbl, _c_dbl, _c_int, _c_vp, _c_vp]),
     ("lzh_block_solution", _c_int, [_c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_partition_rows", _c_int, [_c_i64, _c_vp, _c_int, _c_vp]),
     ("lzh_remap_cols_padded", _c_int, [_c_i64, _c_vp, _c_int, _c_vp, _c_i64, _c_vp]),
@@ -334,6 +343,86 @@ def gershgorin(A: CsrHost):
                                  _p(np.ascontiguousarray(host(A.col), np.int32)), _p(val), _p(out)):
         raise LanczosError("lzh_gershgorin failed (n >= 1)")
     return float(out[0]), float(out[1])
+
+
+def kpm_moments(dots: np.ndarray) -> np.ndarray:
+    """(K+1, 2, b) raw dots of Handle.cheb_moments -> (2K+1, b) Chebyshev moments, column c those
+    of probe c (lzh_kpm_moments: mu_2k = 2 <t_k,t_k> - mu_0, mu_2k+1 = 2 <t_k+1,t_k> - mu_1)."""
+    dots = np.ascontiguousarray(dots, np.float64)
+    if dots.ndim != 3 or dots.shape[1] != 2:
+        raise LanczosError("kpm_moments: dots is (K+1, 2, b)")
+    K, b = dots.shape[0] - 1, dots.shape[2]
+    mu = np.empty((2 * K + 1, b))
+    if host_lib().lzh_kpm_moments(K, b, _p(dots), _p(mu)):
+        raise LanczosError("lzh_kpm_moments failed (K, b >= 1)")
+    return mu
+
+
+def jackson(M: int) -> np.ndarray:
+    """The Jackson damping factors g_0 .. g_{M-1} of a series of M moments (lzh_jackson)."""
+    g = np.empty(max(int(M), 0))
+    if host_lib().lzh_jackson(int(M), _p(g)):
+        raise LanczosError("lzh_jackson failed (M >= 1)")
+    return g
+
+
+def _damping(damping, M: int):
+    if damping not in ("jackson", None):
+        raise LanczosError('damping: "jackson" or None')
+    return jackson(M) if damping == "jackson" else None
+
+
+def kpm_count(mu: np.ndarray, lo: float, hi: float, a: float, b: float, damping="jackson") -> float:
+    """The eigenvalue count of [a, b] from the moments mu[0 .. M) of one probe, or of their mean
+    (lzh_kpm_count), on the enclosure [lo, hi] the moments were taken with."""
+    mu = np.ascontiguousarray(mu, np.float64)
+    g, out = _damping(damping, mu.size), np.empty(1)
+    if mu.ndim != 1 or host_lib().lzh_kpm_count(mu.size, _p(mu), None if g is None else _p(g), lo, hi, a, b, _p(out)):
+        raise LanczosError("lzh_kpm_count failed (M >= 1, lo < hi finite, a <= b)")
+    return float(out[0])
+
+
+def kpm_density(mu: np.ndarray, lo: float, hi: float, x, damping="jackson") -> np.ndarray:
+    """The density of states at the points x from the moments mu[0 .. M) (lzh_kpm_density);
+    0 outside (lo, hi)."""
+    mu = np.ascontiguousarray(mu, np.float64)
+    x = np.ascontiguousarray(np.atleast_1d(x), np.float64)
+    g, rho = _damping(damping, mu.size), np.empty(x.size)
+    if mu.ndim != 1 or host_lib().lzh_kpm_density(mu.size, _p(mu), None if g is None else _p(g), lo, hi, x.size, _p(x),
+                                                  _p(rho)):
+        raise LanczosError("lzh_kpm_density failed (M >= 1, lo < hi finite)")
+    return rho.reshape(x.shape)
+
+
+class KpmMoments:
+    """Chebyshev moments of a symmetric operator from random probes (Handle.spectral_moments):
+    n, the enclosure [lo, hi], mu ((2K+1) x probes, column c the moments x_c^T T_k(Ah) x_c of
+    probe c) and n_spmm.  Host only: one set of moments serves any number of intervals."""
+
+    def __init__(self, n: int, lo: float, hi: float, mu: np.ndarray, n_spmm: int):
+        self.n, self.lo, self.hi, self.n_spmm = int(n), float(lo), float(hi), int(n_spmm)
+        self.mu = np.ascontiguousarray(mu, np.float64)
+
+    @property
+    def probes(self) -> int:
+        return self.mu.shape[1]
+
+    def _mean(self, per_probe: np.ndarray):
+        """(mean, sample standard deviation / sqrt(probes)) over the probes (axis 0)."""
+        p = per_probe.shape[0]
+        sd = per_probe.std(axis=0, ddof=1) / np.sqrt(p) if p > 1 else np.full(per_probe.shape[1:], np.nan)
+        return per_probe.mean(axis=0), sd
+
+    def count(self, a: float, b: float, damping="jackson"):
+        """(estimate, stderr) of the number of eigenvalues in [a, b]: the mean of the per-probe
+        counts and their sample standard deviation / sqrt(probes).  The resolution is about
+        pi (hi - lo) / (2 M) for M moments."""
+        est, sd = self._mean(np.array([kpm_count(col, self.lo, self.hi, a, b, damping) for col in self.mu.T]))
+        return float(est), float(sd)
+
+    def density(self, x, damping="jackson"):
+        """(rho, stderr) at the points x: eigenvalues per unit length, integrating to n."""
+        return self._mean(np.stack([kpm_density(col, self.lo, self.hi, x, damping) for col in self.mu.T]))
 
 
 class ChebFilter(ctypes.Structure):
@@ -800,6 +889,107 @@ class Handle:
         _check(self.L.lz_csr_spmm_axpby(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
                                         a, _ptr(X), c, d, _ptr(Z), _ptr(Y)), "lz_csr_spmm_axpby")
         return Y
+
+    def _dots(self, what: str, dots, rows: int, b: int, like):
+        """The (rows, 2, b) fp64 device tensor the dots land in (allocated when None)."""
+        torch = _torch()
+        if dots is None:
+            return torch.empty(rows, 2, b, dtype=torch.float64, device=like.device)
+        if dots.dtype != torch.float64 or not dots.is_contiguous() or dots.numel() != rows * 2 * b:
+            raise LanczosError(f"{what}: dots is a contiguous fp64 tensor of {rows} x 2 x b elements")
+        return dots
+
+    def col_dots(self, Y, X, dots=None):
+        """dots[0] = the column sums of Y * Y, dots[1] = those of Y * X (lz_col_dots): Y, X (n, b)
+        contiguous, of one dtype, b <= 64; fp64 sums in a fixed order, on the device.  Y may be X."""
+        n, b = Y.shape
+        if tuple(X.shape) != (n, b) or X.dtype != Y.dtype or not (X.is_contiguous() and Y.is_contiguous()):
+            raise LanczosError("col_dots: Y and X (n, b) contiguous (ld = b), of one dtype")
+        dots = self._dots("col_dots", dots, 1, b, Y)
+        _check(self.L.lz_col_dots(self.ptr, n, b, _dt(Y), _ptr(Y), _ptr(X), _ptr(dots)), "lz_col_dots")
+        return dots.view(2, b)
+
+    def spmm_axpby_dots(self, A: CsrDevice, a: float, X, c: float, d: float, Z, Y, dots=None):
+        """spmm_axpby, and the column dots of the stored Y with itself and with X as col_dots
+        returns them (lz_csr_spmm_axpby_dots); returns (Y, dots)."""
+        n, b = self._blocks("spmm_axpby_dots", A, X, Y, Z)
+        dots = self._dots("spmm_axpby_dots", dots, 1, b, Y)
+        _check(self.L.lz_csr_spmm_axpby_dots(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                             a, _ptr(X), c, d, _ptr(Z), _ptr(Y), _ptr(dots)), "lz_csr_spmm_axpby_dots")
+        return Y, dots.view(2, b)
+
+    def cheb_moments(self, A: CsrDevice, X0, K: int, lo: float, hi: float, work=None, dots=None):
+        """The raw dots of K Chebyshev steps from X0 on (A - c0) / e, [lo, hi] = [c0 - e, c0 + e]
+        enclosing A's spectrum (lz_cheb_moments): a (K+1, 2, b) fp64 device tensor, row k =
+        (<t_k,t_k>, <t_k,t_{k-1}>), row 0 = (<t_0,t_0>, 0); kpm_moments turns it into 2K+1
+        moments.  work: flat, 3*n*b elements (allocated when None); X0 is only read."""
+        torch = _torch()
+        n, b = self._blocks("cheb_moments", A, X0)
+        if work is None:
+            work = torch.empty(3 * n * b, dtype=X0.dtype, device=X0.device)
+        if work.dim() != 1 or not work.is_contiguous() or work.numel() < 3 * n * b or work.dtype != X0.dtype:
+            raise LanczosError("cheb_moments: work is a flat contiguous tensor of 3*n*b elements of X0's dtype")
+        dots = self._dots("cheb_moments", dots, max(int(K), 0) + 1, b, X0)
+        _check(self.L.lz_cheb_moments(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                      lo, hi, K, _ptr(X0), _ptr(work), _ptr(dots)), "lz_cheb_moments")
+        return dots.view(-1, 2, b)
+
+    def spectral_moments(self, A: CsrDevice, n_moments: int = 257, probes: Optional[int] = None,
+                         b: Optional[int] = None, bounds=None, pad: float = 0.01, seed: int = 0,
+                         X0=None) -> KpmMoments:
+        """Chebyshev moments of the symmetric operator A by the kernel polynomial method: K =
+        ceil((n_moments - 1) / 2) three-term SpMMs per block of b random +-1 probe columns give
+        2K+1 moments per probe; KpmMoments.count / .density read eigenvalue counts and the
+        density of states off them, for any number of intervals.
+        b: the probe block (default the 128-byte row of A's dtype: 16 fp64, 32 fp32); probes: a
+        multiple of b (default b).  bounds: an enclosure (lo, hi) of the spectrum, default
+        gershgorin(A) (one copy of the CSR arrays to the host); each end is moved out by pad x
+        the width.  An eigenvalue outside the widened bounds makes the recurrence diverge:
+        non-finite dots raise LanczosError.  The probes are drawn on the device from
+        torch.Generator(seed), block by block, unless X0 (n x probes) is given.  One
+        cheb_moments call and one copy of its dots to the host per block."""
+        torch = _torch()
+        n = A.n
+        if b is None:
+            b = 16 if A.dtype == LZ_F64 else 32
+        if X0 is not None:
+            probes = X0.shape[1]
+        elif probes is None:
+            probes = b
+        if n_moments < 2 or b < 1 or probes < b or probes % b:
+            raise LanczosError("spectral_moments: n_moments >= 2, probes a positive multiple of b")
+        if X0 is not None and (X0.shape[0] != n or X0.dtype != A.val.dtype):
+            raise LanczosError("spectral_moments: X0 is n x probes, of A's dtype")
+        K = -(-(n_moments - 1) // 2)
+        lo, hi = gershgorin(A) if bounds is None else (float(bounds[0]), float(bounds[1]))
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi and pad >= 0):
+            raise LanczosError(f"spectral_moments: bounds ({lo}, {hi}) must be finite with lo < hi, pad >= 0")
+        lo, hi = lo - pad * (hi - lo), hi + pad * (hi - lo)
+        dev, dt = A.val.device, A.val.dtype
+        gen = None
+        if X0 is None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(seed)
+        work = torch.empty(3 * n * b, dtype=dt, device=dev)
+        dots = torch.empty(K + 1, 2, b, dtype=torch.float64, device=dev)
+        mu = np.empty((2 * K + 1, probes))
+        for j in range(probes // b):
+            if X0 is None:
+                Xb = (torch.randint(0, 2, (n, b), generator=gen, device=dev, dtype=torch.int8) * 2 - 1).to(dt)
+            else:
+                Xb = X0[:, j * b:(j + 1) * b].contiguous()
+            raw = _f64(self.cheb_moments(A, Xb, K, lo, hi, work=work, dots=dots))
+            if not np.isfinite(raw).all():
+                raise LanczosError(f"spectral_moments: non-finite moments -- the bounds ({lo}, {hi}) do not enclose "
+                                   "the operator's spectrum")
+            mu[:, j * b:(j + 1) * b] = kpm_moments(raw)
+        return KpmMoments(n, lo, hi, mu, K * (probes // b))
+
+    def eigcount(self, A: CsrDevice, a: float, b: float, /, **kw):
+        """(estimate, stderr) of the number of eigenvalues of A in [a, b]:
+        spectral_moments(A, **kw).count(a, b).  a and b are positional only, so that kw may
+        carry spectral_moments' own b (the probe block)."""
+        return self.spectral_moments(A, **kw).count(a, b)
 
     def _work(self, what: str, work, n: int, b: int, like):
         if work.dim() != 1 or not work.is_contiguous() or work.numel() < 2 * n * b or work.dtype != like.dtype:

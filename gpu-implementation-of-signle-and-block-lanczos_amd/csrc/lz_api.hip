@@ -260,6 +260,14 @@ static bool ax3_fused()
     return !(e && e[0] == '0');
 }
 
+// LZ_AX3DOT=0 (read per call, measurement): lz_csr_spmm_axpby_dots as the fused three-term
+// store and then the streaming k_col_dots, where its store would carry the dots too
+static bool ax3dot_fused()
+{
+    const char *e = getenv("LZ_AX3DOT");
+    return !(e && e[0] == '0');
+}
+
 static int cheb_args(const lz_cheb *f)
 {
     LZ_ARG_CHECK(f->degree >= 1 && f->degree <= 256, "Chebyshev filter: 1 <= degree <= 256");
@@ -1565,6 +1573,7 @@ int lz_finalize(lz_handle *h)
     (void)hipFree(h->pairs);
     (void)hipFree(h->longq);
     (void)hipFree(h->cm_buf);
+    (void)hipFree(h->dots_ws);
     (void)hipFree(h->ybuf);
     (void)hipFree(h->coef);
     (void)hipFree(h->tr_ws);
@@ -1642,6 +1651,7 @@ int lz_debug_poison_lds(lz_handle *h, uint32_t pattern)
     LZ_HIP_TRY(hipMemsetAsync(h->partials, byte, h->partials_cap, h->stream));
     LZ_HIP_TRY(hipMemsetAsync(h->partials2, byte, sizeof(double) * kPartials2Doubles, h->stream));
     LZ_HIP_TRY(hipMemsetAsync(h->scratch, byte, sizeof(double) * kScratchDoubles, h->stream));
+    if (h->dots_ws) LZ_HIP_TRY(hipMemsetAsync(h->dots_ws, byte, h->dots_cap, h->stream));
     return LZ_OK;
 }
 
@@ -2022,6 +2032,57 @@ int lz_cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return cheb_apply<T>(h, n, nnz, rp, col, (const T *)val, b, *f, (const T *)X, (T *)Y, (T *)work);
+    });
+}
+
+int lz_col_dots(lz_handle *h, int64_t n, int b, lz_dtype dtype, const void *Y, const void *X, double *dots)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= kMaxB, "n >= 1, b in [1,64]");
+    LZ_ARG_CHECK(Y && X && dots, "Y/X/dots NULL");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return col_dots<T>(h, n, b, (const T *)Y, (const T *)X, dots);
+    });
+}
+
+int lz_csr_spmm_axpby_dots(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                           lz_dtype dtype, int b, double a, const void *X, double c, double d, const void *Z, void *Y,
+                           double *dots)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= kMaxB, "n >= 1, b in [1,64]");
+    LZ_ARG_CHECK(X && Y && (Z || d == 0.0), "X/Y NULL, or Z NULL with d != 0");
+    LZ_ARG_CHECK(dots != nullptr, "dots is NULL");
+    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
+    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && (d == 0.0 || (blocks_apart(Z, nb, Y, nb, es) && Z != X)),
+                 "X, Z and Y must be pairwise distinct (no in-place form)");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return spmm_axpby_dots<T>(h, n, nnz, rp, col, (const T *)val, b, (T)a, (const T *)X, (T)c, (T)d, (const T *)Z,
+                                  (T *)Y, dots, ax3_fused(), ax3dot_fused());
+    });
+}
+
+int lz_cheb_moments(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                    lz_dtype dtype, int b, double lo, double hi, int K, const void *X0, void *work, double *dots)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= kMaxB, "n >= 1, b in [1,64]");
+    LZ_ARG_CHECK(X0 && work && dots, "X0/work/dots NULL");
+    LZ_ARG_CHECK(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "Chebyshev moments: lo < hi, finite");
+    LZ_ARG_CHECK(K >= 1 && K <= 65536, "Chebyshev moments: 1 <= K <= 65536");
+    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
+    LZ_ARG_CHECK(blocks_apart(work, 3 * nb, X0, nb, es), "X0 and work must be distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return cheb_moments<T>(h, n, nnz, rp, col, (const T *)val, b, lo, hi, K, (const T *)X0, (T *)work, dots,
+                               ax3_fused(), ax3dot_fused());
     });
 }
 

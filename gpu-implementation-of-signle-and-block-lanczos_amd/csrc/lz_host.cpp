@@ -650,6 +650,72 @@ int lzh_gershgorin(int64_t n, const int64_t *row_ptr, const int32_t *col, const 
     return 0;
 }
 
+// ---- kernel polynomial method (lz_cheb_moments' raw dots -> moments -> counts, density)
+int lzh_kpm_moments(int K, int b, const double *dots, double *mu)
+{
+    if (K < 1 || b < 1 || !dots || !mu) return -1;
+    const double *m0 = dots, *m1 = dots + (size_t)(2 + 1) * b;  // <t0, t0>, <t1, t0>
+    for (int c = 0; c < b; ++c) {
+        mu[c] = m0[c];
+        mu[b + c] = m1[c];
+    }
+    for (int k = 1; k <= K; ++k) {
+        const double *sq = dots + (size_t)2 * k * b, *cr = sq + b;  // <t_k, t_k>, <t_k, t_{k-1}>
+        for (int c = 0; c < b; ++c) {
+            if (k >= 2) mu[(size_t)(2 * k - 1) * b + c] = 2.0 * cr[c] - m1[c];
+            mu[(size_t)(2 * k) * b + c] = 2.0 * sq[c] - m0[c];
+        }
+    }
+    return 0;
+}
+
+int lzh_jackson(int M, double *g)
+{
+    if (M < 1 || !g) return -1;
+    const double q = M_PI / (M + 1), cot = std::cos(q) / std::sin(q);
+    for (int k = 0; k < M; ++k) g[k] = ((M + 1 - k) * std::cos(q * k) + std::sin(q * k) * cot) / (M + 1);
+    return 0;
+}
+
+static bool kpm_bounds_ok(double lo, double hi) { return std::isfinite(lo) && std::isfinite(hi) && lo < hi; }
+
+static double kpm_theta(double x, double c0, double e)
+{
+    const double t = (x - c0) / e;
+    return std::acos(t < -1.0 ? -1.0 : t > 1.0 ? 1.0 : t);
+}
+
+int lzh_kpm_count(int M, const double *mu, const double *g, double lo, double hi, double a, double b, double *count)
+{
+    if (M < 1 || !mu || !count || !kpm_bounds_ok(lo, hi) || !(a <= b)) return -1;
+    const double e = 0.5 * (hi - lo), c0 = 0.5 * (hi + lo);
+    const double ta = kpm_theta(a, c0, e), tb = kpm_theta(b, c0, e);
+    double s = (g ? g[0] : 1.0) * (ta - tb) / M_PI * mu[0];
+    for (int k = 1; k < M; ++k)
+        s += (g ? g[k] : 1.0) * 2.0 * (std::sin(k * ta) - std::sin(k * tb)) / (k * M_PI) * mu[k];
+    *count = s;
+    return 0;
+}
+
+int lzh_kpm_density(int M, const double *mu, const double *g, double lo, double hi, int npts, const double *x,
+                    double *rho)
+{
+    if (M < 1 || !mu || !kpm_bounds_ok(lo, hi) || npts < 0 || (npts > 0 && (!x || !rho))) return -1;
+    const double e = 0.5 * (hi - lo), c0 = 0.5 * (hi + lo);
+    for (int p = 0; p < npts; ++p) {
+        const double xh = (x[p] - c0) / e;
+        if (!(xh > -1.0 && xh < 1.0)) {
+            rho[p] = 0.0;
+            continue;
+        }
+        const double th = std::acos(xh);
+        double s = (g ? g[0] : 1.0) * mu[0];
+        for (int k = 1; k < M; ++k) s += 2.0 * (g ? g[k] : 1.0) * mu[k] * std::cos(k * th);
+        rho[p] = s / (M_PI * e * std::sqrt(1.0 - xh * xh));
+    }
+    return 0;
+}
+
 int lzh_restart_fill(int r, int m, int b, const double *alpha, const double *beta, double *T_next)
 {
     const int k = m * b;

@@ -16,9 +16,31 @@ int spmm_rm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32
 template <typename T>
 int spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
                T a, const T *X, T c, T d, const T *Z, T *Y, bool fused = true);
+// spmm_axpby, and dots[0 .. b) = sum_i Y[i][c]^2, dots[b .. 2b) = sum_i Y[i][c] X[i][c] of the
+// stored Y (device, fp64, fixed summation order).  fused && fused_dot at spmm_axpby's fused
+// shapes: the dots leave k_spmm_seg's store too (last_kernel | LZ_K_AX3 | LZ_K_DOT), a slab
+// per tile in h->dots_ws; else spmm_axpby(fused), then col_dots.  n >= 1.
+template <typename T>
+int spmm_axpby_dots(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                    T a, const T *X, T c, T d, const T *Z, T *Y, double *dots, bool fused = true,
+                    bool fused_dot = true);
 template <typename T>
 int spmm_cm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
             const T *X, int64_t ldx, int64_t nx, T *Y, int64_t ldy);  // nx: rows of X
+
+// ---- column dots and Chebyshev moments (lz_kpm.hip)
+// h->dots_ws for every dots call on n x b blocks (may synchronise; afterwards those calls never do)
+int dots_reserve(lz_handle *h, int64_t n, int b);
+// the streaming form: Y and X (n x b, ld = b, any b <= 64; Y == X allowed) read once, slabs, fold
+// (zero_cross: dots[b .. 2b) = 0)
+template <typename T>
+int col_dots(lz_handle *h, int64_t n, int b, const T *Y, const T *X, double *dots, bool zero_cross = false);
+// P slabs of 2 b doubles at h->dots_ws -> dots, every sum in a fixed order, no host synchronisation
+int dots_fold(lz_handle *h, int64_t P, int b, double *dots, bool zero_cross = false);
+// lz_cheb_moments (include/lz_hip.h)
+template <typename T>
+int cheb_moments(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                 double lo, double hi, int K, const T *X0, T *work, double *dots, bool fused, bool fused_dot);
 // column-major rows x b (ld >= rows) -> row-major rows x b (ld = b)
 template <typename T>
 int to_row_major(lz_handle *h, int64_t rows, int b, const T *src, int64_t ld, T *dst);

@@ -390,13 +390,16 @@ __device__ __forceinline__ Vec<T, VEC> epi_piece(Vec<T, VEC> y, const T *__restr
 // of a row, a s + c x + d z with x, z the lane's own 16-B pieces of X[row] and
 // Z[row] (zrow == nullptr: d == 0, Z is never read).  X[row] is the piece the
 // diagonal entry gathered, so it usually comes from cache; Z is streamed once:
-// a non-temporal load, as epi_piece loads W.
+// a non-temporal load, as epi_piece loads W.  xo (DOT): the x piece, for the
+// column dots.
 template <typename T, int VEC>
 __device__ __forceinline__ Vec<T, VEC> ax3_piece(Vec<T, VEC> s, const T *__restrict__ xrow,
-                                                 const T *__restrict__ zrow, T a, T c, T d)
+                                                 const T *__restrict__ zrow, T a, T c, T d,
+                                                 Vec<T, VEC> *xo = nullptr)
 {
     static_assert(sizeof(T) * VEC == 16, "128-B rows: 16-B pieces");
     const Vec<T, VEC> x = ldv<T, VEC>(xrow);
+    if (xo) *xo = x;
     Vec<T, VEC> z;
     if (zrow) {
         typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -406,6 +409,59 @@ __device__ __forceinline__ Vec<T, VEC> ax3_piece(Vec<T, VEC> s, const T *__restr
 #pragma unroll
     for (int i = 0; i < VEC; ++i) s.v[i] = fma(a, s.v[i], fma(c, x.v[i], zrow ? d * z.v[i] : T(0)));
     return s;
+}
+
+// Column dots at the fused store (DOT, lz_csr_spmm_axpby_dots): a lane's running
+// y.y and y.x of the pieces it stores -- always the same 16-B column piece, since
+// the store loops step by 256 lanes and a row has 8 -- in fp64 for both dtypes
+// (an fp32 product is exact there).
+template <typename T, int VEC>
+struct DotAcc {
+    double yy[VEC], yx[VEC];
+    __device__ __forceinline__ void clear()
+    {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) yy[i] = yx[i] = 0.0;
+    }
+    __device__ __forceinline__ void add(const Vec<T, VEC> &y, const Vec<T, VEC> &x)
+    {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            const double yd = (double)y.v[i];
+            yy[i] = fma(yd, yd, yy[i]);
+            yx[i] = fma(yd, (double)x.v[i], yx[i]);
+        }
+    }
+};
+
+// The tile's slab of 2 B doubles (yy, then yx) from the 256 lanes' sums: the 8
+// lanes of a wave that hold the same piece by xor shuffles (a fixed tree), the 4
+// waves in order through LDS (red: 8 B doubles).  No atomics: the same bits every
+// run.  Every lane of the block calls it.
+template <typename T, int B, int VEC>
+__device__ __forceinline__ void dot_slab(DotAcc<T, VEC> &d, double *red, double *__restrict__ slab)
+{
+    constexpr int LPR = B / VEC;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i)
+#pragma unroll
+        for (int o = LPR; o < 64; o <<= 1) {
+            d.yy[i] += __shfl_xor(d.yy[i], o, 64);
+            d.yx[i] += __shfl_xor(d.yx[i], o, 64);
+        }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane < LPR) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            red[w * 2 * B + lane * VEC + i] = d.yy[i];
+            red[w * 2 * B + B + lane * VEC + i] = d.yx[i];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * B) {
+        const int e = threadIdx.x;
+        slab[e] = ((red[e] + red[2 * B + e]) + red[4 * B + e]) + red[6 * B + e];
+    }
 }
 
 // ---- CU-partitioned SpMM (LZ_SPMM_PF, diagnostic build only: measured and
@@ -430,18 +486,26 @@ __device__ __forceinline__ int xcc_id()
 }
 
 template <typename T, int B, int TR, int CAP, bool WIN, int MODE, bool YCM = false, bool EPI = false, bool PF = false,
-          bool AX3 = false>
+          bool AX3 = false, bool DOT = false>
 __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__restrict__ rp,
                                                   const int32_t *__restrict__ col,
                                                   const T *__restrict__ val,
                                                   const T *__restrict__ X, int64_t ldx, int64_t nx,
                                                   T *__restrict__ Y, int64_t ldy, int *__restrict__ longq,
                                                   int parity, const T *__restrict__ Wp, const T *__restrict__ Mm,
-                                                  int diag, int *__restrict__ pfc, T ca, T cc, T cd)
+                                                  int diag, int *__restrict__ pfc, T ca, T cc, T cd,
+                                                  double *__restrict__ dslab)
 {
     // AX3 (lz_csr_spmm_axpby; square operator, ldx = ldy = B): the stored row is
     // ca Y + cc X[row] + cd Wp[row] (Wp: Z, nullptr when cd == 0), ax3_piece at
     // both store sites; ca, cc, cd are unused otherwise.
+    // DOT (lz_csr_spmm_axpby_dots; with AX3 only): the column dots of the stored
+    // rows with themselves and with X's, one slab of 2 B doubles per tile at
+    // dslab + tile * 2 B, written by the block that stores the tile: the MODE 0
+    // block, or, for a queued tile, the MODE 1 block that draws it (a slab per
+    // tile, not per MODE 1 block: the queue's order is the order of the MODE 0
+    // blocks' atomics and differs from run to run, the tiles do not).
+    static_assert(!DOT || (AX3 && !WIN && !YCM && !EPI && !PF), "DOT: the fused three-term store only");
     // MODE 0: tiles whose run exceeds the stage (or, WIN, whose columns exceed
     //         the window) are queued (longq[0] = count, longq[1..] = tile ids)
     //         for MODE 1, so their code path costs the main kernel no registers;
@@ -583,14 +647,26 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
             if constexpr (YCM) {
                 store_tile_cm<T>(Y, r0, nrows, B, ldy, [&](int r, int c) { return yt[r][c / VEC].v[c % VEC]; });
             } else {
+                [[maybe_unused]] DotAcc<T, VEC> dacc;
+                if constexpr (DOT) dacc.clear();
                 for (int idx = tid; idx < nrows * LPR; idx += 256) {
                     Vec<T, VEC> y = yt[idx / LPR][idx % LPR];
                     if constexpr (EPI)
                         if (epi) y = epi_piece<T, B, VEC>(y, Wp + (r0 + idx / LPR) * B, Ms, idx % LPR);
-                    if constexpr (AX3)
+                    if constexpr (AX3 && DOT) {
+                        Vec<T, VEC> x;
+                        y = ax3_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC,
+                                              Wp ? Wp + (r0 + idx / LPR) * B + (idx % LPR) * VEC : nullptr, ca, cc, cd,
+                                              &x);
+                        dacc.add(y, x);
+                    } else if constexpr (AX3)
                         y = ax3_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC,
                                               Wp ? Wp + (r0 + idx / LPR) * B + (idx % LPR) * VEC : nullptr, ca, cc, cd);
                     stv<T, VEC>(Y + (r0 + idx / LPR) * ldy + (idx % LPR) * VEC, y);
+                }
+                if constexpr (DOT) {  // (red: read here, next written after the next tile's barriers)
+                    __shared__ double red[8 * B];
+                    dot_slab<T, B, VEC>(dacc, red, dslab + (int64_t)longq[2 + qi] * (2 * B));
                 }
             }
         }
@@ -802,13 +878,20 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
         store_tile_cm<T>(Y, r0, nrows, B, ldy, [&](int r, int c) { return yt[r][c / VEC].v[c % VEC]; });
         return;
     }
+    [[maybe_unused]] DotAcc<T, VEC> dacc;
+    if constexpr (DOT) dacc.clear();
     for (int idx = tid; idx < nrows * LPR; idx += 256) {
         if (ry + idx / LPR >= n) break;  // (diag only: a Y tile shorter than the tile read)
         T *dst = Y + (ry + idx / LPR) * ldy + (idx % LPR) * VEC;
         Vec<T, VEC> y = yt[idx / LPR][idx % LPR];
         if constexpr (EPI)
             if (epi) y = epi_piece<T, B, VEC>(y, Wp + (r0 + idx / LPR) * B, Ms, idx % LPR);
-        if constexpr (AX3)
+        if constexpr (AX3 && DOT) {
+            Vec<T, VEC> x;
+            y = ax3_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC,
+                                  Wp ? Wp + (r0 + idx / LPR) * B + (idx % LPR) * VEC : nullptr, ca, cc, cd, &x);
+            dacc.add(y, x);
+        } else if constexpr (AX3)
             y = ax3_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC,
                                   Wp ? Wp + (r0 + idx / LPR) * B + (idx % LPR) * VEC : nullptr, ca, cc, cd);
         if constexpr (sizeof(T) * VEC == 16) {
@@ -819,6 +902,10 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
         } else {
             stv<T, VEC>(dst, y);
         }
+    }
+    if constexpr (DOT) {
+        __shared__ double red[8 * B];
+        dot_slab<T, B, VEC>(dacc, red, dslab + (r0 / TR) * (2 * B));
     }
     }  // MODE 0
 }
@@ -1432,7 +1519,7 @@ static int launch_seg_pf(lz_handle *h, int64_t n, const int64_t *rp, const int32
     // profiles/r06h_pf_trace.csv shows both kernels running at once)
     hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, false, 0, false, false, true>), dim3((unsigned)st), dim3(256), 0,
                        h->pf_sg, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, nullptr, nullptr, 0, h->pf_ctl,
-                       T(0), T(0), T(0));
+                       T(0), T(0), T(0), nullptr);
     // C = 0: the tile kernel alone on its CUs (the masked launch's own cost);
     // 8 blocks per prefetching CU (4 k CUs per XCD); a band wider than `span`
     // rows gets no X prefetch
@@ -1443,7 +1530,8 @@ static int launch_seg_pf(lz_handle *h, int64_t n, const int64_t *rp, const int32
                            (int64_t)h->pf_band);
     const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>(st, (int64_t)h->n_cu * 4));
     hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, false, 1>), dim3(g2), dim3(256), 0, h->pf_sg, n, rp, col, val, X, ldx,
-                       nx, Y, ldy, h->longq, parity, nullptr, nullptr, 0, nullptr, T(0), T(0), T(0));
+                       nx, Y, ldy, h->longq, parity, nullptr, nullptr, 0, nullptr, T(0), T(0), T(0),
+                       nullptr);
     LZ_HIP_TRY(hipEventRecord(h->ev_pfg, h->pf_sg));
     LZ_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_pfg, 0));
     if (k > 0) {
@@ -1461,16 +1549,18 @@ static int launch_seg_pf(lz_handle *h, int64_t n, const int64_t *rp, const int32
 // (count slot plan_slot, *slot_out of that call, or a list spmm_b2_plan made
 // up front) -- the long-tile pass runs
 // first, on its own stream, beside the main kernel, which then only skips them.
-template <typename T, int B, int TR, int CAP, bool WIN, bool YCM = false, bool EPI = false, bool AX3 = false>
+template <typename T, int B, int TR, int CAP, bool WIN, bool YCM = false, bool EPI = false, bool AX3 = false,
+          bool DOT = false>
 static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, const T *val, const T *X,
                       int64_t ldx, int64_t nx, T *Y, int64_t ldy, const T *Wp = nullptr, const T *Mm = nullptr,
-                      int plan_slot = -1, int *slot_out = nullptr, T ca = T(0), T cc = T(0), T cd = T(0))
+                      int plan_slot = -1, int *slot_out = nullptr, T ca = T(0), T cc = T(0), T cd = T(0),
+                      double *dslab = nullptr)
 {
     const int64_t st = ceil_div(n, (int64_t)TR);
     LZ_ARG_CHECK(st < (1LL << 31), "too many row tiles");
     LZ_TRY(ensure_longq(h, st));
     h->last_kernel[0] = (CAP == 768 ? LZ_K_SEG768 : CAP == 1024 ? LZ_K_SEG1024 : LZ_K_SEG1536) | (WIN ? LZ_K_WIN : 0) |
-                        (YCM ? LZ_K_YCM : 0) | (EPI ? LZ_K_EPI : 0) | (AX3 ? LZ_K_AX3 : 0);
+                        (YCM ? LZ_K_YCM : 0) | (EPI ? LZ_K_EPI : 0) | (AX3 ? LZ_K_AX3 : 0) | (DOT ? LZ_K_DOT : 0);
     if (plan_slot >= 0) {
         LZ_ARG_CHECK(plan_slot <= 1 && sizeof(int) * ((size_t)st + 2) <= h->longq_cap, "planned SpMM: no earlier queue");
         if (!h->lstream) {
@@ -1481,13 +1571,13 @@ static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t 
         const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>(st, (int64_t)h->n_cu * 4));
         LZ_HIP_TRY(hipEventRecord(h->ev_lfork, h->stream));
         LZ_HIP_TRY(hipStreamWaitEvent(h->lstream, h->ev_lfork, 0));
-        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI, false, AX3>), dim3(g2), dim3(256), 0,
+        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI, false, AX3, DOT>), dim3(g2), dim3(256), 0,
                            h->lstream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, Wp, Mm, 0, nullptr,
-                           ca, cc, cd);
+                           ca, cc, cd, dslab);
         LZ_HIP_TRY(hipEventRecord(h->ev_ljoin, h->lstream));
-        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI, false, AX3>), dim3((unsigned)st), dim3(256), 0,
-                           h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, Wp, Mm, 0, nullptr,
-                           ca, cc, cd);
+        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI, false, AX3, DOT>), dim3((unsigned)st),
+                           dim3(256), 0, h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, Wp, Mm,
+                           0, nullptr, ca, cc, cd, dslab);
         LZ_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_ljoin, 0));
         return LZ_OK;
     }
@@ -1520,12 +1610,13 @@ static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t 
 #else
     constexpr int diag = 0;
 #endif
-    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI, false, AX3>), dim3((unsigned)st), dim3(256), 0,
-                       h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, Wp, Mm, diag, nullptr, ca, cc,
-                       cd);
+    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI, false, AX3, DOT>), dim3((unsigned)st), dim3(256),
+                       0, h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, Wp, Mm, diag, nullptr, ca,
+                       cc, cd, dslab);
     const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>(st, (int64_t)h->n_cu * 4));
-    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI, false, AX3>), dim3(g2), dim3(256), 0, h->stream, n,
-                       rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, Wp, Mm, 0, nullptr, ca, cc, cd);
+    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI, false, AX3, DOT>), dim3(g2), dim3(256), 0,
+                       h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, Wp, Mm, 0, nullptr, ca, cc, cd,
+                       dslab);
     return LZ_OK;
 }
 
@@ -1736,32 +1827,46 @@ __global__ __launch_bounds__(256) void k_ax3_rows(int64_t nb, T a, T c, T d, con
 // Y = a A X + c X + d Z (lz_csr_spmm_axpby): square operator, ld = b everywhere.
 // Fused into k_spmm_seg's store (AX3) under the conditions launch_spmm_rm picks
 // launch_seg<..., false> for: 128-B rows, X under 2 GiB / 2^24 rows, 16-B
-// aligned blocks.  fused = false (measurement, scripts/cheb_bench.py's two-launch
-// side) or any other shape: spmm_rm, then k_ax3_rows.
+// aligned blocks (Z == nullptr: d == 0).
+template <typename T>
+static bool ax3_store_ok(int64_t n, int b, const T *X, const T *Z, const T *Y)
+{
+    const bool rows128 = (int64_t)b * (int64_t)sizeof(T) == 128;
+    const bool buf_ok = n * b * (int64_t)sizeof(T) < (1LL << 31) && n < (1 << 24);
+    const bool al16 = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) |
+                        reinterpret_cast<uintptr_t>(Z)) & 15) == 0;
+    const char *fz = getenv("LZ_SPMM_FNZ");  // (the fixed-nnz experiment has no fused store)
+    return rows128 && buf_ok && al16 && !(fz && fz[0] == '1');
+}
+
+// the fused launch at those shapes; DOT: with the tiles' dot slabs to dslab
+template <typename T, bool DOT>
+static int launch_ax3(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, T a,
+                      const T *X, T c, T d, const T *Z, T *Y, double *dslab)
+{
+    constexpr int B = 128 / (int)sizeof(T);
+    const bool wide = (double)nnz > 13.0 * (double)n;
+    const int ev = prof_begin(h, PROF_SPMM);
+    const int rc = wide ? launch_seg<T, B, 48, 1536, false, false, false, true, DOT>(
+                              h, n, rp, col, val, X, B, n, Y, B, Z, nullptr, -1, nullptr, a, c, d, dslab)
+                        : launch_seg<T, B, 48, 768, false, false, false, true, DOT>(
+                              h, n, rp, col, val, X, B, n, Y, B, Z, nullptr, -1, nullptr, a, c, d, dslab);
+    prof_end(h, ev);
+    LZ_TRY(rc);
+    LZ_LAUNCH_CHECK();
+    return LZ_OK;
+}
+
+// fused = false (measurement, scripts/cheb_bench.py's two-launch side) or any
+// other shape: spmm_rm, then k_ax3_rows.
 template <typename T>
 int spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
                T a, const T *X, T c, T d, const T *Z, T *Y, bool fused)
 {
     if (n <= 0) return LZ_OK;
     if (d == T(0)) Z = nullptr;
-    const bool rows128 = (int64_t)b * (int64_t)sizeof(T) == 128;
-    const bool buf_ok = n * b * (int64_t)sizeof(T) < (1LL << 31) && n < (1 << 24);
-    const bool al16 = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) |
-                        reinterpret_cast<uintptr_t>(Z)) & 15) == 0;
-    const char *fz = getenv("LZ_SPMM_FNZ");  // (the fixed-nnz experiment has no fused store)
-    if (fused && rows128 && buf_ok && al16 && !(fz && fz[0] == '1')) {
-        constexpr int B = 128 / (int)sizeof(T);
-        const bool wide = (double)nnz > 13.0 * (double)n;
-        const int ev = prof_begin(h, PROF_SPMM);
-        const int rc = wide ? launch_seg<T, B, 48, 1536, false, false, false, true>(h, n, rp, col, val, X, B, n, Y, B,
-                                                                                    Z, nullptr, -1, nullptr, a, c, d)
-                            : launch_seg<T, B, 48, 768, false, false, false, true>(h, n, rp, col, val, X, B, n, Y, B, Z,
-                                                                                   nullptr, -1, nullptr, a, c, d);
-        prof_end(h, ev);
-        LZ_TRY(rc);
-        LZ_LAUNCH_CHECK();
-        return LZ_OK;
-    }
+    if (fused && ax3_store_ok<T>(n, b, X, Z, Y))
+        return launch_ax3<T, false>(h, n, nnz, rp, col, val, a, X, c, d, Z, Y, nullptr);
     LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, X, b, n, Y, b));
     const int64_t nb = n * b;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(nb, (int64_t)256), (int64_t)h->n_cu * 16));
@@ -1770,6 +1875,29 @@ int spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const in
     return LZ_OK;
 }
 
+// spmm_axpby and the stored Y's column dots (lz_csr_spmm_axpby_dots).  At spmm_axpby's
+// fused shapes the dots leave the same store (DOT): a slab per 48-row tile, folded by
+// dots_fold.  fused_dot = false (LZ_AX3DOT=0, measurement), fused = false or any other
+// shape: spmm_axpby as it is, then the streaming col_dots.
+template <typename T>
+int spmm_axpby_dots(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                    T a, const T *X, T c, T d, const T *Z, T *Y, double *dots, bool fused, bool fused_dot)
+{
+    if (d == T(0)) Z = nullptr;
+    if (fused && fused_dot && ax3_store_ok<T>(n, b, X, Z, Y)) {
+        LZ_TRY(dots_reserve(h, n, b));
+        LZ_TRY((launch_ax3<T, true>(h, n, nnz, rp, col, val, a, X, c, d, Z, Y, h->dots_ws)));
+        return dots_fold(h, ceil_div(n, (int64_t)48), b, dots);
+    }
+    LZ_TRY(spmm_axpby<T>(h, n, nnz, rp, col, val, b, a, X, c, d, Z, Y, fused));
+    return col_dots<T>(h, n, b, Y, X, dots);
+}
+
+template int spmm_axpby_dots<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *,
+                                     int, double, const double *, double, double, const double *, double *, double *,
+                                     bool, bool);
+template int spmm_axpby_dots<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
+                                    float, const float *, float, float, const float *, float *, double *, bool, bool);
 template int spmm_axpby<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *, int,
                                 double, const double *, double, double, const double *, double *, bool);
 template int spmm_axpby<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,

@@ -89,7 +89,8 @@ int lz_debug_fail_next_setup(lz_handle *h, int code);
  * with its low byte, on the handle's stream, so a kernel that reads LDS or
  * workspace it did not write shows it deterministically instead of by chance. */
 int lz_debug_poison_lds(lz_handle *h, uint32_t pattern);
-/* (LZ_POISON=1 in the environment: lz_init fills the new handle's workspaces with 0xFF.) */
+/* (LZ_POISON=1 in the environment: lz_init fills the new handle's workspaces with 0xFF, and the
+ * column dots' slab workspace starts so whenever it grows.) */
 
 int lz_prof_enable(lz_handle *h, int on);
 /* As lz_prof_enable, recording only the classes whose bit is set in
@@ -308,6 +309,36 @@ typedef struct {
  * Y.  No host synchronisation. */
 int lz_cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
                   const void *val, lz_dtype dtype, int b, const lz_cheb *f, const void *X, void *Y, void *work);
+
+/* ---------------- column dots and Chebyshev moments (kernel polynomial method)
+ * dots[0 .. b) = sum_i Y[i][c]^2, dots[b .. 2b) = sum_i Y[i][c] X[i][c] for n x b
+ * row-major blocks with ld = b, n >= 1, 1 <= b <= 64, either dtype; products and
+ * sums in fp64, in a fixed order (the same bits run to run).  dots: 2 b doubles in
+ * device memory, written on the handle's stream (no host synchronisation once
+ * the slab workspace has its size).  Y == X is allowed. */
+int lz_col_dots(lz_handle *h, int64_t n, int b, lz_dtype dtype, const void *Y, const void *X, double *dots);
+/* lz_csr_spmm_axpby (same arguments, same rules, the same bits in Y) and the two
+ * column dots of the stored Y with itself and with X, as lz_col_dots returns
+ * them.  Where lz_csr_spmm_axpby fuses its store, the dots leave that store too
+ * (lz_debug_last_kernel: the SpMM id | LZ_K_AX3 | LZ_K_DOT): one slab of 2 b
+ * doubles per 48-row tile, folded in a fixed order.  Every other shape -- and
+ * LZ_AX3DOT=0, a measurement switch read per call -- runs lz_csr_spmm_axpby and
+ * then the streaming kernel of lz_col_dots. */
+int lz_csr_spmm_axpby_dots(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                           const void *val, lz_dtype dtype, int b, double a, const void *X, double c, double d,
+                           const void *Z, void *Y, double *dots);
+/* The raw dots of K Chebyshev steps on Ah = (A - c0) / e, e = (hi - lo) / 2, c0 =
+ * (hi + lo) / 2:  t_0 = X0 (read only), t_1 = Ah t_0, t_{k+1} = 2 Ah t_k - t_{k-1},
+ * one lz_csr_spmm_axpby_dots each, the coefficients host doubles.
+ * dots: (K + 1) x 2 x b doubles on the device; row 0 = (<t_0,t_0>, 0), row k =
+ * (<t_k,t_k>, <t_k,t_{k-1}>) (lzh_kpm_moments turns them into 2 K + 1 moments).
+ * work: 3 n b elements (not read on entry), rotated so that a step's output is
+ * neither of its inputs; X0 and work distinct.  lo < hi, finite; 1 <= K <= 65536.
+ * [lo, hi] must enclose the spectrum: the recurrence grows without bound
+ * otherwise.  No host synchronisation between steps. */
+int lz_cheb_moments(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                    const void *val, lz_dtype dtype, int b, double lo, double hi, int K, const void *X0, void *work,
+                    double *dots);
 /* lz_block_lanczos_reorth / lz_block_lanczos_reorth_resume on the operator
  * p(A): every W = A Q_j of the solve becomes lz_cheb_apply (f, work as there;
  * work distinct from B, W and the panel).  alpha, beta and the projected
@@ -431,7 +462,7 @@ int lz_debug_last_wf(lz_handle *h, int out[2]);
  * b = 32 fp32 or generic-b solve), out[1]: its last Gram / tall-skinny-product
  * launch (lz_gram, lz_sym_cross_gram, lz_tsmm and the solves that call them);
  * 0: none yet.  SpMM ids: a kernel in the low byte, or-ed with the LZ_K_WIN /
- * LZ_K_YCM / LZ_K_EPI / LZ_K_AX3 flags; LZ_K_SPMV carries its lanes per row in bits 16+. */
+ * LZ_K_YCM / LZ_K_EPI / LZ_K_AX3 / LZ_K_DOT flags; LZ_K_SPMV carries its lanes per row in bits 16+. */
 enum {
     LZ_K_SEG768 = 1,    /* nnz-split tiles, 768-entry stage (128-B rows, <= 13 nnz/row) */
     LZ_K_SEG1536 = 2,   /* ... 1536-entry stage (> 13 nnz/row) */
@@ -446,6 +477,7 @@ enum {
     LZ_K_YCM = 0x200,   /* column-major Y store */
     LZ_K_EPI = 0x400,   /* the beta^2 step's epilogue U = A X - Wp M */
     LZ_K_AX3 = 0x800,   /* lz_csr_spmm_axpby's fused three-term store a A X + c X + d Z */
+    LZ_K_DOT = 0x1000,  /* lz_csr_spmm_axpby_dots: the column dots leave the fused store too */
     LZ_K_GRAM16 = 1,    /* dense ids: b = 16 MFMA Gram (fp64 and fp32) */
     LZ_K_GRAM32F = 2,   /* b = 32 fp32 MFMA Gram */
     LZ_K_GRAM_GEN = 3,  /* any b, any pitch */

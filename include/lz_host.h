@@ -128,6 +128,27 @@ int lzh_restart_fill(int r, int m, int b, const double *alpha, const double *bet
  * filter (lz_cheb in lz_hip.h) needs for the end of its damped interval.  fp64
  * values; n >= 1.  Returns 0, or -1 on a bad argument. */
 int lzh_gershgorin(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val, double out[2]);
+/* ------------------------------------------- kernel polynomial method
+ * Chebyshev moments mu_k = x^T T_k(Ah) x of Ah = (A - c0) / e, e = (hi - lo) / 2,
+ * c0 = (hi + lo) / 2, [lo, hi] enclosing the spectrum; their mean over random +-1
+ * probes x estimates tr T_k(Ah).  Every function returns 0, or -1 on a bad
+ * argument (a NULL array, a size below 1, lo >= hi or not finite, a > b).
+ *
+ * lzh_kpm_moments: the raw dots of lz_cheb_moments ((K+1) x 2 x b: row 0 =
+ * (<t0,t0>, 0), row k = (<t_k,t_k>, <t_k,t_{k-1}>)) -> mu, (2K+1) x b, column c the
+ * moments of probe c, by mu_2k = 2 <t_k,t_k> - mu_0, mu_2k+1 = 2 <t_k+1,t_k> - mu_1. */
+int lzh_kpm_moments(int K, int b, const double *dots, double *mu);
+/* The Jackson damping of a series of M moments, k = 0 .. M-1:
+ * g_k = [(M+1-k) cos(pi k/(M+1)) + sin(pi k/(M+1)) cot(pi/(M+1))] / (M+1). */
+int lzh_jackson(int M, double *g);
+/* The eigenvalue count of [a, b] from M moments mu[0 .. M) of one probe (or their
+ * mean): sum_k g_k gamma_k mu_k, gamma_0 = (th_a - th_b) / pi, gamma_k = 2 (sin k th_a -
+ * sin k th_b) / (k pi), th_x = acos(clamp((x - c0) / e)).  g == NULL: no damping. */
+int lzh_kpm_count(int M, const double *mu, const double *g, double lo, double hi, double a, double b, double *count);
+/* The density of states at x[0 .. npts): rho(x) = [g_0 mu_0 + 2 sum_{k>=1} g_k mu_k
+ * T_k(xh)] / (pi e sqrt(1 - xh^2)), xh = (x - c0) / e; 0 outside (lo, hi). */
+int lzh_kpm_density(int M, const double *mu, const double *g, double lo, double hi, int npts, const double *x,
+                    double *rho);
 /* solution = (expm(T_end T)[:, :b] beta_0)^T q  (test_lanczos.cu:272-286) */
 int lzh_block_solution(int m, int b, double T_end, const double *alpha, const double *beta,
                        const double *q, double *solution);
