@@ -40,6 +40,7 @@ LZ_ROW_MAJOR, LZ_COL_MAJOR = 0, 1
 (LZ_K_SEG768, LZ_K_SEG1536, LZ_K_SEG1024, LZ_K_FNZ, LZ_K_BUF, LZ_K_LDS, LZ_K_ANY_B, LZ_K_CM_DIRECT,
  LZ_K_SPMV) = range(1, 10)
 LZ_K_WIN, LZ_K_YCM, LZ_K_EPI, LZ_K_AX3, LZ_K_DOT = 0x100, 0x200, 0x400, 0x800, 0x1000
+LZ_K_AX4 = 0x2000
 LZ_K_GRAM16, LZ_K_GRAM32F, LZ_K_GRAM_GEN, LZ_K_TSMM16, LZ_K_TSMM32F, LZ_K_TSMM_GEN = range(1, 7)
 LZ_K_PGRAM16, LZ_K_PGRAM_GEN, LZ_K_PAPPLY16, LZ_K_PAPPLY_GEN = range(7, 11)
 # blocks per group of the panel Gram kernels (W is re-read once per group): b = 16 fp64 MFMA, generic
@@ -117,6 +118,16 @@ HIP_SYMBOLS = [
     ("lz_block_lanczos_reorth_resume_cheb", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int,
                                                      _c_int, _c_int, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                                      _c_i64, _c_vp, _c_int, _c_vp, _c_vp]),
+    ("lz_csr_spmm_axpby4", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp,
+                                    _c_dbl, _c_dbl, _c_vp, _c_dbl, _c_vp, _c_vp]),
+    ("lz_cheb_series_apply", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_dbl,
+                                      _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lz_block_lanczos_reorth_series", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int,
+                                                _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int,
+                                                _c_int, _c_dbl, _c_dbl, _c_vp, _c_vp]),
+    ("lz_block_lanczos_reorth_resume_series", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int,
+                                                       _c_int, _c_int, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                                       _c_i64, _c_vp, _c_int, _c_int, _c_dbl, _c_dbl, _c_vp, _c_vp]),
     ("lz_csr_transpose", _c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
     ("lz_normal_apply", _c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int,
                                  _c_int, _c_vp, _c_vp, _c_vp]),
@@ -180,6 +191,7 @@ HOST_SYMBOLS = [
     ("lzh_kpm_moments", _c_int, [_c_int, _c_int, _c_vp, _c_vp]),
     ("lzh_jackson", _c_int, [_c_int, _c_vp]),
     ("lzh_kpm_count", _c_int, [_c_int, _c_vp, _c_vp, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_vp]),
+    ("lzh_cheb_window", _c_int, [_c_int, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_vp, _c_vp]),
     ("lzh_kpm_density", _c_int, [_c_int, _c_vp, _c_vp, _c_dbl, _c_dbl, _c_int, _c_vp, _c_vp]),
     ("lzh_block_solution", _c_int, [_c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_partition_rows", _c_int, [_c_i64, _c_vp, _c_int, _c_vp]),
@@ -380,6 +392,20 @@ def kpm_count(mu: np.ndarray, lo: float, hi: float, a: float, b: float, damping=
     if mu.ndim != 1 or host_lib().lzh_kpm_count(mu.size, _p(mu), None if g is None else _p(g), lo, hi, a, b, _p(out)):
         raise LanczosError("lzh_kpm_count failed (M >= 1, lo < hi finite, a <= b)")
     return float(out[0])
+
+
+def cheb_window(degree: int, lo: float, hi: float, a: float, b: float, damping="jackson") -> np.ndarray:
+    """The degree + 1 Chebyshev coefficients of the indicator of the window [a, b] on the
+    enclosure [lo, hi] (lzh_cheb_window): gamma_k = g_k times the weights kpm_count applies to
+    the moments, so cheb_window(...) @ mu == kpm_count(mu, ...).  lo <= a <= b <= hi.
+    Handle.cheb_series_apply evaluates the series on an operator."""
+    M = int(degree) + 1
+    if M < 1:
+        raise LanczosError("cheb_window: degree >= 0")
+    g, gamma = _damping(damping, M), np.empty(M)
+    if host_lib().lzh_cheb_window(M, lo, hi, a, b, None if g is None else _p(g), _p(gamma)):
+        raise LanczosError("lzh_cheb_window failed (lo < hi finite, lo <= a <= b <= hi)")
+    return gamma
 
 
 def kpm_density(mu: np.ndarray, lo: float, hi: float, x, damping="jackson") -> np.ndarray:
@@ -714,8 +740,8 @@ class _ReorthOp(NamedTuple):
     """What Handle._reorth_op makes of A / filt / work / normal: fn(handle, *head, b, ..., passes, *tail)."""
     name: str                    # the ABI function
     head: tuple                  # n [, P.n], nnz, the CSR pointers [and the transpose's], dtype
-    tail: tuple                  # nothing | &filt, work | work
-    filt: Optional[ChebFilter]   # the struct tail points to: alive as long as this description
+    tail: tuple                  # nothing | &filt, work | work | degree, lo, hi, gamma, work
+    filt: object                 # the ChebFilter or gamma array tail points to: alive as long as this description
 
 
 def _f64(t) -> np.ndarray:
@@ -890,6 +916,15 @@ class Handle:
                                         a, _ptr(X), c, d, _ptr(Z), _ptr(Y)), "lz_csr_spmm_axpby")
         return Y
 
+    def spmm_axpby4(self, A: CsrDevice, a: float, X, c: float, d: float, Z, e: float, U, Y):
+        """Y = a (A X) + c X + d Z + e U (lz_csr_spmm_axpby4): spmm_axpby with a fourth term, the
+        step of Clenshaw's recurrence.  Y is distinct from X, Z and U; U may be X or Z.  d == 0
+        never reads Z and e == 0 never reads U; either may then be None."""
+        n, b = self._blocks("spmm_axpby4", A, X, Y, Z, U)
+        _check(self.L.lz_csr_spmm_axpby4(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                         a, _ptr(X), c, d, _ptr(Z), e, _ptr(U), _ptr(Y)), "lz_csr_spmm_axpby4")
+        return Y
+
     def _dots(self, what: str, dots, rows: int, b: int, like):
         """The (rows, 2, b) fp64 device tensor the dots land in (allocated when None)."""
         torch = _torch()
@@ -1006,6 +1041,19 @@ class Handle:
                                     ctypes.addressof(f), _ptr(X), _ptr(Y), _ptr(work)), "lz_cheb_apply")
         return Y
 
+    def cheb_series_apply(self, A: CsrDevice, series, X, Y, work):
+        """Y = sum_k gamma_k T_k((A - c0) / e) X for series = (degree, lo, hi, gamma), [lo, hi] =
+        [c0 - e, c0 + e] enclosing A's spectrum and gamma the degree + 1 coefficients
+        (cheb_window makes a window's), by Clenshaw's recurrence: degree SpMMs
+        (lz_cheb_series_apply).  work: flat, 2*n*b elements; X is only read."""
+        n, b = self._blocks("cheb_series_apply", A, X, Y)
+        self._work("cheb_series_apply", work, n, b, X)
+        degree, lo, hi, gamma = self._series("cheb_series_apply", series)
+        _check(self.L.lz_cheb_series_apply(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                           degree, lo, hi, _p(gamma), _ptr(X), _ptr(Y), _ptr(work)),
+               "lz_cheb_series_apply")
+        return Y
+
     def _normal(self, what: str, normal, n: int, b: int, like):
         """(P, Pt, work) of a normal-operator call on n x b blocks: P (p, n), Pt (n, p) its
         transpose, work flat with p*b elements of the blocks' dtype."""
@@ -1018,11 +1066,27 @@ class Handle:
             raise LanczosError(f"{what}: work is a flat contiguous tensor of p*b elements of the solve's dtype")
         return P, Pt, work
 
-    def _reorth_op(self, what: str, A, n: int, b: int, like, filt, work, normal) -> "_ReorthOp":
-        """The operator of a kept-basis solve (A, p(A) or Pt (P .): block_lanczos_reorth's
-        docstring), validated, as the ABI function lz_<what>[_cheb | _normal] with the
-        arguments that differ between the three."""
+    @staticmethod
+    def _series(what: str, series):
+        """(degree, lo, hi, gamma) of a Chebyshev series, gamma as degree + 1 contiguous host doubles."""
+        degree, lo, hi, gamma = series
+        gamma = np.ascontiguousarray(gamma, np.float64)
+        if int(degree) < 1 or gamma.ndim != 1 or gamma.size != int(degree) + 1:
+            raise LanczosError(f"{what}: series = (degree, lo, hi, gamma) with degree >= 1 and degree + 1 coefficients")
+        return int(degree), float(lo), float(hi), gamma
+
+    def _reorth_op(self, what: str, A, n: int, b: int, like, filt, work, normal, series=None) -> "_ReorthOp":
+        """The operator of a kept-basis solve (A, p(A), Pt (P .) or a Chebyshev series s(A):
+        block_lanczos_reorth's docstring), validated, as the ABI function
+        lz_<what>[_cheb | _normal | _series] with the arguments that differ between the four."""
         csr = lambda M: (_ptr(M.row_ptr), _ptr(M.col), _ptr(M.val))
+        if series is not None:
+            if filt is not None or normal is not None:
+                raise LanczosError(f"{what}: series= is mutually exclusive with filt= and normal=")
+            self._work(what, work, n, b, like)
+            degree, lo, hi, gamma = self._series(what, series)
+            return _ReorthOp(f"lz_{what}_series", (n, A.nnz, *csr(A), A.dtype), (degree, lo, hi, _p(gamma), _ptr(work)),
+                             gamma)
         if normal is not None:
             if filt is not None:
                 raise LanczosError(f"{what}: normal= and filt= are mutually exclusive")
@@ -1144,7 +1208,7 @@ class Handle:
         return W
 
     def block_lanczos_reorth(self, A: CsrDevice, B, m: int, lc: int, q, alpha, beta, V, vstride: int, W,
-                             passes: int = 2, filt=None, work=None, normal=None):
+                             passes: int = 2, filt=None, work=None, normal=None, series=None):
         """Block Lanczos on a kept basis with `passes` rounds of full reorthogonalisation
         per step (lz_block_lanczos_reorth).  q[m*b], alpha[m,b,b], beta[m+1,b,b] (beta[m]
         = the true beta_m), the panel V (m blocks) and W (the final residual) are written
@@ -1152,10 +1216,12 @@ class Handle:
         solve on the Chebyshev-filtered operator p(A) (lz_block_lanczos_reorth_cheb).
         normal = (P, Pt, work) with P (p, n), Pt its transpose and work flat with p*b elements:
         the same solve on G = P^T P (lz_block_lanczos_reorth_normal); A is not used then (None)
-        and filt must be None."""
+        and filt must be None.  series = (degree, lo, hi, gamma) with work as for filt: the
+        same solve on the Chebyshev series sum_k gamma_k T_k((A - c0) / e) of cheb_series_apply
+        (lz_block_lanczos_reorth_series); filt and normal must be None."""
         n, b = B.shape
         self._panel(V, vstride, n, b, max(m, 1))
-        op = self._reorth_op("block_lanczos_reorth", A, n, b, W, filt, work, normal)
+        op = self._reorth_op("block_lanczos_reorth", A, n, b, W, filt, work, normal, series)
         _check(getattr(self.L, op.name)(self.ptr, *op.head, b, m, lc, _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta),
                                         _ptr(V), vstride, _ptr(W), passes, *op.tail), op.name)
 
@@ -1200,18 +1266,20 @@ class Handle:
         return V
 
     def block_lanczos_reorth_resume(self, A: CsrDevice, r: int, m: int, lc: int, sigma, q, alpha, beta, V,
-                                    vstride: int, W, passes: int = 2, filt=None, work=None, normal=None):
+                                    vstride: int, W, passes: int = 2, filt=None, work=None, normal=None,
+                                    series=None):
         """Steps r .. m-1 of block_lanczos_reorth on a thick-restarted basis
         (lz_block_lanczos_reorth_resume): blocks 0 .. r-1 of V hold the kept Ritz blocks
         (panel_compress), W the previous cycle's residual, sigma (r, b, b) the device copy of
         restart_coeffs' sigma.  Writes alpha[r:], beta[r:], q[r*b:], blocks r .. m-1 and W.
-        filt, work, normal: as block_lanczos_reorth (the same operator for every cycle of a solve)."""
+        filt, work, normal, series: as block_lanczos_reorth (the same operator for every cycle of a
+        solve)."""
         n, b = W.shape
         self._panel(V, vstride, n, b, max(m, 1))
         if not sigma.is_contiguous() or sigma.numel() < max(r, 0) * b * b or sigma.dtype != W.dtype \
                 or V.dtype != W.dtype or not W.is_contiguous():
             raise LanczosError("block_lanczos_reorth_resume: W (n, b) and sigma (r, b, b) contiguous, one dtype")
-        op = self._reorth_op("block_lanczos_reorth_resume", A, n, b, W, filt, work, normal)
+        op = self._reorth_op("block_lanczos_reorth_resume", A, n, b, W, filt, work, normal, series)
         _check(getattr(self.L, op.name)(self.ptr, *op.head, b, r, m, lc, _ptr(sigma), _ptr(q), _ptr(alpha),
                                         _ptr(beta), _ptr(V), vstride, _ptr(W), passes, *op.tail), op.name)
 
@@ -1419,6 +1487,120 @@ class Handle:
         return dict(theta=lam[sel], resid=res[sel], V=V, vstride=vstride, cycles=d.cycles,
                     n_spmm=m + (d.steps - m) * degree + nch * d.cycles, converged=converged, history=history,
                     scale=scale, cols=sel, filter=filt, n_steps=d.steps)
+
+    def eigsh_interval(self, A: CsrDevice, a: float, b: float, /, block: int = 16, m: Optional[int] = None,
+                       keep: Optional[int] = None, degree: Optional[int] = None, bounds=None, pad: float = 0.01,
+                       tol: float = 1e-10, max_cycles: int = 100, B=None, lc: int = 0, passes: int = 2):
+        """The eigenpairs of the symmetric operator A inside the window [a, b], anywhere in the
+        spectrum, by thick-restart block Lanczos on p(A), p the Jackson-damped Chebyshev series
+        of the window's indicator (cheb_window, cheb_series_apply): p is near 1 inside [a, b]
+        and near 0 away from it, so the wanted pairs are the largest of p(A).
+
+        Enclosure: bounds = (lo, hi), default gershgorin(A) (one copy of the CSR arrays to the
+        host), each end moved out by pad x the width as spectral_moments does; [a, b] must lie
+        inside it.  degree: default ceil(2 pi e / (b - a)) clipped to [16, 65536], e half the
+        enclosure's width -- the degree that resolves the window, so the cost grows like
+        n / (eigenvalues per window): the method serves windows that hold a fair share of the
+        spectrum, or operators up to about 1e5 - 1e6 rows.  The coefficients are fixed for
+        the whole solve.  m blocks in the panel, keep of them kept at a restart: keep <
+        m <= PANEL_MAX_BLOCKS, keep <= PANEL_MAX_KEEP; default keep 4 (m - 1 if smaller), default
+        m as eigsh's for nev = (keep - 1) * block.  The panel can hold at most keep * block - 1 pairs
+        of the window.
+
+        Every cycle: the restart of eigsh on p(A) at the largest end of T (first /
+        compress / resume of the shared driver); after the compress, Rayleigh-Ritz on A over
+        the whole kept subspace Y = [Y_0 .. Y_{keep-1}] -- p's values inside the window are
+        nearly degenerate, so the kept Ritz vectors of p(A) mix across blocks: H = Y^T A Y from
+        one SpMM and one panel_gram per kept block, eigh(H) on the host, the rotated vectors
+        formed block by block (panel_apply into the series' free workspace) and their true
+        residuals ||A x - lambda x|| measured with one more SpMM per block.  The panel itself
+        is not rotated: the Lanczos relation of the restart stays intact.
+
+        Stop test, with scale = max(|lo|, |hi|) of the widened enclosure (a bound of ||A||
+        known before the first cycle): converged when every kept pair whose interval
+        [lambda - res, lambda + res] meets [a, b] has res <= tol * scale and fewer than
+        keep * block pairs lie in [a, b].  When all keep * block lie inside, the window may
+        hold more than the panel keeps: it returns after that cycle with full = True,
+        converged = False and no exception -- narrow the window or raise keep (eigcount sizes
+        windows).  Otherwise it stops after max_cycles cycles (converged = False).
+
+        Finish: one panel_compress packs the eigenvectors of the count pairs inside [a, b] into
+        the first ceil(count / block) blocks of the panel, sorted by lambda ascending, the last
+        zero-padded.  Returns a dict: theta[count] ascending, resid[count] (measured on A),
+        count, V (the panel, flat), vstride, cycles, n_steps (Lanczos steps), n_spmm = degree *
+        n_steps + 2 * keep * cycles (every SpMM: degree per step, 2 keep per cycle's check),
+        converged, full, history (per cycle, the largest residual among the pairs that meet
+        the window; 0 when none does), scale, filter = (degree, lo, hi).  Device memory that
+        scales with n: the panel, W, B and 2 n block elements of workspace."""
+        torch = _torch()
+        a, b = float(a), float(b)
+        if not a < b:
+            raise LanczosError(f"eigsh_interval: the window [{a}, {b}] needs a < b")
+        lo, hi = gershgorin(A) if bounds is None else (float(bounds[0]), float(bounds[1]))
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi and pad >= 0):
+            raise LanczosError(f"eigsh_interval: bounds ({lo}, {hi}) must be finite with lo < hi, pad >= 0")
+        lo, hi = lo - pad * (hi - lo), hi + pad * (hi - lo)
+        if not (lo <= a and b <= hi):
+            raise LanczosError(f"eigsh_interval: the window [{a}, {b}] is not inside the enclosure [{lo}, {hi}]")
+        if degree is None:
+            degree = min(65536, max(16, int(np.ceil(np.pi * (hi - lo) / (b - a)))))
+        if not 1 <= int(degree) <= 65536:
+            raise LanczosError("eigsh_interval: 1 <= degree <= 65536")
+        degree = int(degree)
+        if keep is None:
+            keep = 4 if m is None else max(1, min(4, m - 1))
+        m, r = _restart_sizes("eigsh_interval", "(keep - 1) * block", max((keep - 1) * block, 1), block, m, keep)
+        n, bs = A.n, block
+        scale = max(abs(lo), abs(hi))
+        gamma = cheb_window(degree, lo, hi, a, b)
+        work = torch.empty(2 * n * bs, dtype=A.val.dtype, device=A.val.device)
+        d = _Restart(self, A, n, bs, m, r, lc, passes, A.val, series=(degree, lo, hi, gamma), work=work)
+        V, vstride, kw = d.V, d.vstride, d.kw
+        U, X = work[:n * bs].view(n, bs), work[n * bs:].view(n, bs)  # (the series' workspace is free between solves)
+        C = torch.empty(r, bs, bs, **kw)
+        G, Dm = torch.empty(bs, bs, **kw), torch.empty(bs, bs, **kw)
+        rb = r * bs
+
+        def check():
+            """Rayleigh-Ritz on A over the r kept blocks: (lambda ascending, true residual norms,
+            the rb x rb rotation).  W and the panel are not touched."""
+            H = np.empty((rb, rb))
+            for i in range(r):
+                self.spmm(A, V[i * vstride:i * vstride + n * bs].view(n, bs), U)
+                self.panel_gram(V, vstride, r, U, C)  # C_j = Y_j^T A Y_i: block column i of H
+                H[:, i * bs:(i + 1) * bs] = _f64(C).reshape(rb, bs)
+            lam, Cm = np.linalg.eigh(0.5 * (H + H.T))
+            Sd = torch.from_numpy(_pack_chunks(Cm, r, bs)).to(**kw)
+            res = np.empty(rb)
+            for c in range(r):
+                self.panel_apply(0.0, 1.0, V, vstride, r, Sd[c], X)
+                self.spmm(A, X, U)
+                Dm.copy_(torch.from_numpy(np.diag(lam[c * bs:(c + 1) * bs])).to(**kw))
+                self.mm_ts(1.0, -1.0, X, Dm, U)
+                self.mm_tt(U, G)
+                res[c * bs:(c + 1) * bs] = np.sqrt(np.maximum(np.diag(_f64(G)), 0.0))
+            return lam, res, Cm
+
+        d.first(d.start_block(B))
+        history = []
+        while True:
+            d.compress("largest")
+            lam, res, Cm = check()
+            meets = (lam + res >= a) & (lam - res <= b)
+            inside = (lam >= a) & (lam <= b)
+            full = bool(inside.sum() == rb)
+            history.append(float(res[meets].max()) if meets.any() else 0.0)
+            converged = bool(not full and (res[meets] <= tol * scale).all())
+            if converged or full or d.cycles >= max_cycles:
+                break
+            d.resume()
+        sel = np.flatnonzero(inside)  # (eigh: lambda ascending)
+        if sel.size:
+            Zx = _pack_chunks(Cm[:, sel], r, bs)
+            self.panel_compress(V, vstride, r, len(Zx), d._dev(Zx), n=n)
+        return dict(theta=lam[sel], resid=res[sel], count=int(sel.size), V=V, vstride=vstride, cycles=d.cycles,
+                    n_steps=d.steps, n_spmm=degree * d.steps + 2 * r * d.cycles, converged=converged, full=full,
+                    history=history, scale=scale, filter=(degree, lo, hi))
 
     def set_final_state(self, on: bool) -> None:
         """True (default): block_lanczos_blas leaves Q0 = Q1 = Q_{m-1} and W = the

@@ -301,9 +301,57 @@ static int cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, c
     return LZ_OK;
 }
 
-// The operator of a kept-basis solve, in one of three forms:
+// A Chebyshev series on the enclosure [lo, hi] (lz_cheb_series_apply): gamma is degree + 1 host
+// doubles, work the 2 n b elements of the solve's dtype its steps rotate through
+struct SeriesArgs {
+    int degree;
+    double lo, hi;
+    const double *gamma;
+    void *work;
+};
+
+static int series_args(const SeriesArgs *sr)
+{
+    LZ_ARG_CHECK(sr->degree >= 1 && sr->degree <= 65536, "Chebyshev series: 1 <= degree <= 65536");
+    LZ_ARG_CHECK(std::isfinite(sr->lo) && std::isfinite(sr->hi) && sr->lo < sr->hi, "Chebyshev series: lo < hi, finite");
+    LZ_ARG_CHECK(sr->gamma != nullptr, "Chebyshev series: gamma is NULL");
+    return LZ_OK;
+}
+
+// Y = sum_k gamma_k T_k(Ah) X by Clenshaw's recurrence (lz_cheb_series_apply): with D = degree,
+// step 1 is b_{D-1} = gamma_{D-1} X + 2 Ah (gamma_D X), a three-term step on X; step i >= 2 is
+// b_k = gamma_k X + 2 Ah b_{k+1} - b_{k+2}, k = D - i, a four-term step with U = X (b_D = gamma_D X
+// is never stored: at k = D - 2 it joins the U term); the last one, k = 0, has Ah in place of
+// 2 Ah.  Step i writes buffer (i + 2 - D) mod 3 of {work_0, work_1, Y}, as cheb_apply does.
+template <typename T>
+static int cheb_series_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                             const T *val, int b, const SeriesArgs &sr, const T *X, T *Y, T *work)
+{
+    const int D = sr.degree;
+    const double e = 0.5 * (sr.hi - sr.lo), c0 = 0.5 * (sr.hi + sr.lo);
+    const double *g = sr.gamma;
+    T *buf[3] = {work, work + n * b, Y};
+    const bool fused = ax3_fused();
+    auto out = [&](int i) { return buf[((i + 2 - D) % 3 + 3) % 3]; };
+    if (D == 1)
+        return spmm_axpby<T>(h, n, nnz, rp, col, val, b, T(g[1] / e), X, T(g[0] - g[1] * c0 / e), T(0), nullptr, Y,
+                             fused);
+    LZ_TRY(spmm_axpby<T>(h, n, nnz, rp, col, val, b, T(2.0 * g[D] / e), X, T(g[D - 1] - 2.0 * g[D] * c0 / e), T(0),
+                         nullptr, out(1), fused));
+    for (int i = 2; i <= D; ++i) {
+        const int k = D - i;
+        const double f = k > 0 ? 2.0 : 1.0;
+        const bool noz = i == 2;  // b_{k+2} = gamma_D X
+        LZ_TRY(spmm_axpby4<T>(h, n, nnz, rp, col, val, b, T(f / e), out(i - 1), T(-f * c0 / e), noz ? T(0) : T(-1),
+                              noz ? nullptr : out(i - 2), T(noz ? g[k] - g[D] : g[k]), X, out(i), fused));
+    }
+    return LZ_OK;
+}
+
+// The operator of a kept-basis solve, in one of four forms:
 //   A          f == nullptr, p == 0: the n x n CSR (rp, col, val)
 //   p(A)       f != nullptr: the Chebyshev filter on it, work 2 n b elements
+//   s(A)       sr != nullptr: a Chebyshev series on it, work 2 n b elements
 //   P^T (P Q)  p > 0: (rp, col, val) is P, p x n, and (trp, tcol, tval) its n x p
 //              transpose Pt; work p b elements
 template <typename T>
@@ -314,6 +362,7 @@ struct ReorthOp {
     const T *val;
     const lz_cheb *f = nullptr;
     T *work = nullptr;
+    const SeriesArgs *sr = nullptr;
     int64_t p = 0;
     const int64_t *trp = nullptr;
     const int32_t *tcol = nullptr;
@@ -332,10 +381,12 @@ struct NormalArgs {
 
 template <typename T>
 static ReorthOp<T> make_op(int64_t nnz, const int64_t *rp, const int32_t *col, const void *val, const lz_cheb *f,
-                           void *work, const NormalArgs *nm)
+                           void *work, const NormalArgs *nm, const SeriesArgs *sr = nullptr)
 {
     ReorthOp<T> op{nnz, rp, col, (const T *)val};
-    if (nm) {
+    if (sr) {
+        op.sr = sr, op.work = (T *)sr->work;
+    } else if (nm) {
         op.p = nm->p, op.trp = nm->t_rp, op.tcol = nm->t_col, op.tval = (const T *)nm->t_val;
         op.work = (T *)nm->work;
     } else {
@@ -352,6 +403,7 @@ static int reorth_op(lz_handle *h, int64_t n, int b, const ReorthOp<T> &op, cons
         LZ_TRY(spmm_rm<T>(h, op.p, op.nnz, op.rp, op.col, op.val, b, Q, b, n, op.work, b));
         return spmm_rm<T>(h, n, op.nnz, op.trp, op.tcol, op.tval, b, op.work, b, op.p, W, b);
     }
+    if (op.sr) return cheb_series_apply<T>(h, n, op.nnz, op.rp, op.col, op.val, b, *op.sr, Q, W, op.work);
     if (!op.f) return spmm_rm<T>(h, n, op.nnz, op.rp, op.col, op.val, b, Q, b, n, W, b);
     return cheb_apply<T>(h, n, op.nnz, op.rp, op.col, op.val, b, *op.f, Q, W, op.work);
 }
@@ -1931,6 +1983,21 @@ static int cheb_solve_args(const lz_cheb *f, const void *work, int64_t n, int b,
     return LZ_OK;
 }
 
+// the series and its workspace of a solve on s(A), as cheb_solve_args
+static int series_solve_args(const SeriesArgs *sr, int64_t n, int b, int m, lz_dtype dtype, const void *V,
+                             int64_t vstride, const void *W, const void *B)
+{
+    if (!sr) return LZ_OK;
+    LZ_TRY(series_args(sr));
+    LZ_ARG_CHECK(sr->work != nullptr, "work is NULL");
+    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
+    LZ_ARG_CHECK(reinterpret_cast<uintptr_t>(sr->work) % 16 == 0, "work must be on 16 bytes");
+    LZ_ARG_CHECK(blocks_apart(sr->work, 2 * nb, W, nb, es) && (!B || blocks_apart(sr->work, 2 * nb, B, nb, es)) &&
+                     blocks_apart(sr->work, 2 * nb, V, (int64_t)(m - 1) * vstride + nb, es),
+                 "work must not overlap B, W or the panel V");
+    return LZ_OK;
+}
+
 // work (p b) apart from W, B (may be null) and the panel, as cheb_solve_args
 static int normal_solve_args(const NormalArgs *nm, int64_t n, int b, int m, lz_dtype dtype, const void *V,
                              int64_t vstride, const void *W, const void *B)
@@ -2098,7 +2165,7 @@ int lz_block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t 
 static int reorth_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
                         lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q, void *alpha, void *beta,
                         void *V, int64_t vstride, void *W, int passes, const lz_cheb *f, void *work,
-                        const NormalArgs *nm)
+                        const NormalArgs *nm, const SeriesArgs *sr = nullptr)
 {
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(nm ? nm->p : n, nnz, rp, col, val));
@@ -2116,9 +2183,10 @@ static int reorth_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp,
     }
     LZ_TRY(cheb_solve_args(f, work, n, b, m, dtype, V, vstride, W, B));
     LZ_TRY(normal_solve_args(nm, n, b, m, dtype, V, vstride, W, B));
+    LZ_TRY(series_solve_args(sr, n, b, m, dtype, V, vstride, W, B));
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        return block_lanczos_reorth<T>(h, n, make_op<T>(nnz, rp, col, val, f, work, nm), b, m, lc, (const T *)B, (T *)q,
+        return block_lanczos_reorth<T>(h, n, make_op<T>(nnz, rp, col, val, f, work, nm, sr), b, m, lc, (const T *)B, (T *)q,
                                        (T *)alpha, (T *)beta, (T *)V, vstride, (T *)W, passes);
     });
 }
@@ -2169,7 +2237,7 @@ int lz_block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, const i
 static int resume_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
                         lz_dtype dtype, int b, int r, int m, int64_t lc, const void *sigma, void *q, void *alpha,
                         void *beta, void *V, int64_t vstride, void *W, int passes, const lz_cheb *f, void *work,
-                        const NormalArgs *nm)
+                        const NormalArgs *nm, const SeriesArgs *sr = nullptr)
 {
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(nm ? nm->p : n, nnz, rp, col, val));
@@ -2188,9 +2256,10 @@ static int resume_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp,
     }
     LZ_TRY(cheb_solve_args(f, work, n, b, m, dtype, V, vstride, W, nullptr));
     LZ_TRY(normal_solve_args(nm, n, b, m, dtype, V, vstride, W, nullptr));
+    LZ_TRY(series_solve_args(sr, n, b, m, dtype, V, vstride, W, nullptr));
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        return block_lanczos_reorth_resume<T>(h, n, make_op<T>(nnz, rp, col, val, f, work, nm), b, r, m, lc,
+        return block_lanczos_reorth_resume<T>(h, n, make_op<T>(nnz, rp, col, val, f, work, nm, sr), b, r, m, lc,
                                               (const T *)sigma, (T *)q, (T *)alpha, (T *)beta, (T *)V, vstride,
                                               (T *)W, passes);
     });
@@ -2214,6 +2283,69 @@ int lz_block_lanczos_reorth_resume_normal(lz_handle *h, int64_t n, int64_t p, in
     const NormalArgs nm{p, t_rp, t_col, t_val, work};
     return resume_entry(h, n, nnz, rp, col, val, dtype, b, r, m, lc, sigma, q, alpha, beta, V, vstride, W, passes,
                         nullptr, nullptr, &nm);
+}
+
+int lz_csr_spmm_axpby4(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                       lz_dtype dtype, int b, double a, const void *X, double c, double d, const void *Z, double e,
+                       const void *U, void *Y)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(b >= 1 && b <= kMaxB, "b in [1,64]");
+    LZ_ARG_CHECK(X && Y && (Z || d == 0.0), "X/Y NULL, or Z NULL with d != 0");
+    LZ_ARG_CHECK(U || e == 0.0, "U NULL with e != 0");
+    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
+    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && (d == 0.0 || (blocks_apart(Z, nb, Y, nb, es) && Z != X)) &&
+                     (e == 0.0 || blocks_apart(U, nb, Y, nb, es)),
+                 "Y must be distinct from X, Z and U, and Z from X (no in-place form)");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return spmm_axpby4<T>(h, n, nnz, rp, col, (const T *)val, b, (T)a, (const T *)X, (T)c, (T)d, (const T *)Z, (T)e,
+                              (const T *)U, (T *)Y, ax3_fused());
+    });
+}
+
+int lz_cheb_series_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                         lz_dtype dtype, int b, int degree, double lo, double hi, const double *gamma, const void *X,
+                         void *Y, void *work)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= kMaxB, "n >= 1, b in [1,64]");
+    LZ_ARG_CHECK(X && Y && work, "X/Y/work NULL");
+    const SeriesArgs sr{degree, lo, hi, gamma, work};
+    LZ_TRY(series_args(&sr));
+    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
+    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && blocks_apart(work, 2 * nb, X, nb, es) &&
+                     blocks_apart(work, 2 * nb, Y, nb, es),
+                 "X, Y and work must be pairwise distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return cheb_series_apply<T>(h, n, nnz, rp, col, (const T *)val, b, sr, (const T *)X, (T *)Y, (T *)work);
+    });
+}
+
+int lz_block_lanczos_reorth_series(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                                   const void *val, lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q,
+                                   void *alpha, void *beta, void *V, int64_t vstride, void *W, int passes, int degree,
+                                   double lo, double hi, const double *gamma, void *work)
+{
+    const SeriesArgs sr{degree, lo, hi, gamma, work};
+    return reorth_entry(h, n, nnz, rp, col, val, dtype, b, m, lc, B, q, alpha, beta, V, vstride, W, passes, nullptr,
+                        nullptr, nullptr, &sr);
+}
+
+int lz_block_lanczos_reorth_resume_series(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                                          const void *val, lz_dtype dtype, int b, int r, int m, int64_t lc,
+                                          const void *sigma, void *q, void *alpha, void *beta, void *V,
+                                          int64_t vstride, void *W, int passes, int degree, double lo, double hi,
+                                          const double *gamma, void *work)
+{
+    const SeriesArgs sr{degree, lo, hi, gamma, work};
+    return resume_entry(h, n, nnz, rp, col, val, dtype, b, r, m, lc, sigma, q, alpha, beta, V, vstride, W, passes,
+                        nullptr, nullptr, nullptr, &sr);
 }
 
 int lz_vector_lanczos(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,

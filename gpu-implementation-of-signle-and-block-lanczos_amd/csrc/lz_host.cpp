@@ -685,15 +685,30 @@ static double kpm_theta(double x, double c0, double e)
     return std::acos(t < -1.0 ? -1.0 : t > 1.0 ? 1.0 : t);
 }
 
+// the weight of moment k in the indicator series of [a, b] (th_a, th_b its ends' angles), damped
+static double kpm_window_weight(int k, const double *g, double ta, double tb)
+{
+    if (k == 0) return (g ? g[0] : 1.0) * (ta - tb) / M_PI;
+    return (g ? g[k] : 1.0) * 2.0 * (std::sin(k * ta) - std::sin(k * tb)) / (k * M_PI);
+}
+
 int lzh_kpm_count(int M, const double *mu, const double *g, double lo, double hi, double a, double b, double *count)
 {
     if (M < 1 || !mu || !count || !kpm_bounds_ok(lo, hi) || !(a <= b)) return -1;
     const double e = 0.5 * (hi - lo), c0 = 0.5 * (hi + lo);
     const double ta = kpm_theta(a, c0, e), tb = kpm_theta(b, c0, e);
-    double s = (g ? g[0] : 1.0) * (ta - tb) / M_PI * mu[0];
-    for (int k = 1; k < M; ++k)
-        s += (g ? g[k] : 1.0) * 2.0 * (std::sin(k * ta) - std::sin(k * tb)) / (k * M_PI) * mu[k];
+    double s = kpm_window_weight(0, g, ta, tb) * mu[0];
+    for (int k = 1; k < M; ++k) s += kpm_window_weight(k, g, ta, tb) * mu[k];
     *count = s;
+    return 0;
+}
+
+int lzh_cheb_window(int M, double lo, double hi, double a, double b, const double *g, double *gamma)
+{
+    if (M < 1 || !gamma || !kpm_bounds_ok(lo, hi) || !(lo <= a && a <= b && b <= hi)) return -1;
+    const double e = 0.5 * (hi - lo), c0 = 0.5 * (hi + lo);
+    const double ta = kpm_theta(a, c0, e), tb = kpm_theta(b, c0, e);
+    for (int k = 0; k < M; ++k) gamma[k] = kpm_window_weight(k, g, ta, tb);
     return 0;
 }
 

@@ -24,6 +24,11 @@ template <typename T>
 int spmm_axpby_dots(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
                     T a, const T *X, T c, T d, const T *Z, T *Y, double *dots, bool fused = true,
                     bool fused_dot = true);
+// Y = a A X + c X + d Z + e U (lz_csr_spmm_axpby4): spmm_axpby's shapes and switch with U on
+// 16 bytes too (last_kernel | LZ_K_AX3 | LZ_K_AX4); U may be X or Z; e == 0 never reads U
+template <typename T>
+int spmm_axpby4(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                T a, const T *X, T c, T d, const T *Z, T e, const T *U, T *Y, bool fused = true);
 template <typename T>
 int spmm_cm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
             const T *X, int64_t ldx, int64_t nx, T *Y, int64_t ldy);  // nx: rows of X

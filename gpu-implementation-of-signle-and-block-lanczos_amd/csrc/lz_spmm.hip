@@ -411,6 +411,37 @@ __device__ __forceinline__ Vec<T, VEC> ax3_piece(Vec<T, VEC> s, const T *__restr
     return s;
 }
 
+// Four-term row piece (AX4, lz_csr_spmm_axpby4): a s + c x + d z + e u, u the lane's
+// own 16-B piece of U[row], streamed once like z (non-temporal; U may be X or Z: all
+// three are only read).  One arithmetic order, which k_ax4_rows repeats on the stored
+// row: fma(a, s, fma(c, x, t)) with t = fma(d, z, e u), or d z (urow == nullptr: e == 0),
+// or e u (zrow == nullptr: d == 0), or 0 -- without U it is ax3_piece's.
+template <typename T, int VEC>
+__device__ __forceinline__ Vec<T, VEC> ax4_piece(Vec<T, VEC> s, const T *__restrict__ xrow,
+                                                 const T *__restrict__ zrow, const T *__restrict__ urow, T a,
+                                                 T c, T d, T e)
+{
+    static_assert(sizeof(T) * VEC == 16, "128-B rows: 16-B pieces");
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const Vec<T, VEC> x = ldv<T, VEC>(xrow);
+    Vec<T, VEC> z, u;
+    if (zrow) {
+        const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(zrow));
+        __builtin_memcpy(&z, &r, 16);
+    }
+    if (urow) {
+        const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(urow));
+        __builtin_memcpy(&u, &r, 16);
+    }
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+        T t = urow ? e * u.v[i] : T(0);
+        if (zrow) t = urow ? fma(d, z.v[i], t) : d * z.v[i];
+        s.v[i] = fma(a, s.v[i], fma(c, x.v[i], t));
+    }
+    return s;
+}
+
 // Column dots at the fused store (DOT, lz_csr_spmm_axpby_dots): a lane's running
 // y.y and y.x of the pieces it stores -- always the same 16-B column piece, since
 // the store loops step by 256 lanes and a row has 8 -- in fp64 for both dtypes
@@ -486,7 +517,7 @@ __device__ __forceinline__ int xcc_id()
 }
 
 template <typename T, int B, int TR, int CAP, bool WIN, int MODE, bool YCM = false, bool EPI = false, bool PF = false,
-          bool AX3 = false, bool DOT = false>
+          bool AX3 = false, bool DOT = false, bool AX4 = false>
 __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__restrict__ rp,
                                                   const int32_t *__restrict__ col,
                                                   const T *__restrict__ val,
@@ -494,7 +525,7 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
                                                   T *__restrict__ Y, int64_t ldy, int *__restrict__ longq,
                                                   int parity, const T *__restrict__ Wp, const T *__restrict__ Mm,
                                                   int diag, int *__restrict__ pfc, T ca, T cc, T cd,
-                                                  double *__restrict__ dslab)
+                                                  double *__restrict__ dslab, const T *__restrict__ Up, T ce)
 {
     // AX3 (lz_csr_spmm_axpby; square operator, ldx = ldy = B): the stored row is
     // ca Y + cc X[row] + cd Wp[row] (Wp: Z, nullptr when cd == 0), ax3_piece at
@@ -505,7 +536,11 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
     // block, or, for a queued tile, the MODE 1 block that draws it (a slab per
     // tile, not per MODE 1 block: the queue's order is the order of the MODE 0
     // blocks' atomics and differs from run to run, the tiles do not).
+    // AX4 (lz_csr_spmm_axpby4; with AX3 only, not with DOT): one more term, ce Up[row] (Up: U,
+    // nullptr when ce == 0; it may be X or Wp), ax4_piece at both store sites; Up and ce are
+    // unused otherwise.
     static_assert(!DOT || (AX3 && !WIN && !YCM && !EPI && !PF), "DOT: the fused three-term store only");
+    static_assert(!AX4 || (AX3 && !DOT && !WIN && !YCM && !EPI && !PF), "AX4: the fused three-term store only");
     // MODE 0: tiles whose run exceeds the stage (or, WIN, whose columns exceed
     //         the window) are queued (longq[0] = count, longq[1..] = tile ids)
     //         for MODE 1, so their code path costs the main kernel no registers;
@@ -653,7 +688,11 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
                     Vec<T, VEC> y = yt[idx / LPR][idx % LPR];
                     if constexpr (EPI)
                         if (epi) y = epi_piece<T, B, VEC>(y, Wp + (r0 + idx / LPR) * B, Ms, idx % LPR);
-                    if constexpr (AX3 && DOT) {
+                    if constexpr (AX4) {
+                        const int64_t o = (r0 + idx / LPR) * B + (idx % LPR) * VEC;
+                        y = ax4_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC, Wp ? Wp + o : nullptr,
+                                              Up ? Up + o : nullptr, ca, cc, cd, ce);
+                    } else if constexpr (AX3 && DOT) {
                         Vec<T, VEC> x;
                         y = ax3_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC,
                                               Wp ? Wp + (r0 + idx / LPR) * B + (idx % LPR) * VEC : nullptr, ca, cc, cd,
@@ -886,7 +925,11 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
         Vec<T, VEC> y = yt[idx / LPR][idx % LPR];
         if constexpr (EPI)
             if (epi) y = epi_piece<T, B, VEC>(y, Wp + (r0 + idx / LPR) * B, Ms, idx % LPR);
-        if constexpr (AX3 && DOT) {
+        if constexpr (AX4) {
+            const int64_t o = (r0 + idx / LPR) * B + (idx % LPR) * VEC;
+            y = ax4_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC, Wp ? Wp + o : nullptr,
+                                  Up ? Up + o : nullptr, ca, cc, cd, ce);
+        } else if constexpr (AX3 && DOT) {
             Vec<T, VEC> x;
             y = ax3_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC,
                                   Wp ? Wp + (r0 + idx / LPR) * B + (idx % LPR) * VEC : nullptr, ca, cc, cd, &x);
@@ -1519,7 +1562,7 @@ static int launch_seg_pf(lz_handle *h, int64_t n, const int64_t *rp, const int32
     // profiles/r06h_pf_trace.csv shows both kernels running at once)
     hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, false, 0, false, false, true>), dim3((unsigned)st), dim3(256), 0,
                        h->pf_sg, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, nullptr, nullptr, 0, h->pf_ctl,
-                       T(0), T(0), T(0), nullptr);
+                       T(0), T(0), T(0), nullptr, nullptr, T(0));
     // C = 0: the tile kernel alone on its CUs (the masked launch's own cost);
     // 8 blocks per prefetching CU (4 k CUs per XCD); a band wider than `span`
     // rows gets no X prefetch
@@ -1531,7 +1574,7 @@ static int launch_seg_pf(lz_handle *h, int64_t n, const int64_t *rp, const int32
     const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>(st, (int64_t)h->n_cu * 4));
     hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, false, 1>), dim3(g2), dim3(256), 0, h->pf_sg, n, rp, col, val, X, ldx,
                        nx, Y, ldy, h->longq, parity, nullptr, nullptr, 0, nullptr, T(0), T(0), T(0),
-                       nullptr);
+                       nullptr, nullptr, T(0));
     LZ_HIP_TRY(hipEventRecord(h->ev_pfg, h->pf_sg));
     LZ_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_pfg, 0));
     if (k > 0) {
@@ -1550,17 +1593,18 @@ static int launch_seg_pf(lz_handle *h, int64_t n, const int64_t *rp, const int32
 // up front) -- the long-tile pass runs
 // first, on its own stream, beside the main kernel, which then only skips them.
 template <typename T, int B, int TR, int CAP, bool WIN, bool YCM = false, bool EPI = false, bool AX3 = false,
-          bool DOT = false>
+          bool DOT = false, bool AX4 = false>
 static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, const T *val, const T *X,
                       int64_t ldx, int64_t nx, T *Y, int64_t ldy, const T *Wp = nullptr, const T *Mm = nullptr,
                       int plan_slot = -1, int *slot_out = nullptr, T ca = T(0), T cc = T(0), T cd = T(0),
-                      double *dslab = nullptr)
+                      double *dslab = nullptr, const T *Up = nullptr, T ce = T(0))
 {
     const int64_t st = ceil_div(n, (int64_t)TR);
     LZ_ARG_CHECK(st < (1LL << 31), "too many row tiles");
     LZ_TRY(ensure_longq(h, st));
     h->last_kernel[0] = (CAP == 768 ? LZ_K_SEG768 : CAP == 1024 ? LZ_K_SEG1024 : LZ_K_SEG1536) | (WIN ? LZ_K_WIN : 0) |
-                        (YCM ? LZ_K_YCM : 0) | (EPI ? LZ_K_EPI : 0) | (AX3 ? LZ_K_AX3 : 0) | (DOT ? LZ_K_DOT : 0);
+                        (YCM ? LZ_K_YCM : 0) | (EPI ? LZ_K_EPI : 0) | (AX3 ? LZ_K_AX3 : 0) | (DOT ? LZ_K_DOT : 0) |
+                        (AX4 ? LZ_K_AX4 : 0);
     if (plan_slot >= 0) {
         LZ_ARG_CHECK(plan_slot <= 1 && sizeof(int) * ((size_t)st + 2) <= h->longq_cap, "planned SpMM: no earlier queue");
         if (!h->lstream) {
@@ -1571,13 +1615,13 @@ static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t 
         const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>(st, (int64_t)h->n_cu * 4));
         LZ_HIP_TRY(hipEventRecord(h->ev_lfork, h->stream));
         LZ_HIP_TRY(hipStreamWaitEvent(h->lstream, h->ev_lfork, 0));
-        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI, false, AX3, DOT>), dim3(g2), dim3(256), 0,
+        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI, false, AX3, DOT, AX4>), dim3(g2), dim3(256), 0,
                            h->lstream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, Wp, Mm, 0, nullptr,
-                           ca, cc, cd, dslab);
+                           ca, cc, cd, dslab, Up, ce);
         LZ_HIP_TRY(hipEventRecord(h->ev_ljoin, h->lstream));
-        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI, false, AX3, DOT>), dim3((unsigned)st),
+        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI, false, AX3, DOT, AX4>), dim3((unsigned)st),
                            dim3(256), 0, h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, Wp, Mm,
-                           0, nullptr, ca, cc, cd, dslab);
+                           0, nullptr, ca, cc, cd, dslab, Up, ce);
         LZ_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_ljoin, 0));
         return LZ_OK;
     }
@@ -1610,13 +1654,13 @@ static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t 
 #else
     constexpr int diag = 0;
 #endif
-    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI, false, AX3, DOT>), dim3((unsigned)st), dim3(256),
+    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI, false, AX3, DOT, AX4>), dim3((unsigned)st), dim3(256),
                        0, h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, Wp, Mm, diag, nullptr, ca,
-                       cc, cd, dslab);
+                       cc, cd, dslab, Up, ce);
     const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>(st, (int64_t)h->n_cu * 4));
-    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI, false, AX3, DOT>), dim3(g2), dim3(256), 0,
+    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI, false, AX3, DOT, AX4>), dim3(g2), dim3(256), 0,
                        h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, Wp, Mm, 0, nullptr, ca, cc, cd,
-                       dslab);
+                       dslab, Up, ce);
     return LZ_OK;
 }
 
@@ -1874,6 +1918,58 @@ int spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const in
     LZ_LAUNCH_CHECK();
     return LZ_OK;
 }
+
+// The row-local pass of the two-launch four-term step: Y = a Y + c X + d Z + e U over nb = n b
+// contiguous elements, 64-bit indices; Z == nullptr: d == 0, U == nullptr: e == 0, neither is
+// read then.  The arithmetic of ax4_piece on the stored SpMM row.
+template <typename T>
+__global__ __launch_bounds__(256) void k_ax4_rows(int64_t nb, T a, T c, T d, T e, const T *__restrict__ X,
+                                                  const T *__restrict__ Z, const T *__restrict__ U,
+                                                  T *__restrict__ Y)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nb; i += (int64_t)gridDim.x * 256) {
+        T t = U ? e * U[i] : T(0);
+        if (Z) t = U ? fma(d, Z[i], t) : d * Z[i];
+        Y[i] = fma(a, Y[i], fma(c, X[i], t));
+    }
+}
+
+// Y = a A X + c X + d Z + e U (lz_csr_spmm_axpby4): spmm_axpby's shapes and switch, U in the
+// alignment test.  Fused: k_spmm_seg's AX4 store (last_kernel | LZ_K_AX3 | LZ_K_AX4); fused =
+// false or any other shape: spmm_rm, then k_ax4_rows -- the same bits.
+template <typename T>
+int spmm_axpby4(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                T a, const T *X, T c, T d, const T *Z, T e, const T *U, T *Y, bool fused)
+{
+    if (n <= 0) return LZ_OK;
+    if (d == T(0)) Z = nullptr;
+    if (e == T(0)) U = nullptr;
+    if (fused && ax3_store_ok<T>(n, b, X, Z, Y) && (reinterpret_cast<uintptr_t>(U) & 15) == 0) {
+        constexpr int B = 128 / (int)sizeof(T);
+        const bool wide = (double)nnz > 13.0 * (double)n;
+        const int ev = prof_begin(h, PROF_SPMM);
+        const int rc = wide ? launch_seg<T, B, 48, 1536, false, false, false, true, false, true>(
+                                  h, n, rp, col, val, X, B, n, Y, B, Z, nullptr, -1, nullptr, a, c, d, nullptr, U, e)
+                            : launch_seg<T, B, 48, 768, false, false, false, true, false, true>(
+                                  h, n, rp, col, val, X, B, n, Y, B, Z, nullptr, -1, nullptr, a, c, d, nullptr, U, e);
+        prof_end(h, ev);
+        LZ_TRY(rc);
+        LZ_LAUNCH_CHECK();
+        return LZ_OK;
+    }
+    LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, X, b, n, Y, b));
+    const int64_t nb = n * b;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(nb, (int64_t)256), (int64_t)h->n_cu * 16));
+    hipLaunchKernelGGL((k_ax4_rows<T>), dim3(grid), dim3(256), 0, h->stream, nb, a, c, d, e, X, Z, U, Y);
+    LZ_LAUNCH_CHECK();
+    return LZ_OK;
+}
+
+template int spmm_axpby4<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *, int,
+                                 double, const double *, double, double, const double *, double, const double *,
+                                 double *, bool);
+template int spmm_axpby4<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
+                                float, const float *, float, float, const float *, float, const float *, float *, bool);
 
 // spmm_axpby and the stored Y's column dots (lz_csr_spmm_axpby_dots).  At spmm_axpby's
 // fused shapes the dots leave the same store (DOT): a slab per 48-row tile, folded by

@@ -353,6 +353,49 @@ int lz_block_lanczos_reorth_resume_cheb(lz_handle *h, int64_t n, int64_t nnz, co
                                         int64_t lc, const void *sigma, void *q, void *alpha, void *beta, void *V,
                                         int64_t vstride, void *W, int passes, const lz_cheb *f, void *work);
 
+/* ---------------- Chebyshev series and the windowed filter (interior eigenpairs)
+ * Y = a (A X) + c X + d Z + e U: lz_csr_spmm_axpby with a fourth term, the step of
+ * Clenshaw's recurrence.  X, Z, U, Y: n x b row-major with ld = b; Y distinct from
+ * X, Z and U, Z distinct from X; U may be X or Z.  d == 0 never reads Z and e == 0
+ * never reads U; either may then be NULL (a non-zero coefficient with a NULL block
+ * is LZ_E_ARG).  The coefficients are converted once to the solve's dtype and the
+ * stored row is fma(a, s, fma(c, x, t)) with s the finished SpMM row and t =
+ * fma(d, z, e*u), or d*z (e == 0), or e*u (d == 0), or 0.  lz_csr_spmm_axpby's
+ * fused shapes, with U on 16 bytes too, add the terms at the SpMM's store
+ * (lz_debug_last_kernel: the SpMM id | LZ_K_AX3 | LZ_K_AX4): one read of U more
+ * than lz_csr_spmm_axpby.  Every other shape -- and LZ_AX3=0 -- runs lz_csr_spmm
+ * into Y and then one row-local kernel with the same arithmetic: the same bits. */
+int lz_csr_spmm_axpby4(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                       const void *val, lz_dtype dtype, int b, double a, const void *X, double c, double d,
+                       const void *Z, double e, const void *U, void *Y);
+/* Y = sum_{k=0..degree} gamma_k T_k(Ah) X, Ah = (A - c0) / e, e = (hi - lo) / 2, c0 =
+ * (hi + lo) / 2, by Clenshaw's recurrence b_k = gamma_k X + 2 Ah b_{k+1} - b_{k+2},
+ * Y = gamma_0 X + Ah b_1 - b_2: exactly `degree` SpMMs, the first an
+ * lz_csr_spmm_axpby on X (b_{degree-1}), the others lz_csr_spmm_axpby4 with U = X.
+ * gamma: degree + 1 host doubles (lzh_cheb_window in lz_host.h makes a window's),
+ * 1 <= degree <= 65536; lo < hi finite, and [lo, hi] should enclose the spectrum (the
+ * T_k grow without bound outside it).  X (read only), Y: n x b row-major, ld = b;
+ * work: 2 n b elements (not read on entry); X, Y and work pairwise distinct.  The
+ * buffers {work_0, work_1, Y} rotate so that the last step lands in Y and a step's
+ * output is none of its inputs.  No host synchronisation. */
+int lz_cheb_series_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                         const void *val, lz_dtype dtype, int b, int degree, double lo, double hi,
+                         const double *gamma, const void *X, void *Y, void *work);
+/* lz_block_lanczos_reorth / lz_block_lanczos_reorth_resume on the operator
+ * s(A) = sum_k gamma_k T_k(Ah): every W = A Q_j of the solve becomes
+ * lz_cheb_series_apply (degree, lo, hi, gamma, work as there; work distinct from B,
+ * W and the panel).  alpha, beta and the projected matrix are those of s(A). */
+int lz_block_lanczos_reorth_series(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr,
+                                   const int32_t *col, const void *val, lz_dtype dtype, int b, int m,
+                                   int64_t lc, const void *B, void *q, void *alpha, void *beta, void *V,
+                                   int64_t vstride, void *W, int passes, int degree, double lo, double hi,
+                                   const double *gamma, void *work);
+int lz_block_lanczos_reorth_resume_series(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr,
+                                          const int32_t *col, const void *val, lz_dtype dtype, int b, int r, int m,
+                                          int64_t lc, const void *sigma, void *q, void *alpha, void *beta, void *V,
+                                          int64_t vstride, void *W, int passes, int degree, double lo, double hi,
+                                          const double *gamma, void *work);
+
 /* ------------------------- transpose and normal operator (no reference counterpart)
  * The CSR of A^T, built on the device: output row c (c < n_cols) holds the
  * entries of A whose column is c in the order of their positions in A's
@@ -462,7 +505,7 @@ int lz_debug_last_wf(lz_handle *h, int out[2]);
  * b = 32 fp32 or generic-b solve), out[1]: its last Gram / tall-skinny-product
  * launch (lz_gram, lz_sym_cross_gram, lz_tsmm and the solves that call them);
  * 0: none yet.  SpMM ids: a kernel in the low byte, or-ed with the LZ_K_WIN /
- * LZ_K_YCM / LZ_K_EPI / LZ_K_AX3 / LZ_K_DOT flags; LZ_K_SPMV carries its lanes per row in bits 16+. */
+ * LZ_K_YCM / LZ_K_EPI / LZ_K_AX3 / LZ_K_DOT / LZ_K_AX4 flags; LZ_K_SPMV carries its lanes per row in bits 16+. */
 enum {
     LZ_K_SEG768 = 1,    /* nnz-split tiles, 768-entry stage (128-B rows, <= 13 nnz/row) */
     LZ_K_SEG1536 = 2,   /* ... 1536-entry stage (> 13 nnz/row) */
@@ -478,6 +521,7 @@ enum {
     LZ_K_EPI = 0x400,   /* the beta^2 step's epilogue U = A X - Wp M */
     LZ_K_AX3 = 0x800,   /* lz_csr_spmm_axpby's fused three-term store a A X + c X + d Z */
     LZ_K_DOT = 0x1000,  /* lz_csr_spmm_axpby_dots: the column dots leave the fused store too */
+    LZ_K_AX4 = 0x2000,  /* lz_csr_spmm_axpby4: the fused store's fourth term e U (with LZ_K_AX3) */
     LZ_K_GRAM16 = 1,    /* dense ids: b = 16 MFMA Gram (fp64 and fp32) */
     LZ_K_GRAM32F = 2,   /* b = 32 fp32 MFMA Gram */
     LZ_K_GRAM_GEN = 3,  /* any b, any pitch */

@@ -145,6 +145,12 @@ int lzh_jackson(int M, double *g);
  * mean): sum_k g_k gamma_k mu_k, gamma_0 = (th_a - th_b) / pi, gamma_k = 2 (sin k th_a -
  * sin k th_b) / (k pi), th_x = acos(clamp((x - c0) / e)).  g == NULL: no damping. */
 int lzh_kpm_count(int M, const double *mu, const double *g, double lo, double hi, double a, double b, double *count);
+/* The Chebyshev coefficients of the indicator of the window [a, b] on the enclosure
+ * [lo, hi]: gamma[0 .. M), gamma_k = g_k times the weights lzh_kpm_count applies to the
+ * moments, so that sum_k gamma_k T_k((x - c0) / e) approximates 1 inside [a, b] and 0
+ * outside (lz_cheb_series_apply in lz_hip.h takes them).  M >= 1, lo < hi finite,
+ * lo <= a <= b <= hi; g == NULL: no damping. */
+int lzh_cheb_window(int M, double lo, double hi, double a, double b, const double *g, double *gamma);
 /* The density of states at x[0 .. npts): rho(x) = [g_0 mu_0 + 2 sum_{k>=1} g_k mu_k
  * T_k(xh)] / (pi e sqrt(1 - xh^2)), xh = (x - c0) / e; 0 outside (lo, hi). */
 int lzh_kpm_density(int M, const double *mu, const double *g, double lo, double hi, int npts, const double *x,
