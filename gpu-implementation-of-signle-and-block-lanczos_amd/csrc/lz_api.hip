@@ -290,12 +290,14 @@ static int cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, c
     T *buf[3] = {work, work + n * b, Y};
     const bool fused = ax3_fused();
     auto out = [&](int i) { return buf[((i + 2 - f.degree) % 3 + 3) % 3]; };
-    LZ_TRY(spmm_axpby<T>(h, n, nnz, rp, col, val, b, T(s1 / e), X, T(-c0 * s1 / e), T(0), nullptr, out(1), fused));
+    LZ_TRY(spmm_terms<T>(h, n, nnz, rp, col, val, b, {T(s1 / e), X, T(-c0 * s1 / e), T(0), nullptr}, out(1), nullptr,
+                         fused));
     double sg = s1;
     for (int i = 2; i <= f.degree; ++i) {
         const double sn = 1.0 / (2.0 / s1 - sg);
-        LZ_TRY(spmm_axpby<T>(h, n, nnz, rp, col, val, b, T(2.0 * sn / e), out(i - 1), T(-2.0 * sn * c0 / e),
-                             T(-sg * sn), i == 2 ? X : out(i - 2), out(i), fused));
+        LZ_TRY(spmm_terms<T>(h, n, nnz, rp, col, val, b,
+                             {T(2.0 * sn / e), out(i - 1), T(-2.0 * sn * c0 / e), T(-sg * sn), i == 2 ? X : out(i - 2)},
+                             out(i), nullptr, fused));
         sg = sn;
     }
     return LZ_OK;
@@ -334,16 +336,18 @@ static int cheb_series_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t
     const bool fused = ax3_fused();
     auto out = [&](int i) { return buf[((i + 2 - D) % 3 + 3) % 3]; };
     if (D == 1)
-        return spmm_axpby<T>(h, n, nnz, rp, col, val, b, T(g[1] / e), X, T(g[0] - g[1] * c0 / e), T(0), nullptr, Y,
-                             fused);
-    LZ_TRY(spmm_axpby<T>(h, n, nnz, rp, col, val, b, T(2.0 * g[D] / e), X, T(g[D - 1] - 2.0 * g[D] * c0 / e), T(0),
-                         nullptr, out(1), fused));
+        return spmm_terms<T>(h, n, nnz, rp, col, val, b, {T(g[1] / e), X, T(g[0] - g[1] * c0 / e), T(0), nullptr}, Y,
+                             nullptr, fused);
+    LZ_TRY(spmm_terms<T>(h, n, nnz, rp, col, val, b,
+                         {T(2.0 * g[D] / e), X, T(g[D - 1] - 2.0 * g[D] * c0 / e), T(0), nullptr}, out(1), nullptr, fused));
     for (int i = 2; i <= D; ++i) {
         const int k = D - i;
         const double f = k > 0 ? 2.0 : 1.0;
         const bool noz = i == 2;  // b_{k+2} = gamma_D X
-        LZ_TRY(spmm_axpby4<T>(h, n, nnz, rp, col, val, b, T(f / e), out(i - 1), T(-f * c0 / e), noz ? T(0) : T(-1),
-                              noz ? nullptr : out(i - 2), T(noz ? g[k] - g[D] : g[k]), X, out(i), fused));
+        LZ_TRY(spmm_terms<T>(h, n, nnz, rp, col, val, b,
+                             {T(f / e), out(i - 1), T(-f * c0 / e), noz ? T(0) : T(-1), noz ? nullptr : out(i - 2),
+                              T(noz ? g[k] - g[D] : g[k]), X, true},
+                             out(i), nullptr, fused));
     }
     return LZ_OK;
 }
@@ -2065,22 +2069,36 @@ int lz_normal_apply(lz_handle *h, int64_t n, int64_t p, int64_t nnz, const int64
     });
 }
 
-int lz_csr_spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
-                      lz_dtype dtype, int b, double a, const void *X, double c, double d, const void *Z, void *Y)
+// The term steps' entry points (lz_csr_spmm_axpby, _axpby_dots, _axpby4): their shared checks
+// (want_dots: the call returns dots and needs n >= 1; the three-term ones pass e = 0), then
+// spmm_terms in the dtype
+static int terms_entry(lz_handle *h, int64_t n, bool want_dots, int64_t nnz, const int64_t *rp, const int32_t *col,
+                       const void *val, lz_dtype dtype, int b, double a, const void *X, double c, double d, const void *Z,
+                       double e, const void *U, bool four, void *Y, double *dots)
 {
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(n, nnz, rp, col, val));
     LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(b >= 1 && b <= kMaxB, "b in [1,64]");
+    LZ_ARG_CHECK((n >= 1 || !want_dots) && b >= 1 && b <= kMaxB, "b in [1,64] (and n >= 1 with dots)");
     LZ_ARG_CHECK(X && Y && (Z || d == 0.0), "X/Y NULL, or Z NULL with d != 0");
+    LZ_ARG_CHECK(U || e == 0.0, "U NULL with e != 0");
+    LZ_ARG_CHECK(dots || !want_dots, "dots is NULL");
     const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && (d == 0.0 || (blocks_apart(Z, nb, Y, nb, es) && Z != X)),
-                 "X, Z and Y must be pairwise distinct (no in-place form)");
+    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && (d == 0.0 || (blocks_apart(Z, nb, Y, nb, es) && Z != X)) &&
+                     (e == 0.0 || blocks_apart(U, nb, Y, nb, es)),
+                 "Y must be distinct from X, Z and U, and Z from X (no in-place form)");
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        return spmm_axpby<T>(h, n, nnz, rp, col, (const T *)val, b, (T)a, (const T *)X, (T)c, (T)d, (const T *)Z,
-                             (T *)Y, ax3_fused());
+        return spmm_terms<T>(h, n, nnz, rp, col, (const T *)val, b,
+                             {(T)a, (const T *)X, (T)c, (T)d, (const T *)Z, (T)e, (const T *)U, four}, (T *)Y, dots,
+                             ax3_fused(), ax3dot_fused());
     });
+}
+
+int lz_csr_spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                      lz_dtype dtype, int b, double a, const void *X, double c, double d, const void *Z, void *Y)
+{
+    return terms_entry(h, n, false, nnz, rp, col, val, dtype, b, a, X, c, d, Z, 0.0, nullptr, false, Y, nullptr);
 }
 
 int lz_cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
@@ -2118,20 +2136,7 @@ int lz_csr_spmm_axpby_dots(lz_handle *h, int64_t n, int64_t nnz, const int64_t *
                            lz_dtype dtype, int b, double a, const void *X, double c, double d, const void *Z, void *Y,
                            double *dots)
 {
-    LZ_HANDLE_CHECK(h);
-    LZ_TRY(check_csr(n, nnz, rp, col, val));
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= kMaxB, "n >= 1, b in [1,64]");
-    LZ_ARG_CHECK(X && Y && (Z || d == 0.0), "X/Y NULL, or Z NULL with d != 0");
-    LZ_ARG_CHECK(dots != nullptr, "dots is NULL");
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && (d == 0.0 || (blocks_apart(Z, nb, Y, nb, es) && Z != X)),
-                 "X, Z and Y must be pairwise distinct (no in-place form)");
-    return by_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        return spmm_axpby_dots<T>(h, n, nnz, rp, col, (const T *)val, b, (T)a, (const T *)X, (T)c, (T)d, (const T *)Z,
-                                  (T *)Y, dots, ax3_fused(), ax3dot_fused());
-    });
+    return terms_entry(h, n, true, nnz, rp, col, val, dtype, b, a, X, c, d, Z, 0.0, nullptr, false, Y, dots);
 }
 
 int lz_cheb_moments(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
@@ -2289,21 +2294,7 @@ int lz_csr_spmm_axpby4(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, 
                        lz_dtype dtype, int b, double a, const void *X, double c, double d, const void *Z, double e,
                        const void *U, void *Y)
 {
-    LZ_HANDLE_CHECK(h);
-    LZ_TRY(check_csr(n, nnz, rp, col, val));
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(b >= 1 && b <= kMaxB, "b in [1,64]");
-    LZ_ARG_CHECK(X && Y && (Z || d == 0.0), "X/Y NULL, or Z NULL with d != 0");
-    LZ_ARG_CHECK(U || e == 0.0, "U NULL with e != 0");
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && (d == 0.0 || (blocks_apart(Z, nb, Y, nb, es) && Z != X)) &&
-                     (e == 0.0 || blocks_apart(U, nb, Y, nb, es)),
-                 "Y must be distinct from X, Z and U, and Z from X (no in-place form)");
-    return by_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        return spmm_axpby4<T>(h, n, nnz, rp, col, (const T *)val, b, (T)a, (const T *)X, (T)c, (T)d, (const T *)Z, (T)e,
-                              (const T *)U, (T *)Y, ax3_fused());
-    });
+    return terms_entry(h, n, false, nnz, rp, col, val, dtype, b, a, X, c, d, Z, e, U, true, Y, nullptr);
 }
 
 int lz_cheb_series_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,

@@ -9,26 +9,30 @@ template <typename T>
 int spmm_rm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
             const T *X, int64_t ldx, int64_t nx, T *Y, int64_t ldy,
             bool ycm = false);  // nx: rows of X; ycm: Y column-major (leading dimension ldy), b >= 2
-// Y = a A X + c X + d Z, square operator, X / Z / Y n x b row-major with ld = b and
-// pairwise distinct; d == 0 never reads Z.  128-B rows under 2 GiB: fused into
-// k_spmm_seg's store (last_kernel | LZ_K_AX3); else, or fused = false: spmm_rm,
-// then one row-local kernel
+// The terms of Y = a A X + c X + d Z + e U: X / Z / U / Y n x b row-major with ld = b, Y
+// distinct from the others and Z from X (U may be X or Z); d == 0 never reads Z, e == 0
+// never reads U.  four: the four-term step (lz_csr_spmm_axpby4), whatever e is; without
+// it e and U are ignored.
 template <typename T>
-int spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
-               T a, const T *X, T c, T d, const T *Z, T *Y, bool fused = true);
-// spmm_axpby, and dots[0 .. b) = sum_i Y[i][c]^2, dots[b .. 2b) = sum_i Y[i][c] X[i][c] of the
-// stored Y (device, fp64, fixed summation order).  fused && fused_dot at spmm_axpby's fused
-// shapes: the dots leave k_spmm_seg's store too (last_kernel | LZ_K_AX3 | LZ_K_DOT), a slab
-// per tile in h->dots_ws; else spmm_axpby(fused), then col_dots.  n >= 1.
+struct SpmmTerms {
+    T a;
+    const T *X;
+    T c, d;
+    const T *Z;
+    T e = T(0);
+    const T *U = nullptr;
+    bool four = false;
+};
+// Y = those terms on a square operator.  128-B rows under 2 GiB, every block read on 16
+// bytes: they leave k_spmm_seg's store (SegStore::Terms3, last_kernel | LZ_K_AX3; four:
+// Terms4, | LZ_K_AX4); else, or fused = false: spmm_rm, then one row-local kernel.
+// dots != nullptr: also dots[0 .. b) = sum_i Y[i][c]^2, dots[b .. 2b) = sum_i Y[i][c] X[i][c]
+// of the stored Y (device, fp64, fixed summation order; n >= 1).  A three-term step at the
+// fused shapes with fused_dot: the dots leave the store too (Terms3Dots, | LZ_K_DOT), a
+// slab per tile in h->dots_ws; else col_dots afterwards.
 template <typename T>
-int spmm_axpby_dots(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
-                    T a, const T *X, T c, T d, const T *Z, T *Y, double *dots, bool fused = true,
-                    bool fused_dot = true);
-// Y = a A X + c X + d Z + e U (lz_csr_spmm_axpby4): spmm_axpby's shapes and switch with U on
-// 16 bytes too (last_kernel | LZ_K_AX3 | LZ_K_AX4); U may be X or Z; e == 0 never reads U
-template <typename T>
-int spmm_axpby4(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
-                T a, const T *X, T c, T d, const T *Z, T e, const T *U, T *Y, bool fused = true);
+int spmm_terms(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+               SpmmTerms<T> t, T *Y, double *dots = nullptr, bool fused = true, bool fused_dot = true);
 template <typename T>
 int spmm_cm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
             const T *X, int64_t ldx, int64_t nx, T *Y, int64_t ldy);  // nx: rows of X

@@ -147,7 +147,7 @@ template int col_dots<double>(lz_handle *, int64_t, int, const double *, const d
 template int col_dots<float>(lz_handle *, int64_t, int, const float *, const float *, double *, bool);
 
 // lz_cheb_moments: t_0 = X0, t_1 = Ah t_0, t_{k+1} = 2 Ah t_k - t_{k-1}, one
-// spmm_axpby_dots each; t_k (k >= 1) lives in buffer (k - 1) mod 3 of work, so a
+// spmm_terms with dots each; t_k (k >= 1) lives in buffer (k - 1) mod 3 of work, so a
 // step's output is neither of its inputs.  The slab workspace is reserved
 // before the first step: no host synchronisation between steps.
 template <typename T>
@@ -158,11 +158,11 @@ int cheb_moments(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const 
     LZ_TRY(dots_reserve(h, n, b));
     auto t = [&](int k) { return k == 0 ? X0 : work + (int64_t)((k - 1) % 3) * n * b; };
     LZ_TRY(col_dots<T>(h, n, b, X0, X0, dots, true));
-    LZ_TRY(spmm_axpby_dots<T>(h, n, nnz, rp, col, val, b, T(1.0 / e), X0, T(-c0 / e), T(0), nullptr,
-                              const_cast<T *>(t(1)), dots + 2 * b, fused, fused_dot));
+    LZ_TRY(spmm_terms<T>(h, n, nnz, rp, col, val, b, {T(1.0 / e), X0, T(-c0 / e), T(0), nullptr}, const_cast<T *>(t(1)),
+                         dots + 2 * b, fused, fused_dot));
     for (int k = 1; k < K; ++k)
-        LZ_TRY(spmm_axpby_dots<T>(h, n, nnz, rp, col, val, b, T(2.0 / e), t(k), T(-2.0 * c0 / e), T(-1), t(k - 1),
-                                  const_cast<T *>(t(k + 1)), dots + (int64_t)(k + 1) * 2 * b, fused, fused_dot));
+        LZ_TRY(spmm_terms<T>(h, n, nnz, rp, col, val, b, {T(2.0 / e), t(k), T(-2.0 * c0 / e), T(-1), t(k - 1)},
+                             const_cast<T *>(t(k + 1)), dots + (int64_t)(k + 1) * 2 * b, fused, fused_dot));
     return LZ_OK;
 }
 template int cheb_moments<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *, int,

@@ -356,11 +356,10 @@ __global__ __launch_bounds__(256) void k_spmm_buf(int64_t n, const int64_t *__re
 // window goes to the long-tile queue, whose kernel then gathers with 64-bit
 // addresses.  Banded operators of any size keep the buffer-addressed gather
 // (BASELINE config C4: 40M rows on one GPU).
-// YCM: Y is column-major (element (r, c) at r + c*ldy, the reference's
-// Dense_matrix layout): the finished Y tile leaves column by column, nrows
-// contiguous elements per column (the caller transposed X in).
-// U row piece = Y piece - Wp[row] . M[:, piece] (k in order, one fma chain per
-// element): the C5 beta^2 epilogue of k_spmm_seg (EPI).
+// What a launch does with its finished rows is one SegStore (below, at the kernel).
+
+// U row piece = Y piece - W_{j-1}[row] . M[:, piece] (k in order, one fma chain per
+// element): the C5 beta^2 epilogue of k_spmm_seg (SegStore::Beta2).
 // The B / VEC = 8 lanes of a row (consecutive lanes) each load one 16-B piece
 // of the row and pass it round by lane shuffles: one load per piece, not B / 4.
 template <typename T, int B, int VEC>
@@ -386,63 +385,48 @@ __device__ __forceinline__ Vec<T, VEC> epi_piece(Vec<T, VEC> y, const T *__restr
     return y;
 }
 
-// Three-term row piece (AX3, lz_csr_spmm_axpby): from the finished SpMM piece s
-// of a row, a s + c x + d z with x, z the lane's own 16-B pieces of X[row] and
-// Z[row] (zrow == nullptr: d == 0, Z is never read).  X[row] is the piece the
-// diagonal entry gathered, so it usually comes from cache; Z is streamed once:
-// a non-temporal load, as epi_piece loads W.  xo (DOT): the x piece, for the
-// column dots.
-template <typename T, int VEC>
-__device__ __forceinline__ Vec<T, VEC> ax3_piece(Vec<T, VEC> s, const T *__restrict__ xrow,
-                                                 const T *__restrict__ zrow, T a, T c, T d,
-                                                 Vec<T, VEC> *xo = nullptr)
-{
-    static_assert(sizeof(T) * VEC == 16, "128-B rows: 16-B pieces");
-    const Vec<T, VEC> x = ldv<T, VEC>(xrow);
-    if (xo) *xo = x;
-    Vec<T, VEC> z;
-    if (zrow) {
-        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-        const u32x4 u = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(zrow));
-        __builtin_memcpy(&z, &u, 16);
-    }
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) s.v[i] = fma(a, s.v[i], fma(c, x.v[i], zrow ? d * z.v[i] : T(0)));
-    return s;
-}
-
-// Four-term row piece (AX4, lz_csr_spmm_axpby4): a s + c x + d z + e u, u the lane's
-// own 16-B piece of U[row], streamed once like z (non-temporal; U may be X or Z: all
-// three are only read).  One arithmetic order, which k_ax4_rows repeats on the stored
-// row: fma(a, s, fma(c, x, t)) with t = fma(d, z, e u), or d z (urow == nullptr: e == 0),
-// or e u (zrow == nullptr: d == 0), or 0 -- without U it is ax3_piece's.
-template <typename T, int VEC>
-__device__ __forceinline__ Vec<T, VEC> ax4_piece(Vec<T, VEC> s, const T *__restrict__ xrow,
-                                                 const T *__restrict__ zrow, const T *__restrict__ urow, T a,
-                                                 T c, T d, T e)
+// Term row piece (the term stores, lz_csr_spmm_axpby / _axpby_dots / _axpby4): from the
+// finished SpMM piece s of a row, a s + c x + d z + e u with x, z, u the lane's own 16-B
+// pieces of X[row], Z[row] and U[row].  X[row] is the piece the diagonal entry gathered,
+// so it usually comes from cache; Z and U are streamed once: non-temporal loads, as
+// epi_piece loads W (U may be X or Z: all three are only read).  One arithmetic order,
+// which k_term_rows repeats on the stored row: fma(a, s, fma(c, x, t)) with
+// t = fma(d, z, e u), or d z (e == 0), or e u (d == 0), or 0.  Z, U: the blocks (ld = B),
+// the pieces at element o.  The tests are uniform over the launch, on the block, not on a
+// lane's row pointer: Z == nullptr exactly when d == 0, and U through e (spmm_terms: U ==
+// nullptr exactly when e == 0); a term whose test fails is never read.  (A test on U itself
+// keeps one more flag live across the MODE 1 gather: 100 VGPRs for 94 and a wave per SIMD
+// less at fp64.)  HAS_U = false (the three-term stores): no U load and no branch for it.
+// xo (Terms3Dots): the x piece, for the column dots.
+template <typename T, int VEC, bool HAS_U>
+__device__ __forceinline__ Vec<T, VEC> term_piece(Vec<T, VEC> s, const T *__restrict__ xrow, const T *__restrict__ Z,
+                                                  const T *__restrict__ U, int64_t o, T a, T c, T d, T e,
+                                                  Vec<T, VEC> *xo = nullptr)
 {
     static_assert(sizeof(T) * VEC == 16, "128-B rows: 16-B pieces");
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const bool hu = HAS_U && e != T(0), hz = Z != nullptr;
     const Vec<T, VEC> x = ldv<T, VEC>(xrow);
+    if (xo) *xo = x;
     Vec<T, VEC> z, u;
-    if (zrow) {
-        const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(zrow));
+    if (hz) {
+        const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(Z + o));
         __builtin_memcpy(&z, &r, 16);
     }
-    if (urow) {
-        const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(urow));
+    if (hu) {
+        const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(U + o));
         __builtin_memcpy(&u, &r, 16);
     }
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
-        T t = urow ? e * u.v[i] : T(0);
-        if (zrow) t = urow ? fma(d, z.v[i], t) : d * z.v[i];
+        T t = hu ? e * u.v[i] : T(0);
+        if (hz) t = hu ? fma(d, z.v[i], t) : d * z.v[i];
         s.v[i] = fma(a, s.v[i], fma(c, x.v[i], t));
     }
     return s;
 }
 
-// Column dots at the fused store (DOT, lz_csr_spmm_axpby_dots): a lane's running
+// Column dots at the fused store (Terms3Dots, lz_csr_spmm_axpby_dots): a lane's running
 // y.y and y.x of the pieces it stores -- always the same 16-B column piece, since
 // the store loops step by 256 lanes and a row has 8 -- in fp64 for both dtypes
 // (an fp32 product is exact there).
@@ -516,31 +500,81 @@ __device__ __forceinline__ int xcc_id()
     return (int)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 7u);  // HW_REG_XCC_ID
 }
 
-template <typename T, int B, int TR, int CAP, bool WIN, int MODE, bool YCM = false, bool EPI = false, bool PF = false,
-          bool AX3 = false, bool DOT = false, bool AX4 = false>
+// What k_spmm_seg does with a finished row y = (A X)[row], one policy per launch:
+//   Rows        Y[row] = y, row-major.
+//   ColMajor    Y column-major (element (r, c) at r + c*ldy, the reference's Dense_matrix
+//               layout): the finished tile leaves column by column, nrows contiguous
+//               elements per column (the caller transposed X in).
+//   Beta2       b = 32 fp32, the C5 Q-free step in its beta^2 form: Y[row] = y - Wprev[row] M
+//               (Wprev = W_{j-1}, M = beta_{j-1}^-1 G_j, 32 x 32 in LDS), epi_piece;
+//               Wprev == nullptr (the solve's first step): the plain row.
+//   Terms3      lz_csr_spmm_axpby (square operator, ldx = ldy = B): Y[row] = a y + c X[row]
+//               + d Z[row] (Z == nullptr when d == 0), term_piece.
+//   Terms3Dots  lz_csr_spmm_axpby_dots: Terms3, and the column dots of the stored rows with
+//               themselves and with X's, one slab of 2 B doubles per tile at dots + tile * 2 B,
+//               written by the block that stores the tile: the MODE 0 block, or, for a
+//               queued tile, the MODE 1 block that draws it (a slab per tile, not per MODE 1
+//               block: the queue's order is the order of the MODE 0 blocks' atomics and
+//               differs from run to run, the tiles do not).
+//   Terms4      lz_csr_spmm_axpby4: Terms3 and one more term, e U[row] (U == nullptr when
+//               e == 0; it may be X or Z).
+// Only Rows and ColMajor have windowed (WIN) launches; only Rows the diagnostic build's PF.
+enum class SegStore { Rows, ColMajor, Beta2, Terms3, Terms3Dots, Terms4 };
+
+constexpr bool seg_terms(SegStore st)
+{
+    return st == SegStore::Terms3 || st == SegStore::Terms3Dots || st == SegStore::Terms4;
+}
+
+// the store's bits of lz_debug_last_kernel's SpMM word
+constexpr int seg_store_bits(SegStore st)
+{
+    return (st == SegStore::ColMajor ? LZ_K_YCM : 0) | (st == SegStore::Beta2 ? LZ_K_EPI : 0) |
+           (seg_terms(st) ? LZ_K_AX3 : 0) | (st == SegStore::Terms3Dots ? LZ_K_DOT : 0) |
+           (st == SegStore::Terms4 ? LZ_K_AX4 : 0);
+}
+
+// What the stores read or write besides Y; a field is dead in the launches of the other stores
+template <typename T>
+struct SegOperands {
+    const T *Wprev = nullptr, *M = nullptr;  // Beta2
+    const T *Z = nullptr, *U = nullptr;      // the term stores (U: Terms4)
+    T a = T(0), c = T(0), d = T(0), e = T(0);
+    double *dots = nullptr;                  // Terms3Dots: the tiles' slabs
+};
+
+// A finished 16-B piece (piece pc of row `row`) becomes the piece to store: the one place
+// the store policies differ per piece, for both store loops of k_spmm_seg.  epi, Ms: the
+// kernel's runtime Beta2 test and its LDS copy of M; dacc: the lane's running dots
+// (Terms3Dots).  In place, on the loop's own y: with y passed and returned by value the
+// Beta2 long-tile kernel is scheduled to 118 VGPRs instead of 112.  (The operands' pointers
+// reach epi_piece and term_piece through their __restrict__ parameters, as the kernel's
+// own pointer arguments did: members of a by-value struct carry no such qualifier.)
+template <SegStore ST, typename T, int B, int VEC>
+__device__ __forceinline__ void seg_store_piece(Vec<T, VEC> &y, int64_t row, int pc, const T *X, int64_t ldx,
+                                                const SegOperands<T> &ops, bool epi, const T *Ms,
+                                                DotAcc<T, VEC> &dacc)
+{
+    if constexpr (ST == SegStore::Beta2) {
+        if (epi) y = epi_piece<T, B, VEC>(y, ops.Wprev + row * B, Ms, pc);
+    } else if constexpr (seg_terms(ST)) {
+        [[maybe_unused]] Vec<T, VEC> x;
+        y = term_piece<T, VEC, ST == SegStore::Terms4>(y, X + row * ldx + pc * VEC, ops.Z, ops.U, row * B + pc * VEC,
+                                                       ops.a, ops.c, ops.d, ops.e,
+                                                       ST == SegStore::Terms3Dots ? &x : nullptr);
+        if constexpr (ST == SegStore::Terms3Dots) dacc.add(y, x);
+    }
+}
+
+template <typename T, int B, int TR, int CAP, bool WIN, int MODE, SegStore ST = SegStore::Rows, bool PF = false>
 __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__restrict__ rp,
                                                   const int32_t *__restrict__ col,
                                                   const T *__restrict__ val,
                                                   const T *__restrict__ X, int64_t ldx, int64_t nx,
                                                   T *__restrict__ Y, int64_t ldy, int *__restrict__ longq,
-                                                  int parity, const T *__restrict__ Wp, const T *__restrict__ Mm,
-                                                  int diag, int *__restrict__ pfc, T ca, T cc, T cd,
-                                                  double *__restrict__ dslab, const T *__restrict__ Up, T ce)
+                                                  int parity, const SegOperands<T> ops, int diag,
+                                                  int *__restrict__ pfc)
 {
-    // AX3 (lz_csr_spmm_axpby; square operator, ldx = ldy = B): the stored row is
-    // ca Y + cc X[row] + cd Wp[row] (Wp: Z, nullptr when cd == 0), ax3_piece at
-    // both store sites; ca, cc, cd are unused otherwise.
-    // DOT (lz_csr_spmm_axpby_dots; with AX3 only): the column dots of the stored
-    // rows with themselves and with X's, one slab of 2 B doubles per tile at
-    // dslab + tile * 2 B, written by the block that stores the tile: the MODE 0
-    // block, or, for a queued tile, the MODE 1 block that draws it (a slab per
-    // tile, not per MODE 1 block: the queue's order is the order of the MODE 0
-    // blocks' atomics and differs from run to run, the tiles do not).
-    // AX4 (lz_csr_spmm_axpby4; with AX3 only, not with DOT): one more term, ce Up[row] (Up: U,
-    // nullptr when ce == 0; it may be X or Wp), ax4_piece at both store sites; Up and ce are
-    // unused otherwise.
-    static_assert(!DOT || (AX3 && !WIN && !YCM && !EPI && !PF), "DOT: the fused three-term store only");
-    static_assert(!AX4 || (AX3 && !DOT && !WIN && !YCM && !EPI && !PF), "AX4: the fused three-term store only");
     // MODE 0: tiles whose run exceeds the stage (or, WIN, whose columns exceed
     //         the window) are queued (longq[0] = count, longq[1..] = tile ids)
     //         for MODE 1, so their code path costs the main kernel no registers;
@@ -562,13 +596,13 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
     __shared__ Vec<T, VEC> yt[TR][LPR];      // the tile's finished rows
     __shared__ Vec<T, VEC> head[G][LPR];     // a group's piece of a row begun in an earlier slice
     __shared__ int32_t cmin, cmax;           // WIN: the tile's column range
-    // EPI (b = 32 fp32, the C5 Q-free step in its beta^2 form): the stored row
-    // is U = Y - Wp M (Wp: W_{j-1}, M = beta_{j-1}^-1 G_j, 32 x 32 in LDS)
-    __shared__ T Ms[EPI ? B * B : 1];
+    __shared__ T Ms[ST == SegStore::Beta2 ? B * B : 1];  // Beta2: M
     const int tid = threadIdx.x;
-    const bool epi = EPI && Wp != nullptr;
-    if (epi)
+    const bool epi = ST == SegStore::Beta2 && ops.Wprev != nullptr;
+    if (epi) {
+        const T *Mm = ops.M;
         for (int e = tid; e < B * B; e += 256) Ms[e] = Mm[e];  // visible after the staging barriers
+    }
     const int gi = tid / LPR, p = tid % LPR;
     const uint32_t rowb = (uint32_t)(ldx * sizeof(T)), lane_off = p * VEC * sizeof(T);
     Vec<T, VEC> zero;
@@ -679,33 +713,20 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
                 }
             }
             __syncthreads();
-            if constexpr (YCM) {
+            if constexpr (ST == SegStore::ColMajor) {
                 store_tile_cm<T>(Y, r0, nrows, B, ldy, [&](int r, int c) { return yt[r][c / VEC].v[c % VEC]; });
             } else {
                 [[maybe_unused]] DotAcc<T, VEC> dacc;
-                if constexpr (DOT) dacc.clear();
+                if constexpr (ST == SegStore::Terms3Dots) dacc.clear();
                 for (int idx = tid; idx < nrows * LPR; idx += 256) {
                     Vec<T, VEC> y = yt[idx / LPR][idx % LPR];
-                    if constexpr (EPI)
-                        if (epi) y = epi_piece<T, B, VEC>(y, Wp + (r0 + idx / LPR) * B, Ms, idx % LPR);
-                    if constexpr (AX4) {
-                        const int64_t o = (r0 + idx / LPR) * B + (idx % LPR) * VEC;
-                        y = ax4_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC, Wp ? Wp + o : nullptr,
-                                              Up ? Up + o : nullptr, ca, cc, cd, ce);
-                    } else if constexpr (AX3 && DOT) {
-                        Vec<T, VEC> x;
-                        y = ax3_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC,
-                                              Wp ? Wp + (r0 + idx / LPR) * B + (idx % LPR) * VEC : nullptr, ca, cc, cd,
-                                              &x);
-                        dacc.add(y, x);
-                    } else if constexpr (AX3)
-                        y = ax3_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC,
-                                              Wp ? Wp + (r0 + idx / LPR) * B + (idx % LPR) * VEC : nullptr, ca, cc, cd);
+                    seg_store_piece<ST, T, B, VEC>(y, r0 + idx / LPR, idx % LPR, X, ldx, ops, epi, Ms, dacc);
                     stv<T, VEC>(Y + (r0 + idx / LPR) * ldy + (idx % LPR) * VEC, y);
                 }
-                if constexpr (DOT) {  // (red: read here, next written after the next tile's barriers)
+                if constexpr (ST == SegStore::Terms3Dots) {  // (red: read here, next written after the next
+                                                             // tile's barriers)
                     __shared__ double red[8 * B];
-                    dot_slab<T, B, VEC>(dacc, red, dslab + (int64_t)longq[2 + qi] * (2 * B));
+                    dot_slab<T, B, VEC>(dacc, red, ops.dots + (int64_t)longq[2 + qi] * (2 * B));
                 }
             }
         }
@@ -913,30 +934,17 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
         yt[r][p] = sum;
     }
     __syncthreads();
-    if constexpr (YCM) {
+    if constexpr (ST == SegStore::ColMajor) {
         store_tile_cm<T>(Y, r0, nrows, B, ldy, [&](int r, int c) { return yt[r][c / VEC].v[c % VEC]; });
         return;
     }
     [[maybe_unused]] DotAcc<T, VEC> dacc;
-    if constexpr (DOT) dacc.clear();
+    if constexpr (ST == SegStore::Terms3Dots) dacc.clear();
     for (int idx = tid; idx < nrows * LPR; idx += 256) {
         if (ry + idx / LPR >= n) break;  // (diag only: a Y tile shorter than the tile read)
         T *dst = Y + (ry + idx / LPR) * ldy + (idx % LPR) * VEC;
         Vec<T, VEC> y = yt[idx / LPR][idx % LPR];
-        if constexpr (EPI)
-            if (epi) y = epi_piece<T, B, VEC>(y, Wp + (r0 + idx / LPR) * B, Ms, idx % LPR);
-        if constexpr (AX4) {
-            const int64_t o = (r0 + idx / LPR) * B + (idx % LPR) * VEC;
-            y = ax4_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC, Wp ? Wp + o : nullptr,
-                                  Up ? Up + o : nullptr, ca, cc, cd, ce);
-        } else if constexpr (AX3 && DOT) {
-            Vec<T, VEC> x;
-            y = ax3_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC,
-                                  Wp ? Wp + (r0 + idx / LPR) * B + (idx % LPR) * VEC : nullptr, ca, cc, cd, &x);
-            dacc.add(y, x);
-        } else if constexpr (AX3)
-            y = ax3_piece<T, VEC>(y, X + (r0 + idx / LPR) * ldx + (idx % LPR) * VEC,
-                                  Wp ? Wp + (r0 + idx / LPR) * B + (idx % LPR) * VEC : nullptr, ca, cc, cd);
+        seg_store_piece<ST, T, B, VEC>(y, r0 + idx / LPR, idx % LPR, X, ldx, ops, epi, Ms, dacc);
         if constexpr (sizeof(T) * VEC == 16) {
             typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
             u32x4 u;
@@ -946,9 +954,9 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
             stv<T, VEC>(dst, y);
         }
     }
-    if constexpr (DOT) {
+    if constexpr (ST == SegStore::Terms3Dots) {
         __shared__ double red[8 * B];
-        dot_slab<T, B, VEC>(dacc, red, dslab + (r0 / TR) * (2 * B));
+        dot_slab<T, B, VEC>(dacc, red, ops.dots + (r0 / TR) * (2 * B));
     }
     }  // MODE 0
 }
@@ -1560,9 +1568,8 @@ static int launch_seg_pf(lz_handle *h, int64_t n, const int64_t *rp, const int32
     if (k > 0) LZ_HIP_TRY(hipStreamWaitEvent(h->pf_sp, h->ev_pff, 0));
     // the tile kernel first (the two masked streams have queues of their own:
     // profiles/r06h_pf_trace.csv shows both kernels running at once)
-    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, false, 0, false, false, true>), dim3((unsigned)st), dim3(256), 0,
-                       h->pf_sg, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, nullptr, nullptr, 0, h->pf_ctl,
-                       T(0), T(0), T(0), nullptr, nullptr, T(0));
+    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, false, 0, SegStore::Rows, true>), dim3((unsigned)st), dim3(256), 0,
+                       h->pf_sg, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, SegOperands<T>{}, 0, h->pf_ctl);
     // C = 0: the tile kernel alone on its CUs (the masked launch's own cost);
     // 8 blocks per prefetching CU (4 k CUs per XCD); a band wider than `span`
     // rows gets no X prefetch
@@ -1573,8 +1580,7 @@ static int launch_seg_pf(lz_handle *h, int64_t n, const int64_t *rp, const int32
                            (int64_t)h->pf_band);
     const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>(st, (int64_t)h->n_cu * 4));
     hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, false, 1>), dim3(g2), dim3(256), 0, h->pf_sg, n, rp, col, val, X, ldx,
-                       nx, Y, ldy, h->longq, parity, nullptr, nullptr, 0, nullptr, T(0), T(0), T(0),
-                       nullptr, nullptr, T(0));
+                       nx, Y, ldy, h->longq, parity, SegOperands<T>{}, 0, nullptr);
     LZ_HIP_TRY(hipEventRecord(h->ev_pfg, h->pf_sg));
     LZ_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_pfg, 0));
     if (k > 0) {
@@ -1592,19 +1598,16 @@ static int launch_seg_pf(lz_handle *h, int64_t n, const int64_t *rp, const int32
 // (count slot plan_slot, *slot_out of that call, or a list spmm_b2_plan made
 // up front) -- the long-tile pass runs
 // first, on its own stream, beside the main kernel, which then only skips them.
-template <typename T, int B, int TR, int CAP, bool WIN, bool YCM = false, bool EPI = false, bool AX3 = false,
-          bool DOT = false, bool AX4 = false>
+template <typename T, int B, int TR, int CAP, bool WIN, SegStore ST>
 static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, const T *val, const T *X,
-                      int64_t ldx, int64_t nx, T *Y, int64_t ldy, const T *Wp = nullptr, const T *Mm = nullptr,
-                      int plan_slot = -1, int *slot_out = nullptr, T ca = T(0), T cc = T(0), T cd = T(0),
-                      double *dslab = nullptr, const T *Up = nullptr, T ce = T(0))
+                      int64_t ldx, int64_t nx, T *Y, int64_t ldy, const SegOperands<T> &ops, int plan_slot,
+                      int *slot_out)
 {
     const int64_t st = ceil_div(n, (int64_t)TR);
     LZ_ARG_CHECK(st < (1LL << 31), "too many row tiles");
     LZ_TRY(ensure_longq(h, st));
     h->last_kernel[0] = (CAP == 768 ? LZ_K_SEG768 : CAP == 1024 ? LZ_K_SEG1024 : LZ_K_SEG1536) | (WIN ? LZ_K_WIN : 0) |
-                        (YCM ? LZ_K_YCM : 0) | (EPI ? LZ_K_EPI : 0) | (AX3 ? LZ_K_AX3 : 0) | (DOT ? LZ_K_DOT : 0) |
-                        (AX4 ? LZ_K_AX4 : 0);
+                        seg_store_bits(ST);
     if (plan_slot >= 0) {
         LZ_ARG_CHECK(plan_slot <= 1 && sizeof(int) * ((size_t)st + 2) <= h->longq_cap, "planned SpMM: no earlier queue");
         if (!h->lstream) {
@@ -1615,18 +1618,16 @@ static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t 
         const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>(st, (int64_t)h->n_cu * 4));
         LZ_HIP_TRY(hipEventRecord(h->ev_lfork, h->stream));
         LZ_HIP_TRY(hipStreamWaitEvent(h->lstream, h->ev_lfork, 0));
-        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI, false, AX3, DOT, AX4>), dim3(g2), dim3(256), 0,
-                           h->lstream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, Wp, Mm, 0, nullptr,
-                           ca, cc, cd, dslab, Up, ce);
+        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, ST>), dim3(g2), dim3(256), 0, h->lstream, n, rp, col, val,
+                           X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, ops, 0, nullptr);
         LZ_HIP_TRY(hipEventRecord(h->ev_ljoin, h->lstream));
-        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI, false, AX3, DOT, AX4>), dim3((unsigned)st),
-                           dim3(256), 0, h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, Wp, Mm,
-                           0, nullptr, ca, cc, cd, dslab, Up, ce);
+        hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, ST>), dim3((unsigned)st), dim3(256), 0, h->stream, n, rp,
+                           col, val, X, ldx, nx, Y, ldy, h->longq, 2 + plan_slot, ops, 0, nullptr);
         LZ_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_ljoin, 0));
         return LZ_OK;
     }
 #ifdef LZ_DIAG
-    if constexpr (!WIN && !YCM && !EPI && !AX3) {
+    if constexpr (!WIN && ST == SegStore::Rows) {
         int k = 0, C = 8, D = 96, span = 65536;
         if (pf_config(&k, &C, &D, &span) && (k > 0 || C == 0))
             return launch_seg_pf<T, B, TR, CAP>(h, n, rp, col, val, X, ldx, nx, Y, ldy, k, C, D, span);
@@ -1654,14 +1655,36 @@ static int launch_seg(lz_handle *h, int64_t n, const int64_t *rp, const int32_t 
 #else
     constexpr int diag = 0;
 #endif
-    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, YCM, EPI, false, AX3, DOT, AX4>), dim3((unsigned)st), dim3(256),
-                       0, h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, Wp, Mm, diag, nullptr, ca,
-                       cc, cd, dslab, Up, ce);
+    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 0, ST>), dim3((unsigned)st), dim3(256), 0, h->stream, n, rp, col,
+                       val, X, ldx, nx, Y, ldy, h->longq, parity, ops, diag, nullptr);
     const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>(st, (int64_t)h->n_cu * 4));
-    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, YCM, EPI, false, AX3, DOT, AX4>), dim3(g2), dim3(256), 0,
-                       h->stream, n, rp, col, val, X, ldx, nx, Y, ldy, h->longq, parity, Wp, Mm, 0, nullptr, ca, cc, cd,
-                       dslab, Up, ce);
+    hipLaunchKernelGGL((k_spmm_seg<T, B, TR, CAP, WIN, 1, ST>), dim3(g2), dim3(256), 0, h->stream, n, rp, col, val, X,
+                       ldx, nx, Y, ldy, h->longq, parity, ops, 0, nullptr);
     return LZ_OK;
+}
+
+// launch_seg at the stage (768 entries, or the store's larger one: 1024 for Beta2, 1536
+// for the others) and gather (win: windowed, Rows and ColMajor only) chosen at run time:
+// f(integral_constant<int, CAP>, bool_constant<WIN>) once, as by_dtype does for the dtype.
+// Only the combinations a store has are instantiated.
+template <SegStore ST, typename F>
+static int by_stage(int cap, bool win, F &&f)
+{
+    constexpr bool kHasWin = ST == SegStore::Rows || ST == SegStore::ColMajor;
+    constexpr int kLarge = ST == SegStore::Beta2 ? 1024 : 1536;
+    LZ_ARG_CHECK((cap == 768 || cap == kLarge) && (kHasWin || !win),
+                 "k_spmm_seg: no such stage or window for this store");
+    using Small = std::integral_constant<int, 768>;
+    using Large = std::integral_constant<int, kLarge>;
+    if constexpr (kHasWin)
+        if (win) return cap == 768 ? f(Small{}, std::true_type{}) : f(Large{}, std::true_type{});
+    return cap == 768 ? f(Small{}, std::false_type{}) : f(Large{}, std::false_type{});
+}
+
+// the stage of every store but Beta2 (spmm_b2_stage): 1536 entries past 13 nnz per row
+static int seg_stage(int64_t n, int64_t nnz)
+{
+    return (double)nnz > 13.0 * (double)n ? 1536 : 768;
 }
 
 // Kernel choice.  128-B rows (b = 16 fp64, b = 32 fp32): the nnz-split
@@ -1681,7 +1704,6 @@ static int launch_spmm_rm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *r
     const int ev = prof_begin(h, PROF_SPMM);
     int rc = LZ_OK;
     if constexpr (S::LPR == 8) {
-        const bool wide = (double)nnz > 13.0 * (double)n;
         const char *fz = getenv("LZ_SPMM_FNZ");  // experiment: fixed-nnz tiles (read per call)
         bool fnz = false;
         if (fz && fz[0] == '1' && !ycm && buf_ok && ldx == B && ldy == B)
@@ -1689,15 +1711,17 @@ static int launch_spmm_rm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *r
         if (fnz) {
             h->last_kernel[0] = LZ_K_FNZ;
             rc = launch_fnz<T, B>(h, nnz, val, X, ldx, nx, Y, ldy);
-        } else if (ycm) {
-            if (buf_ok && !wide) rc = launch_seg<T, B, 48, 768, false, true>(h, n, rp, col, val, X, ldx, nx, Y, ldy);
-            else if (buf_ok) rc = launch_seg<T, B, 48, 1536, false, true>(h, n, rp, col, val, X, ldx, nx, Y, ldy);
-            else if (!wide) rc = launch_seg<T, B, 48, 768, true, true>(h, n, rp, col, val, X, ldx, nx, Y, ldy);
-            else rc = launch_seg<T, B, 48, 1536, true, true>(h, n, rp, col, val, X, ldx, nx, Y, ldy);
-        } else if (buf_ok && !wide) rc = launch_seg<T, B, 48, 768, false>(h, n, rp, col, val, X, ldx, nx, Y, ldy);
-        else if (buf_ok) rc = launch_seg<T, B, 48, 1536, false>(h, n, rp, col, val, X, ldx, nx, Y, ldy);
-        else if (!wide) rc = launch_seg<T, B, 48, 768, true>(h, n, rp, col, val, X, ldx, nx, Y, ldy);
-        else rc = launch_seg<T, B, 48, 1536, true>(h, n, rp, col, val, X, ldx, nx, Y, ldy);
+        } else {
+            auto seg = [&](auto store) {
+                constexpr SegStore ST = decltype(store)::value;
+                return by_stage<ST>(seg_stage(n, nnz), !buf_ok, [&](auto cap, auto win) {
+                    return launch_seg<T, B, 48, decltype(cap)::value, decltype(win)::value, ST>(
+                        h, n, rp, col, val, X, ldx, nx, Y, ldy, SegOperands<T>{}, -1, nullptr);
+                });
+            };
+            rc = ycm ? seg(std::integral_constant<SegStore, SegStore::ColMajor>{})
+                     : seg(std::integral_constant<SegStore, SegStore::Rows>{});
+        }
     } else {
         const int64_t tiles = ceil_div(n, (int64_t)S::RB * 2);
         LZ_ARG_CHECK(tiles < (1LL << 31), "too many row tiles");
@@ -1804,10 +1828,13 @@ int spmm_rm_b2(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const in
     LZ_ARG_CHECK(cap == 768 || cap == 1024, "beta^2 SpMM stage: 768 or 1024 (spmm_b2_stage)");
     if (n <= 0) return LZ_OK;
     const int ev = prof_begin(h, PROF_SPMM);
-    const int rc = cap == 1024 ? launch_seg<float, 32, 48, 1024, false, false, true>(h, n, rp, col, val, X, 32, nx, Y,
-                                                                                   32, Wp, Mm, plan_slot, slot_out)
-                               : launch_seg<float, 32, 48, 768, false, false, true>(h, n, rp, col, val, X, 32, nx, Y, 32,
-                                                                                  Wp, Mm, plan_slot, slot_out);
+    SegOperands<float> ops;
+    ops.Wprev = Wp;
+    ops.M = Mm;
+    const int rc = by_stage<SegStore::Beta2>(cap, false, [&](auto stage, auto win) {
+        return launch_seg<float, 32, 48, decltype(stage)::value, decltype(win)::value, SegStore::Beta2>(
+            h, n, rp, col, val, X, 32, nx, Y, 32, ops, plan_slot, slot_out);
+    });
     prof_end(h, ev);
     LZ_TRY(rc);
     LZ_LAUNCH_CHECK();
@@ -1857,147 +1884,87 @@ int spmm_rm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32
     }
 }
 
-// The row-local pass of the two-launch three-term step: Y = a Y + c X + d Z over
-// nb = n b contiguous elements (ld = b), 64-bit indices; Z == nullptr: d == 0,
-// Z is never read.  The arithmetic of ax3_piece on the stored SpMM row.
-template <typename T>
-__global__ __launch_bounds__(256) void k_ax3_rows(int64_t nb, T a, T c, T d, const T *__restrict__ X,
-                                                  const T *__restrict__ Z, T *__restrict__ Y)
+// The row-local pass of the two-launch term steps: Y = a Y + c X + d Z + e U over nb = n b
+// contiguous elements (ld = b), 64-bit indices; Z == nullptr: d == 0, U == nullptr: e == 0,
+// neither is read then (HAS_U = false: the three-term steps).  The arithmetic of term_piece
+// on the stored SpMM row.
+template <typename T, bool HAS_U>
+__global__ __launch_bounds__(256) void k_term_rows(int64_t nb, T a, T c, T d, T e, const T *__restrict__ X,
+                                                   const T *__restrict__ Z, const T *__restrict__ U,
+                                                   T *__restrict__ Y)
 {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nb; i += (int64_t)gridDim.x * 256)
-        Y[i] = fma(a, Y[i], fma(c, X[i], Z ? d * Z[i] : T(0)));
-}
-
-// Y = a A X + c X + d Z (lz_csr_spmm_axpby): square operator, ld = b everywhere.
-// Fused into k_spmm_seg's store (AX3) under the conditions launch_spmm_rm picks
-// launch_seg<..., false> for: 128-B rows, X under 2 GiB / 2^24 rows, 16-B
-// aligned blocks (Z == nullptr: d == 0).
-template <typename T>
-static bool ax3_store_ok(int64_t n, int b, const T *X, const T *Z, const T *Y)
-{
-    const bool rows128 = (int64_t)b * (int64_t)sizeof(T) == 128;
-    const bool buf_ok = n * b * (int64_t)sizeof(T) < (1LL << 31) && n < (1 << 24);
-    const bool al16 = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) |
-                        reinterpret_cast<uintptr_t>(Z)) & 15) == 0;
-    const char *fz = getenv("LZ_SPMM_FNZ");  // (the fixed-nnz experiment has no fused store)
-    return rows128 && buf_ok && al16 && !(fz && fz[0] == '1');
-}
-
-// the fused launch at those shapes; DOT: with the tiles' dot slabs to dslab
-template <typename T, bool DOT>
-static int launch_ax3(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, T a,
-                      const T *X, T c, T d, const T *Z, T *Y, double *dslab)
-{
-    constexpr int B = 128 / (int)sizeof(T);
-    const bool wide = (double)nnz > 13.0 * (double)n;
-    const int ev = prof_begin(h, PROF_SPMM);
-    const int rc = wide ? launch_seg<T, B, 48, 1536, false, false, false, true, DOT>(
-                              h, n, rp, col, val, X, B, n, Y, B, Z, nullptr, -1, nullptr, a, c, d, dslab)
-                        : launch_seg<T, B, 48, 768, false, false, false, true, DOT>(
-                              h, n, rp, col, val, X, B, n, Y, B, Z, nullptr, -1, nullptr, a, c, d, dslab);
-    prof_end(h, ev);
-    LZ_TRY(rc);
-    LZ_LAUNCH_CHECK();
-    return LZ_OK;
-}
-
-// fused = false (measurement, scripts/cheb_bench.py's two-launch side) or any
-// other shape: spmm_rm, then k_ax3_rows.
-template <typename T>
-int spmm_axpby(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
-               T a, const T *X, T c, T d, const T *Z, T *Y, bool fused)
-{
-    if (n <= 0) return LZ_OK;
-    if (d == T(0)) Z = nullptr;
-    if (fused && ax3_store_ok<T>(n, b, X, Z, Y))
-        return launch_ax3<T, false>(h, n, nnz, rp, col, val, a, X, c, d, Z, Y, nullptr);
-    LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, X, b, n, Y, b));
-    const int64_t nb = n * b;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(nb, (int64_t)256), (int64_t)h->n_cu * 16));
-    hipLaunchKernelGGL((k_ax3_rows<T>), dim3(grid), dim3(256), 0, h->stream, nb, a, c, d, X, Z, Y);
-    LZ_LAUNCH_CHECK();
-    return LZ_OK;
-}
-
-// The row-local pass of the two-launch four-term step: Y = a Y + c X + d Z + e U over nb = n b
-// contiguous elements, 64-bit indices; Z == nullptr: d == 0, U == nullptr: e == 0, neither is
-// read then.  The arithmetic of ax4_piece on the stored SpMM row.
-template <typename T>
-__global__ __launch_bounds__(256) void k_ax4_rows(int64_t nb, T a, T c, T d, T e, const T *__restrict__ X,
-                                                  const T *__restrict__ Z, const T *__restrict__ U,
-                                                  T *__restrict__ Y)
-{
+    const bool hu = HAS_U && U != nullptr;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nb; i += (int64_t)gridDim.x * 256) {
-        T t = U ? e * U[i] : T(0);
-        if (Z) t = U ? fma(d, Z[i], t) : d * Z[i];
+        T t = hu ? e * U[i] : T(0);
+        if (Z) t = hu ? fma(d, Z[i], t) : d * Z[i];
         Y[i] = fma(a, Y[i], fma(c, X[i], t));
     }
 }
 
-// Y = a A X + c X + d Z + e U (lz_csr_spmm_axpby4): spmm_axpby's shapes and switch, U in the
-// alignment test.  Fused: k_spmm_seg's AX4 store (last_kernel | LZ_K_AX3 | LZ_K_AX4); fused =
-// false or any other shape: spmm_rm, then k_ax4_rows -- the same bits.
+// Y = a A X + c X + d Z (+ e U) (lz_csr_spmm_axpby, _axpby_dots, _axpby4): square operator,
+// ld = b everywhere.  The terms leave k_spmm_seg's store (Terms3 / Terms3Dots / Terms4)
+// under the conditions launch_spmm_rm picks launch_seg<..., false, Rows> for: 128-B rows,
+// X under 2 GiB / 2^24 rows, 16-B aligned blocks (Z, U: those that are read).  fused =
+// false (measurement, the benchmarks' two-launch side) or any other shape: spmm_rm, then
+// k_term_rows -- the same bits.  dots: the stored Y's column dots; from the store too
+// (a slab per 48-row tile, folded by dots_fold) unless fused_dot = false (measurement) or
+// the step has four terms, else the streaming col_dots.
 template <typename T>
-int spmm_axpby4(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
-                T a, const T *X, T c, T d, const T *Z, T e, const T *U, T *Y, bool fused)
+int spmm_terms(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+               SpmmTerms<T> t, T *Y, double *dots, bool fused, bool fused_dot)
 {
     if (n <= 0) return LZ_OK;
-    if (d == T(0)) Z = nullptr;
-    if (e == T(0)) U = nullptr;
-    if (fused && ax3_store_ok<T>(n, b, X, Z, Y) && (reinterpret_cast<uintptr_t>(U) & 15) == 0) {
+    if (t.d == T(0)) t.Z = nullptr;
+    if (t.e == T(0) || !t.four) t.U = nullptr;
+    const bool rows128 = (int64_t)b * (int64_t)sizeof(T) == 128;
+    const bool buf_ok = n * b * (int64_t)sizeof(T) < (1LL << 31) && n < (1 << 24);
+    const bool al16 = ((reinterpret_cast<uintptr_t>(t.X) | reinterpret_cast<uintptr_t>(Y) |
+                        reinterpret_cast<uintptr_t>(t.Z) | reinterpret_cast<uintptr_t>(t.U)) & 15) == 0;
+    const char *fz = getenv("LZ_SPMM_FNZ");  // (the fixed-nnz experiment has no fused store)
+    if (fused && rows128 && buf_ok && al16 && !(fz && fz[0] == '1')) {
         constexpr int B = 128 / (int)sizeof(T);
-        const bool wide = (double)nnz > 13.0 * (double)n;
+        const bool store_dots = dots && fused_dot && !t.four;
+        SegOperands<T> ops;
+        ops.Z = t.Z, ops.U = t.U;
+        ops.a = t.a, ops.c = t.c, ops.d = t.d, ops.e = t.e;
+        if (store_dots) {
+            LZ_TRY(dots_reserve(h, n, b));
+            ops.dots = h->dots_ws;
+        }
+        auto seg = [&](auto store) {
+            constexpr SegStore ST = decltype(store)::value;
+            return by_stage<ST>(seg_stage(n, nnz), false, [&](auto cap, auto win) {
+                return launch_seg<T, B, 48, decltype(cap)::value, decltype(win)::value, ST>(
+                    h, n, rp, col, val, t.X, B, n, Y, B, ops, -1, nullptr);
+            });
+        };
         const int ev = prof_begin(h, PROF_SPMM);
-        const int rc = wide ? launch_seg<T, B, 48, 1536, false, false, false, true, false, true>(
-                                  h, n, rp, col, val, X, B, n, Y, B, Z, nullptr, -1, nullptr, a, c, d, nullptr, U, e)
-                            : launch_seg<T, B, 48, 768, false, false, false, true, false, true>(
-                                  h, n, rp, col, val, X, B, n, Y, B, Z, nullptr, -1, nullptr, a, c, d, nullptr, U, e);
+        const int rc = store_dots ? seg(std::integral_constant<SegStore, SegStore::Terms3Dots>{})
+                       : t.four   ? seg(std::integral_constant<SegStore, SegStore::Terms4>{})
+                                  : seg(std::integral_constant<SegStore, SegStore::Terms3>{});
         prof_end(h, ev);
         LZ_TRY(rc);
         LZ_LAUNCH_CHECK();
-        return LZ_OK;
+        if (store_dots) return dots_fold(h, ceil_div(n, (int64_t)48), b, dots);
+    } else {
+        LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, t.X, b, n, Y, b));
+        const int64_t nb = n * b;
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(nb, (int64_t)256), (int64_t)h->n_cu * 16));
+        if (t.four)
+            hipLaunchKernelGGL((k_term_rows<T, true>), dim3(grid), dim3(256), 0, h->stream, nb, t.a, t.c, t.d, t.e, t.X,
+                               t.Z, t.U, Y);
+        else
+            hipLaunchKernelGGL((k_term_rows<T, false>), dim3(grid), dim3(256), 0, h->stream, nb, t.a, t.c, t.d, t.e, t.X,
+                               t.Z, t.U, Y);
+        LZ_LAUNCH_CHECK();
     }
-    LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, X, b, n, Y, b));
-    const int64_t nb = n * b;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(nb, (int64_t)256), (int64_t)h->n_cu * 16));
-    hipLaunchKernelGGL((k_ax4_rows<T>), dim3(grid), dim3(256), 0, h->stream, nb, a, c, d, e, X, Z, U, Y);
-    LZ_LAUNCH_CHECK();
-    return LZ_OK;
+    return dots ? col_dots<T>(h, n, b, Y, t.X, dots) : LZ_OK;
 }
 
-template int spmm_axpby4<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *, int,
-                                 double, const double *, double, double, const double *, double, const double *,
-                                 double *, bool);
-template int spmm_axpby4<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
-                                float, const float *, float, float, const float *, float, const float *, float *, bool);
-
-// spmm_axpby and the stored Y's column dots (lz_csr_spmm_axpby_dots).  At spmm_axpby's
-// fused shapes the dots leave the same store (DOT): a slab per 48-row tile, folded by
-// dots_fold.  fused_dot = false (LZ_AX3DOT=0, measurement), fused = false or any other
-// shape: spmm_axpby as it is, then the streaming col_dots.
-template <typename T>
-int spmm_axpby_dots(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
-                    T a, const T *X, T c, T d, const T *Z, T *Y, double *dots, bool fused, bool fused_dot)
-{
-    if (d == T(0)) Z = nullptr;
-    if (fused && fused_dot && ax3_store_ok<T>(n, b, X, Z, Y)) {
-        LZ_TRY(dots_reserve(h, n, b));
-        LZ_TRY((launch_ax3<T, true>(h, n, nnz, rp, col, val, a, X, c, d, Z, Y, h->dots_ws)));
-        return dots_fold(h, ceil_div(n, (int64_t)48), b, dots);
-    }
-    LZ_TRY(spmm_axpby<T>(h, n, nnz, rp, col, val, b, a, X, c, d, Z, Y, fused));
-    return col_dots<T>(h, n, b, Y, X, dots);
-}
-
-template int spmm_axpby_dots<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *,
-                                     int, double, const double *, double, double, const double *, double *, double *,
-                                     bool, bool);
-template int spmm_axpby_dots<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
-                                    float, const float *, float, float, const float *, float *, double *, bool, bool);
-template int spmm_axpby<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *, int,
-                                double, const double *, double, double, const double *, double *, bool);
-template int spmm_axpby<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
-                               float, const float *, float, float, const float *, float *, bool);
+template int spmm_terms<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *, int,
+                                SpmmTerms<double>, double *, double *, bool, bool);
+template int spmm_terms<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
+                               SpmmTerms<float>, float *, double *, bool, bool);
 
 // Column-major block (b columns, leading dimension ld) -> row-major (ld = b),
 // kCmRows rows per workgroup through LDS: the column reads and the row writes
