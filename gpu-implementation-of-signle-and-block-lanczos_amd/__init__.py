@@ -52,6 +52,12 @@ PANEL_MAX_KEEP = 16  # most output blocks of one panel_compress (LZ_PANEL_MAX_KE
 # sorted by one lane group, up to TRANSPOSE_LDS by one workgroup through LDS, a longer one in
 # chunks of TRANSPOSE_LDS merged pairwise; the scan covers TRANSPOSE_SCAN_BLOCK counts per workgroup
 TRANSPOSE_SHORT, TRANSPOSE_LDS, TRANSPOSE_SCAN_BLOCK = 16, 4096, 2048
+# lz_cg_update (csrc/lz_internal.hpp kCg*): CG_THREADS threads per block; the 128-byte-row form covers
+# CG_ROWS_128 rows per block pass, the generic form CG_THREADS // b; at most CG_GRID_CAP blocks (one
+# slab each), then grid-stride.  CG_CHECK_EVERY: lz_cg_solve's default iterations between two reads
+# of the live count
+CG_THREADS, CG_ROWS_128, CG_GRID_CAP, CG_CHECK_EVERY = 256, 32, 2048, 8
+CG_MET, CG_SPENT, CG_NOT_PD = 0, 1, 2  # Handle.solve's status per column
 
 _c_i64, _c_i32, _c_int, _c_dbl, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_double, ctypes.c_void_p
 _c_u32, _c_u64 = ctypes.c_uint32, ctypes.c_uint64
@@ -112,6 +118,9 @@ HIP_SYMBOLS = [
                                         _c_dbl, _c_dbl, _c_vp, _c_vp, _c_vp]),
     ("lz_cheb_moments", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_dbl, _c_int,
                                  _c_vp, _c_vp, _c_vp]),
+    ("lz_cg_update", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lz_cg_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp,
+                             _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_block_lanczos_reorth_cheb", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int,
                                               _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int,
                                               _c_vp, _c_vp]),
@@ -188,6 +197,10 @@ HOST_SYMBOLS = [
     ("lzh_restart_coeffs", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_restart_fill", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     ("lzh_gershgorin", _c_int, [_c_i64, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lzh_cg_start", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                              _c_vp]),
+    ("lzh_cg_scalars", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                _c_vp, _c_vp]),
     ("lzh_kpm_moments", _c_int, [_c_int, _c_int, _c_vp, _c_vp]),
     ("lzh_jackson", _c_int, [_c_int, _c_vp]),
     ("lzh_kpm_count", _c_int, [_c_int, _c_vp, _c_vp, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_vp]),
@@ -455,6 +468,11 @@ class ChebFilter(ctypes.Structure):
     """lz_cheb (include/lz_hip.h): the scaled Chebyshev filter of `degree` that damps
     [lo, hi] and is 1 at ref."""
     _fields_ = [("degree", _c_int), ("lo", _c_dbl), ("hi", _c_dbl), ("ref", _c_dbl)]
+
+
+class CgOpts(ctypes.Structure):
+    """lz_cg_opts (include/lz_hip.h): check_every 0 = the library's default."""
+    _fields_ = [("tol", _c_dbl), ("max_iter", _c_int), ("check_every", _c_int), ("max_restarts", _c_int)]
 
 
 def _cheb(filt):
@@ -968,6 +986,80 @@ class Handle:
         _check(self.L.lz_cheb_moments(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
                                       lo, hi, K, _ptr(X0), _ptr(work), _ptr(dots)), "lz_cheb_moments")
         return dots.view(-1, 2, b)
+
+    def cg_update(self, coef, R, W, P, S, X, rr=None):
+        """The row-local half of one conjugate-gradient step with per-column device coefficients
+        (lz_cg_update): P = R + beta P, S = W + beta S, X += alpha P, R -= alpha S, each element
+        finished as one fma in that order, and rr[c] = the column sums of the new R * R in fp64.
+        coef: 2 b fp64 on the device, [alpha(b) | beta(b)], read only, rounded once to the blocks'
+        dtype; R, W (read only), P, S, X: (n, b) contiguous, of one dtype, pairwise distinct; a zero
+        coefficient skips its product.  Returns rr (b fp64 on the device; allocated when None)."""
+        torch = _torch()
+        n, b = R.shape
+        for t in (R, W, P, S, X):
+            if tuple(t.shape) != (n, b) or t.dtype != R.dtype or not t.is_contiguous():
+                raise LanczosError("cg_update: R, W, P, S, X (n, b) contiguous (ld = b), of one dtype")
+        if coef.dtype != torch.float64 or not coef.is_contiguous() or coef.numel() != 2 * b:
+            raise LanczosError("cg_update: coef is a contiguous fp64 tensor of 2 b elements")
+        if rr is None:
+            rr = torch.empty(b, dtype=torch.float64, device=R.device)
+        if rr.dtype != torch.float64 or not rr.is_contiguous() or rr.numel() != b:
+            raise LanczosError("cg_update: rr is a contiguous fp64 tensor of b elements")
+        _check(self.L.lz_cg_update(self.ptr, n, b, _dt(R), _ptr(coef), _ptr(R), _ptr(W), _ptr(P), _ptr(S), _ptr(X),
+                                   _ptr(rr)), "lz_cg_update")
+        return rr
+
+    def solve(self, A: CsrDevice, B, shift: float = 0.0, tol: Optional[float] = None, max_iter: Optional[int] = None,
+              X0=None, check_every: Optional[int] = None, max_restarts: int = 3, work=None):
+        """Solves (A + shift I) X = B for a symmetric positive definite A + shift I by conjugate
+        gradients, the b <= 64 columns of B in lock step, each by its own scalars (lz_cg_solve).
+
+        The precision is A's: blocks and the SpMM run in A's dtype (shift is rounded to it once), the
+        dots and the scalars in fp64.  tol: the relative residual |B_c - M X_c| / |B_c| a column must
+        reach, default 1e-10 for an fp64 operator and 1e-4 for fp32; max_iter: most steps of one
+        column, default min(10 n, 10000); X0: the start block, default zeros (it is copied, not
+        overwritten).  Device memory: 6 blocks of n b elements (B, X and the four of work: flat,
+        4 n b elements, allocated when None).  There is no preconditioner, so the iterations grow
+        like the square root of the condition number.  Per iteration: one fused SpMM with dots, one
+        scalar launch and one update pass; the host reads one live count per check_every iterations
+        (default: the library's, CG_CHECK_EVERY).  A converged column is frozen and its X no longer
+        changes by a bit; when all are frozen the true residual is measured and columns that fail
+        it run again from it, at most max_restarts times.  A column whose B holds a NaN ends at
+        once with status 2 (its denominator is not finite), its X untouched.
+
+        Returns a dict: X; iters, status (0 met tol on the measured residual, 1 iterations or
+        restarts spent, 2 not positive definite), converged (status == 0), resid (measured), est
+        (the recurrence's last value) -- NumPy arrays of b entries; restarts, n_spmm, iterations."""
+        torch = _torch()
+        n, b = self._blocks("solve", A, B)
+        f64 = A.val.dtype == torch.float64
+        tol = (1e-10 if f64 else 1e-4) if tol is None else float(tol)
+        max_iter = min(10 * n, 10000) if max_iter is None else int(max_iter)
+        if X0 is None:
+            X = torch.zeros_like(B)
+        else:
+            self._blocks("solve", A, B, X0)
+            X = X0.clone()
+        work = self._work4("solve", work, n, b, B)
+        if check_every is not None and check_every < 1:
+            raise LanczosError("solve: check_every >= 1")
+        opts = CgOpts(tol, max_iter, 0 if check_every is None else int(check_every), int(max_restarts))
+        iters, status = np.zeros(b, np.int32), np.zeros(b, np.int32)
+        resid, est, info = np.zeros(b), np.zeros(b), np.zeros(3, np.int32)
+        _check(self.L.lz_cg_solve(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                  float(shift), _ptr(B), _ptr(X), _ptr(work), ctypes.addressof(opts), _p(iters),
+                                  _p(status), _p(resid), _p(est), _p(info)), "lz_cg_solve")
+        return {"X": X, "iters": iters, "status": status, "converged": status == 0, "resid": resid, "est": est,
+                "iterations": int(info[0]), "restarts": int(info[1]), "n_spmm": int(info[2])}
+
+    @staticmethod
+    def _work4(what: str, work, n: int, b: int, like):
+        torch = _torch()
+        if work is None:
+            return torch.empty(4 * n * b, dtype=like.dtype, device=like.device)
+        if work.dim() != 1 or not work.is_contiguous() or work.numel() < 4 * n * b or work.dtype != like.dtype:
+            raise LanczosError(f"{what}: work is a flat contiguous tensor of 4*n*b elements of B's dtype")
+        return work
 
     def spectral_moments(self, A: CsrDevice, n_moments: int = 257, probes: Optional[int] = None,
                          b: Optional[int] = None, bounds=None, pad: float = 0.01, seed: int = 0,

@@ -1,0 +1,365 @@
+// lz_cg.hip -- batched conjugate gradients on M = A + shift I for b right-hand
+// sides in lock step: lz_cg_update and lz_cg_solve.
+//   * k_cg_update: the row-local half of a Chronopoulos-Gear step with per-column
+//     device coefficients -- five blocks read, four written, slabs of the new
+//     residual's column dots; a 128-byte-row form and a generic one;
+//   * k_cg_start / k_cg_scalars: one workgroup, the per-column rules of lz_cg.hpp
+//     on device memory only;
+//   * cg_solve: the host loop -- one fused SpMM with dots, the scalars, the
+//     update and its fold per iteration; one 4-byte read of the live count per
+//     check_every iterations is its only synchronisation.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+
+#include "lz_cg.hpp"
+#include "lz_common.hpp"
+#include "lz_internal.hpp"
+
+namespace lz {
+
+// The solve's device state (h->cg_ws).  sd: the dots of the last SpMM ([Y.Y |
+// Y.X], 2 b used); bn2: col_dots(B, B); coef: [alpha(b) | beta(b)].
+struct CgState {
+    double sd[2 * kMaxB], bn2[2 * kMaxB], coef[2 * kMaxB];
+    double gamma[kMaxB], meas[kMaxB];
+    CgCol col[kMaxB];
+    int nlive, pad;
+};
+
+static int cg_reserve(lz_handle *h, int64_t n, int b)
+{
+    const size_t had = h->cg_cap;
+    LZ_TRY(grow_ws(h, &h->cg_ws, &h->cg_cap, sizeof(CgState)));
+    // test support, as lz_init's: a workspace grown under LZ_POISON=1 starts NaN-filled
+    if (const char *pz = getenv("LZ_POISON"); h->cg_cap != had && pz && pz[0] == '1')
+        LZ_HIP_TRY(hipMemsetAsync(h->cg_ws, 0xFF, h->cg_cap, h->stream));
+    // the update's slabs are b doubles per block: half a dots slab each
+    return dots_reserve(h, n, b, kCgGridCap);
+}
+
+template <typename T>
+struct Vec16;
+template <>
+struct Vec16<double> {
+    typedef double type __attribute__((ext_vector_type(2)));
+};
+template <>
+struct Vec16<float> {
+    typedef float type __attribute__((ext_vector_type(4)));
+};
+
+template <bool NT, typename V>
+__device__ inline V ld16(const V *p)
+{
+    if constexpr (NT)
+        return __builtin_nontemporal_load(p);
+    else
+        return *p;
+}
+template <bool NT, typename V>
+__device__ inline void st16(V *p, V v)
+{
+    if constexpr (NT)
+        __builtin_nontemporal_store(v, p);
+    else
+        *p = v;
+}
+
+// Both forms finish every element in this order, alpha and beta being the
+// column's coef entries rounded once to T:
+//   p' = fma(beta, p, r);  s' = fma(beta, s, w);
+//   x' = fma(alpha, p', x);  r' = fma(-alpha, s', r);
+// and add (double)r' * (double)r' into the column's fp64 partial with fma.  A
+// coefficient that is zero skips its product: beta == 0 gives p' = r, s' = w
+// whatever P and S hold (a solve's first step reads work it never wrote), and
+// alpha == 0 leaves x and r as they are, bit for bit (a frozen column).
+//
+// The 128-byte-row form (b = 16 fp64, b = 32 fp32; every block on 16 bytes):
+// lane t moves 16 bytes, columns VEC (t % 8) .. + VEC of row lane t / 8, so its
+// coefficients stay in registers; block q takes rows q kCgRows128 + t / 8 + k G
+// kCgRows128, k = 0, 1, ...  The row lanes of a column are summed in order
+// through LDS into slab q (b doubles).  NT: P, S, X and W move with non-temporal
+// loads and stores (nothing reads them again before a whole iteration has
+// passed); R, which the next SpMM gathers, always with plain ones.
+template <typename T, bool NT>
+__global__ __launch_bounds__(kCgThreads) void k_cg_update128(int64_t n, const double *__restrict__ coef,
+                                                             T *__restrict__ R, const T *__restrict__ W,
+                                                             T *__restrict__ P, T *__restrict__ S, T *__restrict__ X,
+                                                             double *__restrict__ slabs)
+{
+    using V = typename Vec16<T>::type;
+    constexpr int VEC = 16 / (int)sizeof(T), B = 8 * VEC;
+    __shared__ double red[kCgThreads][VEC];
+    const int tid = threadIdx.x, l = tid & 7, rl = tid >> 3;
+    T al[VEC], be[VEC];
+    double acc[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+        al[v] = (T)coef[l * VEC + v];
+        be[v] = (T)coef[B + l * VEC + v];
+        acc[v] = 0.0;
+    }
+    const int64_t step = (int64_t)gridDim.x * kCgRows128;
+    for (int64_t row = (int64_t)blockIdx.x * kCgRows128 + rl; row < n; row += step) {
+        const int64_t i = row * 8 + l;  // in 16-byte units
+        V r = reinterpret_cast<const V *>(R)[i];
+        const V w = ld16<NT>(reinterpret_cast<const V *>(W) + i);
+        V p = ld16<NT>(reinterpret_cast<const V *>(P) + i);
+        V s = ld16<NT>(reinterpret_cast<const V *>(S) + i);
+        V x = ld16<NT>(reinterpret_cast<const V *>(X) + i);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            p[v] = be[v] == T(0) ? r[v] : fma(be[v], p[v], r[v]);
+            s[v] = be[v] == T(0) ? w[v] : fma(be[v], s[v], w[v]);
+            x[v] = al[v] == T(0) ? x[v] : fma(al[v], p[v], x[v]);
+            r[v] = al[v] == T(0) ? r[v] : fma(-al[v], s[v], r[v]);
+            acc[v] = fma((double)r[v], (double)r[v], acc[v]);
+        }
+        st16<NT>(reinterpret_cast<V *>(P) + i, p);
+        st16<NT>(reinterpret_cast<V *>(S) + i, s);
+        st16<NT>(reinterpret_cast<V *>(X) + i, x);
+        reinterpret_cast<V *>(R)[i] = r;
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) red[tid][v] = acc[v];
+    __syncthreads();
+    if (tid < B) {
+        const int cl = tid / VEC, cv = tid - cl * VEC;
+        double sum = 0.0;
+        for (int j = 0; j < kCgRows128; ++j) sum += red[j * 8 + cl][cv];
+        slabs[(int64_t)blockIdx.x * B + tid] = sum;
+    }
+}
+
+// The generic form, 1 <= b <= 64, either dtype: k_col_dots's mapping -- thread t <
+// rpb b (rpb = kCgThreads / b) holds column t % b of row lane t / b; block q takes
+// rows q rpb + t / b + k G rpb.
+template <typename T>
+__global__ __launch_bounds__(kCgThreads) void k_cg_update_gen(int64_t n, int b, const double *__restrict__ coef,
+                                                              T *__restrict__ R, const T *__restrict__ W,
+                                                              T *__restrict__ P, T *__restrict__ S, T *__restrict__ X,
+                                                              double *__restrict__ slabs)
+{
+    __shared__ double red[kCgThreads];
+    const int tid = threadIdx.x, rpb = kCgThreads / b, rl = tid / b, c = tid - rl * b;
+    double acc = 0.0;
+    if (rl < rpb) {
+        const T al = (T)coef[c], be = (T)coef[b + c];
+        const int64_t step = (int64_t)gridDim.x * rpb;
+        for (int64_t row = (int64_t)blockIdx.x * rpb + rl; row < n; row += step) {
+            const int64_t i = row * b + c;
+            const T p = be == T(0) ? R[i] : fma(be, P[i], R[i]);
+            const T s = be == T(0) ? W[i] : fma(be, S[i], W[i]);
+            const T x = al == T(0) ? X[i] : fma(al, p, X[i]);
+            const T r = al == T(0) ? R[i] : fma(-al, s, R[i]);
+            P[i] = p;
+            S[i] = s;
+            X[i] = x;
+            R[i] = r;
+            acc = fma((double)r, (double)r, acc);
+        }
+    }
+    red[tid] = acc;
+    __syncthreads();
+    if (tid < b) {
+        double sum = 0.0;
+        for (int j = 0; j < rpb; ++j) sum += red[j * b + tid];
+        slabs[(int64_t)blockIdx.x * b + tid] = sum;
+    }
+}
+
+// LZ_CG_GENERIC=1 (read per call, measurement): the generic form at every shape
+static bool cg_force_generic()
+{
+    const char *e = getenv("LZ_CG_GENERIC");
+    return e && e[0] == '1';
+}
+
+// LZ_CG_NT=0 (read per call, measurement): plain loads and stores for every stream
+static bool cg_nt()
+{
+    const char *e = getenv("LZ_CG_NT");
+    return !(e && e[0] == '0');
+}
+
+// One update: the kernel, then the fold of its G slabs of b doubles into rr.
+// h->dots_ws must hold them (cg_reserve, or dots_reserve(h, n, b, kCgGridCap)).
+template <typename T>
+static int cg_update_launch(lz_handle *h, int64_t n, int b, const double *coef, T *R, const T *W, T *P, T *S, T *X,
+                            double *rr)
+{
+    const bool al16 = ((reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(W) |
+                        reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(S) |
+                        reinterpret_cast<uintptr_t>(X)) & 15) == 0;
+    const bool rows128 = (int64_t)b * (int64_t)sizeof(T) == 128 && al16 && !cg_force_generic();
+    const int64_t rpb = rows128 ? kCgRows128 : kCgThreads / b;
+    const int G = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, rpb), kCgGridCap));
+    const int ev = prof_begin(h, PROF_UPDATE_PASS);
+    if (rows128) {
+        if (cg_nt())
+            hipLaunchKernelGGL((k_cg_update128<T, true>), dim3(G), dim3(kCgThreads), 0, h->stream, n, coef, R, W, P, S,
+                               X, h->dots_ws);
+        else
+            hipLaunchKernelGGL((k_cg_update128<T, false>), dim3(G), dim3(kCgThreads), 0, h->stream, n, coef, R, W, P, S,
+                               X, h->dots_ws);
+    } else {
+        hipLaunchKernelGGL((k_cg_update_gen<T>), dim3(G), dim3(kCgThreads), 0, h->stream, n, b, coef, R, W, P, S, X,
+                           h->dots_ws);
+    }
+    prof_end(h, ev);
+    LZ_LAUNCH_CHECK();
+    return slabs_fold(h, G, b, rr);
+}
+
+template <typename T>
+int cg_update(lz_handle *h, int64_t n, int b, const double *coef, T *R, const T *W, T *P, T *S, T *X, double *rr)
+{
+    LZ_TRY(dots_reserve(h, n, b, kCgGridCap));
+    return cg_update_launch<T>(h, n, b, coef, R, W, P, S, X, rr);
+}
+template int cg_update<double>(lz_handle *, int64_t, int, const double *, double *, const double *, double *, double *,
+                               double *, double *);
+template int cg_update<float>(lz_handle *, int64_t, int, const double *, float *, const float *, float *, float *,
+                              float *, double *);
+
+// the live count of the one-workgroup kernels: live[0 .. b) summed by thread 0
+__device__ inline void cg_count_live(CgState *st, int b, const int *live)
+{
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int nl = 0;
+        for (int j = 0; j < b; ++j) nl += live[j];
+        st->nlive = nl;
+    }
+}
+
+// gamma = the measured residual dots st->sd[0 .. b); the start rule per column;
+// the live count.
+__global__ __launch_bounds__(kMaxB) void k_cg_start(CgState *st, int b, double tol2, int max_iter, int initial)
+{
+    __shared__ int live[kMaxB];
+    const int c = threadIdx.x;
+    if (c < b) {
+        const double g = st->sd[c];
+        CgCol s = st->col[c];
+        cg_start_rule(g, st->gamma[c], tol2 * st->bn2[c], max_iter, initial != 0, s);
+        st->col[c] = s;
+        st->gamma[c] = g;
+        st->meas[c] = g;
+        live[c] = s.live;
+    }
+    cg_count_live(st, b, live);
+}
+
+// delta = st->sd[b .. 2b) of W = M R; the step rule per column; coef and the live count.
+__global__ __launch_bounds__(kMaxB) void k_cg_scalars(CgState *st, int b, double tol2, int max_iter, int first)
+{
+    __shared__ int live[kMaxB];
+    const int c = threadIdx.x;
+    if (c < b) {
+        CgCol s = st->col[c];
+        double alpha, beta;
+        cg_step_rule(st->gamma[c], st->sd[b + c], tol2 * st->bn2[c], first != 0, max_iter, s, alpha, beta);
+        st->col[c] = s;
+        st->coef[c] = alpha;
+        st->coef[b + c] = beta;
+        live[c] = s.live;
+    }
+    cg_count_live(st, b, live);
+}
+
+// The end of a chunk of iterations: the columns the next step would still run, by the
+// recurrence's new gamma (no state changes; a breakdown shows only in that step).
+__global__ __launch_bounds__(kMaxB) void k_cg_live(CgState *st, int b, double tol2, int max_iter)
+{
+    __shared__ int live[kMaxB];
+    const int c = threadIdx.x;
+    if (c < b) {
+        const CgCol s = st->col[c];
+        live[c] = s.live && !(st->gamma[c] <= tol2 * st->bn2[c]) && s.iters < max_iter;
+    }
+    cg_count_live(st, b, live);
+}
+
+// The solve.  work = [R | W | P | S].  A verification (the start step) follows
+// every phase of iterations, so resid is always a measured residual.
+template <typename T>
+int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+             double shift, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status, double *resid,
+             double *est, int *info)
+{
+    LZ_TRY(cg_reserve(h, n, b));
+    CgState *st = static_cast<CgState *>(h->cg_ws);
+    const int64_t nb = n * b;
+    T *R = work, *W = work + nb, *P = work + 2 * nb, *S = work + 3 * nb;
+    const T sg = (T)shift;  // rounded once: it travels as the store's c coefficient
+    const double tol2 = o.tol * o.tol;
+    const int chunk = o.check_every > 0 ? o.check_every : kCgCheckEvery;
+    int iterations = 0, restarts = 0, n_spmm = 0, nlive = 0;
+
+    auto read_live = [&]() -> int {
+        LZ_HIP_TRY(hipMemcpyAsync(&nlive, &st->nlive, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        LZ_HIP_TRY(hipStreamSynchronize(h->stream));
+        return LZ_OK;
+    };
+    // R = B - M X with its dots; gamma = R.R measured
+    auto start = [&](bool initial) -> int {
+        LZ_TRY(spmm_terms<T>(h, n, nnz, rp, col, val, b, {T(-1), X, -sg, T(1), B}, R, st->sd));
+        ++n_spmm;
+        hipLaunchKernelGGL(k_cg_start, dim3(1), dim3(kMaxB), 0, h->stream, st, b, tol2, o.max_iter, initial ? 1 : 0);
+        LZ_LAUNCH_CHECK();
+        return read_live();
+    };
+
+    LZ_TRY(col_dots<T>(h, n, b, B, B, st->bn2, true));
+    LZ_TRY(start(true));
+    while (nlive > 0) {
+        bool first = true;
+        while (nlive > 0) {
+            for (int k = 0; k < chunk; ++k) {
+                LZ_TRY(spmm_terms<T>(h, n, nnz, rp, col, val, b, {T(1), R, sg, T(0), nullptr}, W, st->sd));
+                hipLaunchKernelGGL(k_cg_scalars, dim3(1), dim3(kMaxB), 0, h->stream, st, b, tol2, o.max_iter,
+                                   first ? 1 : 0);
+                LZ_LAUNCH_CHECK();
+                LZ_TRY(cg_update_launch<T>(h, n, b, st->coef, R, W, P, S, X, st->gamma));
+                first = false;
+            }
+            iterations += chunk;
+            n_spmm += chunk;
+            hipLaunchKernelGGL(k_cg_live, dim3(1), dim3(kMaxB), 0, h->stream, st, b, tol2, o.max_iter);
+            LZ_LAUNCH_CHECK();
+            LZ_TRY(read_live());
+        }
+        LZ_TRY(start(false));
+        if (nlive > 0) {
+            if (restarts >= o.max_restarts) break;
+            ++restarts;
+        }
+    }
+
+    CgState hs;
+    LZ_HIP_TRY(hipMemcpyAsync(&hs, st, sizeof(CgState), hipMemcpyDeviceToHost, h->stream));
+    LZ_HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int c = 0; c < b; ++c) {
+        const double bn2 = hs.bn2[c];
+        iters[c] = hs.col[c].iters;
+        status[c] = hs.col[c].status;
+        // a zero column: 0 (with a start vector that is not zero nothing can meet tol: infinity)
+        const double e2 = hs.col[c].est2;
+        resid[c] = bn2 == 0.0 ? (hs.meas[c] == 0.0 ? 0.0 : INFINITY) : std::sqrt(hs.meas[c] / bn2);
+        est[c] = bn2 == 0.0 ? resid[c] : std::sqrt(e2 / bn2);
+    }
+    info[0] = iterations;
+    info[1] = restarts;
+    info[2] = n_spmm;
+    return LZ_OK;
+}
+template int cg_solve<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *, int,
+                              double, const double *, double *, double *, const lz_cg_opts &, int *, int *, double *,
+                              double *, int *);
+template int cg_solve<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int, double,
+                             const float *, float *, float *, const lz_cg_opts &, int *, int *, double *, double *,
+                             int *);
+
+}  // namespace lz

@@ -1,0 +1,90 @@
+// lz_cg.hpp -- the per-column scalar rules of the batched conjugate gradients
+// (DESIGN.md 23), one definition for the device (k_cg_start, k_cg_scalars in
+// lz_cg.hip) and the host library (lzh_cg_start, lzh_cg_scalars in lz_host.cpp).
+// Chronopoulos-Gear CG on M = A + shift I, column by column:
+//   gamma = r.r, delta = (M r).r, beta = gamma / gamma_prev,
+//   alpha = gamma / (delta - beta gamma / alpha_prev),
+//   p = r + beta p, s = M r + beta s, x += alpha p, r -= alpha s.
+// A column's status while it runs is 1 (not yet shown to meet tol); only the
+// start rule, on a measured residual, sets 0.
+#pragma once
+#include <cmath>
+
+#if defined(__HIPCC__)
+#define LZ_CG_HD __host__ __device__
+#else
+#define LZ_CG_HD
+#endif
+
+namespace lz {
+
+enum { kCgMet = 0, kCgSpent = 1, kCgNotPd = 2 };
+
+// One column's state between the launches.
+struct CgCol {
+    double gamma_prev, alpha_prev;  // of the column's last step (read only when !first)
+    double est2;                    // the recurrence's gamma when the column last froze
+    int live, iters, status;
+};
+
+// Start, and every restart: gamma is the measured |b - M x|^2, thr = tol^2 |b|^2.
+// A column that broke down stays frozen; one that passes is frozen with status 0
+// (a zero column passes with 0 <= 0: nothing is divided); one that fails with its
+// iterations spent is frozen with status 1; every other column is live.
+// initial: the solve's first call, which also clears iters and the recurrence state.
+// Otherwise rec is the recurrence's gamma, kept as est2 by a column that was still
+// marked live (the host saw its end before the next step's rule did).
+LZ_CG_HD inline void cg_start_rule(double gamma, double rec, double thr, int max_iter, bool initial, CgCol &s)
+{
+    if (initial) {
+        s.gamma_prev = 0.0;
+        s.alpha_prev = 0.0;
+        s.est2 = gamma;
+        s.iters = 0;
+        s.status = kCgSpent;
+    } else if (s.live) {
+        s.est2 = rec;
+    }
+    if (s.status == kCgNotPd) {
+        s.live = 0;
+    } else if (gamma <= thr) {
+        s.live = 0;
+        s.status = kCgMet;
+    } else {
+        s.status = kCgSpent;
+        s.live = s.iters < max_iter;
+    }
+}
+
+// One iteration's scalars: gamma = r.r (the recurrence's), delta = (M r).r.
+// A live column whose gamma has reached thr, or whose iterations are spent, is
+// frozen here (est2 = gamma); a frozen column gets alpha = beta = 0 and its
+// state is not touched.  den <= 0 or not finite: status 2, frozen for good,
+// alpha = beta = 0, iters not advanced.
+LZ_CG_HD inline void cg_step_rule(double gamma, double delta, double thr, bool first, int max_iter, CgCol &s,
+                                  double &alpha, double &beta)
+{
+    alpha = 0.0;
+    beta = 0.0;
+    if (!s.live) return;
+    if (gamma <= thr || s.iters >= max_iter) {
+        s.live = 0;
+        s.est2 = gamma;
+        return;
+    }
+    const double bt = first ? 0.0 : gamma / s.gamma_prev;
+    const double den = first ? delta : delta - bt * gamma / s.alpha_prev;
+    if (!(den > 0.0) || !std::isfinite(den)) {
+        s.live = 0;
+        s.status = kCgNotPd;
+        s.est2 = gamma;
+        return;
+    }
+    alpha = gamma / den;
+    beta = bt;
+    s.gamma_prev = gamma;
+    s.alpha_prev = alpha;
+    s.iters += 1;
+}
+
+}  // namespace lz

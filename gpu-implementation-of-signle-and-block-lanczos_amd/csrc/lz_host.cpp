@@ -4,6 +4,8 @@
 
 #include <omp.h>
 
+#include "lz_cg.hpp"
+
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -647,6 +649,42 @@ int lzh_gershgorin(int64_t n, const int64_t *row_ptr, const int32_t *col, const 
     }
     out[0] = lo;
     out[1] = hi;
+    return 0;
+}
+
+// ---- batched conjugate gradients: the per-column rules of lz_cg.hpp, as k_cg_start and
+// k_cg_scalars apply them, on host arrays of b entries
+int lzh_cg_start(int b, int max_iter, int initial, const double *gamma, const double *rec, const double *thr,
+                 double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters, int *status, int *nlive)
+{
+    if (b < 1 || !gamma || !rec || !thr || !gamma_prev || !alpha_prev || !est2 || !live || !iters || !status || !nlive)
+        return -1;
+    *nlive = 0;
+    for (int c = 0; c < b; ++c) {
+        lz::CgCol s{gamma_prev[c], alpha_prev[c], est2[c], live[c], iters[c], status[c]};
+        lz::cg_start_rule(gamma[c], rec[c], thr[c], max_iter, initial != 0, s);
+        gamma_prev[c] = s.gamma_prev, alpha_prev[c] = s.alpha_prev, est2[c] = s.est2;
+        live[c] = s.live, iters[c] = s.iters, status[c] = s.status;
+        *nlive += s.live;
+    }
+    return 0;
+}
+
+int lzh_cg_scalars(int b, int first, int max_iter, const double *gamma, const double *delta, const double *thr,
+                   double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters, int *status,
+                   double *coef, int *nlive)
+{
+    if (b < 1 || !gamma || !delta || !thr || !gamma_prev || !alpha_prev || !est2 || !live || !iters || !status ||
+        !coef || !nlive)
+        return -1;
+    *nlive = 0;
+    for (int c = 0; c < b; ++c) {
+        lz::CgCol s{gamma_prev[c], alpha_prev[c], est2[c], live[c], iters[c], status[c]};
+        lz::cg_step_rule(gamma[c], delta[c], thr[c], first != 0, max_iter, s, coef[c], coef[b + c]);
+        gamma_prev[c] = s.gamma_prev, alpha_prev[c] = s.alpha_prev, est2[c] = s.est2;
+        live[c] = s.live, iters[c] = s.iters, status[c] = s.status;
+        *nlive += s.live;
+    }
     return 0;
 }
 

@@ -39,13 +39,31 @@ int spmm_cm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32
 
 // ---- column dots and Chebyshev moments (lz_kpm.hip)
 // h->dots_ws for every dots call on n x b blocks (may synchronise; afterwards those calls never do)
-int dots_reserve(lz_handle *h, int64_t n, int b);
+// (min_slabs: room for at least that many slabs, for a kernel with a grid of its own)
+int dots_reserve(lz_handle *h, int64_t n, int b, int64_t min_slabs = 0);
 // the streaming form: Y and X (n x b, ld = b, any b <= 64; Y == X allowed) read once, slabs, fold
 // (zero_cross: dots[b .. 2b) = 0)
 template <typename T>
 int col_dots(lz_handle *h, int64_t n, int b, const T *Y, const T *X, double *dots, bool zero_cross = false);
 // P slabs of 2 b doubles at h->dots_ws -> dots, every sum in a fixed order, no host synchronisation
 int dots_fold(lz_handle *h, int64_t P, int b, double *dots, bool zero_cross = false);
+// the same fold for P slabs of bb <= 128 doubles (the partials behind them at h->dots_ws + P bb)
+int slabs_fold(lz_handle *h, int64_t P, int bb, double *out, int zero_from = -1);
+
+// ---- batched conjugate gradients (lz_cg.hip)
+// k_cg_update: kCgThreads threads per block; the 128-byte-row form (b = 16 fp64, b = 32
+// fp32) covers kCgRows128 rows per block pass, the generic form kCgThreads / b; at most
+// kCgGridCap blocks, one slab of b doubles each, then grid-stride.  kCgCheckEvery: the
+// iterations lz_cg_solve enqueues between two reads of the live count by default.
+constexpr int kCgThreads = 256, kCgRows128 = 32, kCgGridCap = 2048, kCgCheckEvery = 8;
+// lz_cg_update (include/lz_hip.h)
+template <typename T>
+int cg_update(lz_handle *h, int64_t n, int b, const double *coef, T *R, const T *W, T *P, T *S, T *X, double *rr);
+// lz_cg_solve (include/lz_hip.h)
+template <typename T>
+int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+             double shift, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status, double *resid,
+             double *est, int *info);
 // lz_cheb_moments (include/lz_hip.h)
 template <typename T>
 int cheb_moments(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,

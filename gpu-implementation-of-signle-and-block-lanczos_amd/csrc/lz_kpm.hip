@@ -29,9 +29,9 @@ static int col_dots_grid(const lz_handle *h, int64_t n, int b)
     return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, rpb * 4), (int64_t)h->n_cu * 8));
 }
 
-int dots_reserve(lz_handle *h, int64_t n, int b)
+int dots_reserve(lz_handle *h, int64_t n, int b, int64_t min_slabs)
 {
-    const int64_t P = std::max<int64_t>(ceil_div(n, (int64_t)48), col_dots_grid(h, n, b));
+    const int64_t P = std::max<int64_t>({ceil_div(n, (int64_t)48), (int64_t)col_dots_grid(h, n, b), min_slabs});
     const size_t had = h->dots_cap;
     LZ_TRY(grow_ws(h, &h->dots_ws, &h->dots_cap, sizeof(double) * (size_t)(P + kDotsFoldBlocks) * 2 * (size_t)b));
     // test support, as lz_init's: a workspace grown under LZ_POISON=1 starts NaN-filled
@@ -119,7 +119,13 @@ __global__ __launch_bounds__(256) void k_dots_fold(const double *__restrict__ pa
 // 256, else two (the partials behind the slabs).  No host synchronisation.
 int dots_fold(lz_handle *h, int64_t P, int b, double *dots, bool zero_cross)
 {
-    const int bb = 2 * b, zf = zero_cross ? b : bb;
+    return slabs_fold(h, P, 2 * b, dots, zero_cross ? b : 2 * b);
+}
+
+// The same for slabs of bb <= 128 doubles (zero_from < bb: out[zero_from ..) = 0).
+int slabs_fold(lz_handle *h, int64_t P, int bb, double *dots, int zero_from)
+{
+    const int zf = zero_from < 0 ? bb : zero_from;
     const double *src = h->dots_ws;
     const int ev = prof_begin(h, PROF_SMALL);
     if (P > kDotsFoldBlocks) {

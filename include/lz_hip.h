@@ -396,6 +396,55 @@ int lz_block_lanczos_reorth_resume_series(lz_handle *h, int64_t n, int64_t nnz, 
                                           int64_t vstride, void *W, int passes, int degree, double lo, double hi,
                                           const double *gamma, void *work);
 
+/* ----------------------------- batched conjugate gradients (no reference counterpart)
+ * The row-local half of one Chronopoulos-Gear step on n x b row-major blocks with
+ * ld = b, n >= 1, 1 <= b <= 64, either dtype, the coefficients per column and on the
+ * device: with alpha_c = coef[c] and beta_c = coef[b + c] rounded once to the blocks'
+ * dtype,
+ *   P = fma(beta, P, R),  S = fma(beta, S, W),  X = fma(alpha, P, X),  R = fma(-alpha, S, R)
+ * element by element in that order (the new P and S feed X and R), and rr[c] =
+ * sum_i R[i][c]^2 of the stored R, products and sums in fp64 in a fixed order.  A zero
+ * coefficient skips its product: beta_c == 0 stores P = R, S = W whatever column c of
+ * P and S held, alpha_c == 0 leaves column c of X and R bit for bit.  coef (2 b
+ * doubles) and W are read only; rr: b doubles; all three in device memory.  One pass
+ * -- five blocks read, four written -- and one fold; no host synchronisation once the
+ * slab workspace has its size.  128-byte rows (b = 16 fp64, b = 32 fp32) on 16-byte
+ * aligned blocks move 16 bytes per lane; every other shape -- and LZ_CG_GENERIC=1, a
+ * measurement switch read per call -- one element per thread, the same bits in the
+ * four blocks (rr sums in another order).  LZ_CG_NT=0 (measurement): plain loads and
+ * stores where the 128-byte form uses non-temporal ones.  The five blocks must not
+ * overlap: LZ_E_ARG. */
+int lz_cg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *coef, void *R, const void *W, void *P,
+                 void *S, void *X, double *rr);
+/* tol: the relative residual a column must reach; max_iter: most steps of one column;
+ * check_every: the iterations enqueued between two reads of the live count (<= 0: the
+ * library's default); max_restarts: most residual replacements. */
+typedef struct {
+    double tol;
+    int max_iter, check_every, max_restarts;
+} lz_cg_opts;
+/* Solves (A + shift I) X = B for a symmetric positive definite A + shift I by
+ * conjugate gradients, the b columns in lock step and each by its own scalars; shift
+ * is rounded once to the solve's dtype.  B (read only), X (the start vector on entry,
+ * the solution on return): n x b row-major, ld = b; work: 4 n b elements, not read
+ * on entry; B, X and work pairwise distinct; n >= 1, 1 <= b <= 64, tol > 0, max_iter
+ * >= 0, max_restarts >= 0: anything else is LZ_E_ARG.  Per iteration: one
+ * lz_csr_spmm_axpby_dots (W = (A + shift I) R, with W.R), one one-workgroup launch
+ * for the scalars, one lz_cg_update; no host synchronisation but one 4-byte read of
+ * the live count per check_every iterations.  A column is frozen (alpha = beta = 0:
+ * its X does not change by a bit) once its recurrence residual reaches tol |B_c|,
+ * its steps reach max_iter, or its denominator is not positive.  When no column is
+ * live, R = B - (A + shift I) X is measured: columns that fail tol and have steps
+ * left run again from it (a restart), at most max_restarts times.  On the host:
+ * iters[b], status[b] (0: met tol on the measured residual; 1: iterations or
+ * restarts spent; 2: not positive definite on this Krylov space), resid[b] the
+ * measured |B_c - (A + shift I) X_c| / |B_c| (0 for a zero column), est[b] the
+ * recurrence's last value of it, info[3] = {iterations enqueued, restarts, SpMMs}.
+ * No preconditioner.  One column's arithmetic depends on no other column's data. */
+int lz_cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const void *val,
+                lz_dtype dtype, int b, double shift, const void *B, void *X, void *work, const lz_cg_opts *opts,
+                int *iters, int *status, double *resid, double *est, int *info);
+
 /* ------------------------- transpose and normal operator (no reference counterpart)
  * The CSR of A^T, built on the device: output row c (c < n_cols) holds the
  * entries of A whose column is c in the order of their positions in A's

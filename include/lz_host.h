@@ -128,6 +128,31 @@ int lzh_restart_fill(int r, int m, int b, const double *alpha, const double *bet
  * filter (lz_cheb in lz_hip.h) needs for the end of its damped interval.  fp64
  * values; n >= 1.  Returns 0, or -1 on a bad argument. */
 int lzh_gershgorin(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val, double out[2]);
+/* ------------------------------------------- batched conjugate gradients
+ * The per-column scalar rules of lz_cg_solve (lz_hip.h), the very code its
+ * one-workgroup kernels run (csrc/lz_cg.hpp), on host arrays of b entries.  State per
+ * column: gamma_prev, alpha_prev (the last step's), est2 (the recurrence's gamma when
+ * the column last froze), live, iters, status (0 met tol, 1 not shown to, 2 not
+ * positive definite).  thr[c] = tol^2 |B_c|^2.  Both return 0 and the live count in
+ * *nlive, or -1 on a bad argument.
+ *
+ * lzh_cg_start: gamma[c] is the measured |B_c - M X_c|^2, rec[c] the recurrence's
+ * last gamma (unused when initial).  initial != 0 clears the state first; otherwise a
+ * column still marked live keeps rec as its est2.  A status-2 column stays frozen; gamma <= thr: frozen, status 0 (a zero
+ * column passes with 0 <= 0, nothing is divided); else status 1, live while iters <
+ * max_iter.
+ * lzh_cg_scalars: one iteration.  gamma[c] = R_c.R_c of the recurrence, delta[c] =
+ * (M R_c).R_c.  A live column with gamma <= thr or iters >= max_iter is frozen; a
+ * frozen column gets coef[c] = coef[b + c] = 0 and its state is untouched.  Otherwise
+ * beta = first ? 0 : gamma / gamma_prev, den = delta - beta gamma / alpha_prev (delta
+ * when first); den <= 0 or not finite: status 2, frozen for good, coefficients 0;
+ * else alpha = gamma / den, coef = [alpha(b) | beta(b)], gamma_prev = gamma,
+ * alpha_prev = alpha, iters += 1. */
+int lzh_cg_start(int b, int max_iter, int initial, const double *gamma, const double *rec, const double *thr,
+                 double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters, int *status, int *nlive);
+int lzh_cg_scalars(int b, int first, int max_iter, const double *gamma, const double *delta, const double *thr,
+                   double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters, int *status,
+                   double *coef, int *nlive);
 /* ------------------------------------------- kernel polynomial method
  * Chebyshev moments mu_k = x^T T_k(Ah) x of Ah = (A - c0) / e, e = (hi - lo) / 2,
  * c0 = (hi + lo) / 2, [lo, hi] enclosing the spectrum; their mean over random +-1
