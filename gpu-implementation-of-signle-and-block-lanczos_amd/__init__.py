@@ -58,6 +58,20 @@ TRANSPOSE_SHORT, TRANSPOSE_LDS, TRANSPOSE_SCAN_BLOCK = 16, 4096, 2048
 # of the live count
 CG_THREADS, CG_ROWS_128, CG_GRID_CAP, CG_CHECK_EVERY = 256, 32, 2048, 8
 CG_MET, CG_SPENT, CG_NOT_PD = 0, 1, 2  # Handle.solve's status per column
+# lz_bcg_update / lz_bcg_direction (csrc/lz_internal.hpp kBcg*): BCG_THREADS threads per block; the b = 16
+# fp64 MFMA form covers BCG_ROWS_16 rows per block pass (16-row tiles), the b = 32 fp32 one BCG_ROWS_32
+# (32-row tiles), the generic form BCG_ROWS_GEN; at
+# most BCG_GRID_CAP blocks (one b x b slab each), then grid-stride.  BCG_MAX_B: lz_bcg_solve's widest block
+BCG_THREADS, BCG_ROWS_16, BCG_ROWS_32, BCG_ROWS_GEN, BCG_GRID_CAP, BCG_MAX_B = 256, 64, 128, 16, 1024, 32
+LZ_K_BCG16, LZ_K_BCG32F, LZ_K_BCG_GEN = 13, 14, 15  # lz_debug_last_kernel's dense ids of the two passes
+# Handle.solve(method="block")'s stop reason (csrc/lz_bcg.hpp kBcg*)
+BCG_NONE, BCG_CONVERGED, BCG_SPENT, BCG_RANK, BCG_NOT_PD = 0, 1, 2, 3, 4
+
+
+def bcg_guard(b: int, eps: float) -> float:
+    """The block solver's rank guard: lambda_min > bcg_guard * lambda_max (lzh_bcg_guard)."""
+    return max(1e-10, 64.0 * b * eps)
+
 
 _c_i64, _c_i32, _c_int, _c_dbl, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_double, ctypes.c_void_p
 _c_u32, _c_u64 = ctypes.c_uint32, ctypes.c_uint64
@@ -121,6 +135,10 @@ HIP_SYMBOLS = [
     ("lz_cg_update", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_cg_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp,
                              _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lz_bcg_update", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lz_bcg_direction", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lz_bcg_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp,
+                              _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_block_lanczos_reorth_cheb", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int,
                                               _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int,
                                               _c_vp, _c_vp]),
@@ -201,6 +219,11 @@ HOST_SYMBOLS = [
                               _c_vp]),
     ("lzh_cg_scalars", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                 _c_vp, _c_vp]),
+    ("lzh_bcg_start", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lzh_bcg_start_finish", _c_int, [_c_int, _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lzh_bcg_mid", _c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lzh_bcg_end", _c_int, [_c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lzh_bcg_guard", _c_dbl, [_c_int, _c_dbl]),
     ("lzh_kpm_moments", _c_int, [_c_int, _c_int, _c_vp, _c_vp]),
     ("lzh_jackson", _c_int, [_c_int, _c_vp]),
     ("lzh_kpm_count", _c_int, [_c_int, _c_vp, _c_vp, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_vp]),
@@ -1009,8 +1032,44 @@ class Handle:
                                    _ptr(rr)), "lz_cg_update")
         return rr
 
+    def _bcg_factors(self, what: str, b: int, *ms):
+        torch = _torch()
+        for m in ms:
+            if m.dtype != torch.float64 or not m.is_contiguous() or m.numel() != b * b:
+                raise LanczosError(f"{what}: the b x b factors are contiguous fp64 tensors on the device")
+
+    def bcg_update(self, xi, E, S, W, Q, X, G=None):
+        """The update pass of one block conjugate-gradient iteration (lz_bcg_update): X += S E, Q -= W xi
+        and G = Q^T Q of the stored Q (b x b fp64 on the device; allocated when None).  xi, E: b x b
+        fp64 on the device, read only, rounded once to the blocks' dtype; S, W (read only), Q, X: (n, b)
+        contiguous, of one dtype, pairwise distinct, b <= BCG_MAX_B.  Returns G."""
+        torch = _torch()
+        n, b = S.shape
+        for t in (S, W, Q, X):
+            if tuple(t.shape) != (n, b) or t.dtype != S.dtype or not t.is_contiguous():
+                raise LanczosError("bcg_update: S, W, Q, X (n, b) contiguous (ld = b), of one dtype")
+        self._bcg_factors("bcg_update", b, xi, E)
+        if G is None:
+            G = torch.empty(b, b, dtype=torch.float64, device=S.device)
+        self._bcg_factors("bcg_update", b, G)
+        _check(self.L.lz_bcg_update(self.ptr, n, b, _dt(S), _ptr(xi), _ptr(E), _ptr(S), _ptr(W), _ptr(Q), _ptr(X),
+                                    _ptr(G)), "lz_bcg_update")
+        return G
+
+    def bcg_direction(self, z, zinv, Q, S):
+        """The direction pass of one block conjugate-gradient iteration (lz_bcg_direction): Q <- Q zinv,
+        then S <- Q + S z with the new Q, in place.  z (symmetric), zinv: b x b fp64 on the device; Q, S:
+        (n, b) contiguous, of one dtype, distinct."""
+        n, b = Q.shape
+        if tuple(S.shape) != (n, b) or S.dtype != Q.dtype or not S.is_contiguous() or not Q.is_contiguous():
+            raise LanczosError("bcg_direction: Q, S (n, b) contiguous (ld = b), of one dtype")
+        self._bcg_factors("bcg_direction", b, z, zinv)
+        _check(self.L.lz_bcg_direction(self.ptr, n, b, _dt(Q), _ptr(z), _ptr(zinv), _ptr(Q), _ptr(S)),
+               "lz_bcg_direction")
+
     def solve(self, A: CsrDevice, B, shift: float = 0.0, tol: Optional[float] = None, max_iter: Optional[int] = None,
-              X0=None, check_every: Optional[int] = None, max_restarts: int = 3, work=None):
+              X0=None, check_every: Optional[int] = None, max_restarts: int = 3, work=None,
+              method: str = "columns"):
         """Solves (A + shift I) X = B for a symmetric positive definite A + shift I by conjugate
         gradients, the b <= 64 columns of B in lock step, each by its own scalars (lz_cg_solve).
 
@@ -1027,11 +1086,24 @@ class Handle:
         it run again from it, at most max_restarts times.  A column whose B holds a NaN ends at
         once with status 2 (its denominator is not finite), its X untouched.
 
+        method="block" (lz_bcg_solve, b <= BCG_MAX_B): block conjugate gradients, the columns
+        sharing one Krylov space, so the rate follows lambda_max / lambda_b instead of lambda_max /
+        lambda_1 -- fewer iterations on Laplacian-like operators, none fewer (and more work per
+        iteration) on a well-conditioned one.  Same arguments; iters is the block's count for
+        every column; status 2 is the block's diagnosis, given to every column that is not met.
+        A start or restart whose residual block is rank deficient (a zero or duplicated column,
+        b > n, an exhausted Krylov space) hands the rest to the column method (fallback = 1).
+
         Returns a dict: X; iters, status (0 met tol on the measured residual, 1 iterations or
         restarts spent, 2 not positive definite), converged (status == 0), resid (measured), est
-        (the recurrence's last value) -- NumPy arrays of b entries; restarts, n_spmm, iterations."""
+        (the recurrence's last value) -- NumPy arrays of b entries; restarts, n_spmm, iterations;
+        with method="block" also fallback (0 / 1) and stop (BCG_* reason of the last stop)."""
         torch = _torch()
+        if method not in ("columns", "block"):
+            raise LanczosError('solve: method is "columns" or "block"')
         n, b = self._blocks("solve", A, B)
+        if method == "block" and b > BCG_MAX_B:
+            raise LanczosError(f'solve: method="block" takes b <= {BCG_MAX_B}')
         f64 = A.val.dtype == torch.float64
         tol = (1e-10 if f64 else 1e-4) if tol is None else float(tol)
         max_iter = min(10 * n, 10000) if max_iter is None else int(max_iter)
@@ -1046,6 +1118,14 @@ class Handle:
         opts = CgOpts(tol, max_iter, 0 if check_every is None else int(check_every), int(max_restarts))
         iters, status = np.zeros(b, np.int32), np.zeros(b, np.int32)
         resid, est, info = np.zeros(b), np.zeros(b), np.zeros(3, np.int32)
+        if method == "block":
+            info = np.zeros(5, np.int32)
+            _check(self.L.lz_bcg_solve(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                       float(shift), _ptr(B), _ptr(X), _ptr(work), ctypes.addressof(opts), _p(iters),
+                                       _p(status), _p(resid), _p(est), _p(info)), "lz_bcg_solve")
+            return {"X": X, "iters": iters, "status": status, "converged": status == 0, "resid": resid, "est": est,
+                    "iterations": int(info[0]), "restarts": int(info[1]), "n_spmm": int(info[2]),
+                    "fallback": int(info[3]), "stop": int(info[4])}
         _check(self.L.lz_cg_solve(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
                                   float(shift), _ptr(B), _ptr(X), _ptr(work), ctypes.addressof(opts), _p(iters),
                                   _p(status), _p(resid), _p(est), _p(info)), "lz_cg_solve")

@@ -1631,6 +1631,7 @@ int lz_finalize(lz_handle *h)
     (void)hipFree(h->cm_buf);
     (void)hipFree(h->dots_ws);
     (void)hipFree(h->cg_ws);
+    (void)hipFree(h->bcg_ws);
     (void)hipFree(h->ybuf);
     (void)hipFree(h->coef);
     (void)hipFree(h->tr_ws);
@@ -1710,6 +1711,7 @@ int lz_debug_poison_lds(lz_handle *h, uint32_t pattern)
     LZ_HIP_TRY(hipMemsetAsync(h->scratch, byte, sizeof(double) * kScratchDoubles, h->stream));
     if (h->dots_ws) LZ_HIP_TRY(hipMemsetAsync(h->dots_ws, byte, h->dots_cap, h->stream));
     if (h->cg_ws) LZ_HIP_TRY(hipMemsetAsync(h->cg_ws, byte, h->cg_cap, h->stream));
+    if (h->bcg_ws) LZ_HIP_TRY(hipMemsetAsync(h->bcg_ws, byte, h->bcg_cap, h->stream));
     return LZ_OK;
 }
 
@@ -2198,6 +2200,61 @@ int lz_cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const i
         using T = decltype(t);
         return cg_solve<T>(h, n, nnz, rp, col, (const T *)val, b, shift, (const T *)B, (T *)X, (T *)work, *opts, iters,
                            status, resid, est, info);
+    });
+}
+
+int lz_bcg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *xi, const double *E, const void *S,
+                  const void *W, void *Q, void *X, double *G)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= 32, "n >= 1, b in [1,32]");
+    LZ_ARG_CHECK(xi && E && S && W && Q && X && G, "xi/E/S/W/Q/X/G NULL");
+    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
+    const void *blk[4] = {S, W, Q, X};
+    bool apart = true;
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j) apart = apart && blocks_apart(blk[i], nb, blk[j], nb, es);
+    LZ_ARG_CHECK(apart, "S, W, Q and X must be pairwise distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return bcg_update<T>(h, n, b, xi, E, (const T *)S, (const T *)W, (T *)Q, (T *)X, G);
+    });
+}
+
+int lz_bcg_direction(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *z, const double *zinv, void *Q,
+                     void *S)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= 32, "n >= 1, b in [1,32]");
+    LZ_ARG_CHECK(z && zinv && Q && S, "z/zinv/Q/S NULL");
+    LZ_ARG_CHECK(blocks_apart(Q, n * b, S, n * b, dtype == LZ_F64 ? 8 : 4), "Q and S must be distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return bcg_direction<T>(h, n, b, z, zinv, (T *)Q, (T *)S);
+    });
+}
+
+int lz_bcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                 lz_dtype dtype, int b, double shift, const void *B, void *X, void *work, const lz_cg_opts *opts,
+                 int *iters, int *status, double *resid, double *est, int *info)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= 32, "n >= 1, b in [1,32]");
+    LZ_ARG_CHECK(B && X && work && opts && iters && status && resid && est && info, "NULL argument");
+    LZ_ARG_CHECK(opts->tol > 0.0 && std::isfinite(opts->tol) && std::isfinite(shift), "tol > 0, tol and shift finite");
+    LZ_ARG_CHECK(opts->max_iter >= 0 && opts->max_restarts >= 0, "max_iter, max_restarts >= 0");
+    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
+    LZ_ARG_CHECK(blocks_apart(B, nb, X, nb, es) && blocks_apart(work, 4 * nb, B, nb, es) &&
+                     blocks_apart(work, 4 * nb, X, nb, es),
+                 "B, X and work must be pairwise distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return bcg_solve<T>(h, n, nnz, rp, col, (const T *)val, b, shift, (const T *)B, (T *)X, (T *)work, *opts,
+                            iters, status, resid, est, info);
     });
 }
 

@@ -15,6 +15,7 @@
 #include "lz_cg.hpp"
 #include "lz_common.hpp"
 #include "lz_internal.hpp"
+#include "lz_kernels.hpp"
 
 namespace lz {
 
@@ -48,23 +49,6 @@ template <>
 struct Vec16<float> {
     typedef float type __attribute__((ext_vector_type(4)));
 };
-
-template <bool NT, typename V>
-__device__ inline V ld16(const V *p)
-{
-    if constexpr (NT)
-        return __builtin_nontemporal_load(p);
-    else
-        return *p;
-}
-template <bool NT, typename V>
-__device__ inline void st16(V *p, V v)
-{
-    if constexpr (NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
-}
 
 // Both forms finish every element in this order, alpha and beta being the
 // column's coef entries rounded once to T:
@@ -104,10 +88,10 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update128(int64_t n, const do
     for (int64_t row = (int64_t)blockIdx.x * kCgRows128 + rl; row < n; row += step) {
         const int64_t i = row * 8 + l;  // in 16-byte units
         V r = reinterpret_cast<const V *>(R)[i];
-        const V w = ld16<NT>(reinterpret_cast<const V *>(W) + i);
-        V p = ld16<NT>(reinterpret_cast<const V *>(P) + i);
-        V s = ld16<NT>(reinterpret_cast<const V *>(S) + i);
-        V x = ld16<NT>(reinterpret_cast<const V *>(X) + i);
+        const V w = ldnt<NT>(reinterpret_cast<const V *>(W) + i);
+        V p = ldnt<NT>(reinterpret_cast<const V *>(P) + i);
+        V s = ldnt<NT>(reinterpret_cast<const V *>(S) + i);
+        V x = ldnt<NT>(reinterpret_cast<const V *>(X) + i);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
             p[v] = be[v] == T(0) ? r[v] : fma(be[v], p[v], r[v]);
@@ -116,9 +100,9 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update128(int64_t n, const do
             r[v] = al[v] == T(0) ? r[v] : fma(-al[v], s[v], r[v]);
             acc[v] = fma((double)r[v], (double)r[v], acc[v]);
         }
-        st16<NT>(reinterpret_cast<V *>(P) + i, p);
-        st16<NT>(reinterpret_cast<V *>(S) + i, s);
-        st16<NT>(reinterpret_cast<V *>(X) + i, x);
+        stnt<NT>(reinterpret_cast<V *>(P) + i, p);
+        stnt<NT>(reinterpret_cast<V *>(S) + i, s);
+        stnt<NT>(reinterpret_cast<V *>(X) + i, x);
         reinterpret_cast<V *>(R)[i] = r;
     }
 #pragma unroll

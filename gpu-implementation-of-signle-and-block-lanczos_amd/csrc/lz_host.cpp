@@ -4,6 +4,7 @@
 
 #include <omp.h>
 
+#include "lz_bcg.hpp"
 #include "lz_cg.hpp"
 
 #include <algorithm>
@@ -687,6 +688,45 @@ int lzh_cg_scalars(int b, int first, int max_iter, const double *gamma, const do
     }
     return 0;
 }
+
+// ---- block conjugate gradients: the b x b rules of lz_bcg.hpp, as the one-workgroup kernels of
+// lz_bcg.hip apply them, on host arrays; ctl = {live, reason, iters, 0}
+static bool bcg_args(int b, const int *ctl) { return b >= 1 && b <= lz::kBcgMaxB && ctl; }
+
+int lzh_bcg_start(int b, int max_iter, const double *G, const double *thr, int *ctl, double *gamma, double *d,
+                  double *Gs)
+{
+    if (!bcg_args(b, ctl) || !G || !thr || !gamma || !d || !Gs) return -1;
+    lz::bcg_start_rule(lz::BcgSerial{}, b, G, thr, max_iter, reinterpret_cast<lz::BcgCtl *>(ctl), gamma, d, Gs);
+    return 0;
+}
+
+int lzh_bcg_start_finish(int b, double ratio, const double *eig, const double *Cp, const double *Cpi, const double *d,
+                         int *ctl, double *C, double *T)
+{
+    if (!bcg_args(b, ctl) || !eig || !Cp || !Cpi || !d || !C || !T) return -1;
+    lz::bcg_start_finish_rule(lz::BcgSerial{}, b, ratio, eig, Cp, Cpi, d, reinterpret_cast<lz::BcgCtl *>(ctl), C, T);
+    return 0;
+}
+
+int lzh_bcg_mid(int b, const double *eig, const double *dis, const double *C, int *ctl, double *xi, double *E)
+{
+    if (!bcg_args(b, ctl) || !eig || !dis || !C || !xi || !E) return -1;
+    lz::bcg_mid_rule(lz::BcgSerial{}, b, eig, dis, C, reinterpret_cast<lz::BcgCtl *>(ctl), xi, E);
+    return 0;
+}
+
+int lzh_bcg_end(int b, int max_iter, double ratio, const double *eig, const double *z, const double *zinv,
+                const double *thr, int *ctl, double *C, double *est2)
+{
+    if (!bcg_args(b, ctl) || !eig || !z || !zinv || !thr || !C || !est2) return -1;
+    double tmp[lz::kBcgMaxB * lz::kBcgMaxB];
+    lz::bcg_end_rule(lz::BcgSerial{}, b, max_iter, ratio, eig, z, zinv, thr, reinterpret_cast<lz::BcgCtl *>(ctl), C,
+                     tmp, est2);
+    return 0;
+}
+
+double lzh_bcg_guard(int b, double eps) { return lz::bcg_guard(b, eps); }
 
 // ---- kernel polynomial method (lz_cheb_moments' raw dots -> moments -> counts, density)
 int lzh_kpm_moments(int K, int b, const double *dots, double *mu)

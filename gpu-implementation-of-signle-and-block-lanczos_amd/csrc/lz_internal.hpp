@@ -64,6 +64,24 @@ template <typename T>
 int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
              double shift, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status, double *resid,
              double *est, int *info);
+// ---- block conjugate gradients (lz_bcg.hip)
+// k_bcg_update / k_bcg_direction: kBcgThreads threads per block; the b = 16 fp64 MFMA
+// form covers kBcgRows16 rows per block pass (one 16-row tile per wave), the b = 32 fp32
+// one kBcgRows32 (a 32-row tile per wave), the generic form kBcgRowsGen; at most kBcgGridCap blocks, one b x b slab each, then grid-stride.
+// The one-workgroup rule kernels run kBcgRuleThreads threads.
+constexpr int kBcgThreads = 256, kBcgRows16 = 64, kBcgRows32 = 128, kBcgRowsGen = 16, kBcgGridCap = 1024, kBcgRuleThreads = 256;
+// lz_bcg_update (include/lz_hip.h)
+template <typename T>
+int bcg_update(lz_handle *h, int64_t n, int b, const double *xi, const double *E, const T *S, const T *W, T *Q, T *X,
+               double *G);
+// lz_bcg_direction (include/lz_hip.h)
+template <typename T>
+int bcg_direction(lz_handle *h, int64_t n, int b, const double *z, const double *zinv, T *Q, T *S);
+// lz_bcg_solve (include/lz_hip.h)
+template <typename T>
+int bcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+              double shift, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status, double *resid,
+              double *est, int *info);
 // lz_cheb_moments (include/lz_hip.h)
 template <typename T>
 int cheb_moments(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,

@@ -93,6 +93,25 @@ __device__ __forceinline__ void stv(T *p, const Vec<T, VEC> &r)
     }
 }
 
+// One load / store of a scalar or ext-vector V, non-temporal when NT (a stream nothing
+// reads again before the caches have turned over), plain otherwise.
+template <bool NT, typename V>
+__device__ __forceinline__ V ldnt(const V *p)
+{
+    if constexpr (NT)
+        return __builtin_nontemporal_load(p);
+    else
+        return *p;
+}
+template <bool NT, typename V>
+__device__ __forceinline__ void stnt(V *p, V v)
+{
+    if constexpr (NT)
+        __builtin_nontemporal_store(v, p);
+    else
+        *p = v;
+}
+
 // v_mfma_f64_16x16x4_f64: D(16x16) += A(16x4) * B(4x16).
 // Lane l supplies A[l&15][l>>4] and B[l>>4][l&15]; D lane l holds
 // D[(l>>4) + 4*r][l&15], r = 0..3 -- i.e. for each r, element l of a

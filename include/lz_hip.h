@@ -445,6 +445,75 @@ int lz_cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, co
                 lz_dtype dtype, int b, double shift, const void *B, void *X, void *work, const lz_cg_opts *opts,
                 int *iters, int *status, double *resid, double *est, int *info);
 
+/* ----------------------------- block conjugate gradients (no reference counterpart)
+ * The b columns share one Krylov space: Dubrulle's BCGrQ with the symmetric
+ * orthonormalisation of lz_sqrtm_pair in place of the QR.  M = A + shift I; the
+ * residual is held as R = Q C with Q^T Q = I and C b x b fp64 on the device.  One
+ * iteration: W = M S (one SpMM); D = sym(S^T W); the mid rule xi = D^-1/2 D^-1/2, E =
+ * xi C (a smallest eigenvalue of D that is <= 0 or not finite stops the solve as not
+ * positive definite, X untouched by that iteration); lz_bcg_update; the end rule z =
+ * (Q^T Q)^1/2, C <- z C, est_c^2 = sum_k C[k][c]^2; lz_bcg_direction.  Its rate is
+ * governed by lambda_max / lambda_b instead of lambda_max / lambda_1.
+ *
+ * lz_bcg_update: X <- X + S E and Q <- Q - W xi on n x b row-major blocks (ld = b, n
+ * >= 1, 1 <= b <= 32, either dtype), and G (b x b fp64, device) = Q^T Q of the stored
+ * Q, products and sums in fp64, one slab per workgroup folded in a fixed order (no
+ * atomics: two runs give the same bits).  xi and E: b x b row-major fp64 on the
+ * device, read only, rounded once to the blocks' dtype.  128-byte rows on 16-byte
+ * aligned blocks run on the MFMA: b = 16 fp64 on v_mfma_f64_16x16x4f64, b = 32 fp32
+ * on v_mfma_f32_32x32x2f32 with its Q^T Q taken from the stored fp32 values on the
+ * f64 MFMA; every other shape -- and LZ_BCG_GENERIC=1, a measurement switch read per
+ * call -- a generic kernel (same values within rounding, other summation order).
+ * lz_debug_last_kernel's dense id says which ran (LZ_K_BCG16, LZ_K_BCG32F,
+ * LZ_K_BCG_GEN).  The fp64 MFMA form moves S, W, X (update) and Q (direction) with
+ * non-temporal loads and stores, the fp32 one with plain ones, as measured;
+ * LZ_BCG_NT=0 / 1 (measurement) forces plain / non-temporal at both.  S, W, Q, X must
+ * not overlap: LZ_E_ARG.
+ * lz_bcg_direction: Q <- Q zinv, then S <- Q + S z (z symmetric) with the new Q, in
+ * place and row-local; z, zinv as xi and E above.  Q and S must not overlap. */
+int lz_bcg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *xi, const double *E, const void *S,
+                  const void *W, void *Q, void *X, double *G);
+int lz_bcg_direction(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *z, const double *zinv, void *Q,
+                     void *S);
+/* Solves (A + shift I) X = B for a symmetric positive definite A + shift I by block
+ * conjugate gradients.  Arguments as lz_cg_solve's (B read only; X the start block
+ * on entry, the solution on return; work 4 n b elements, not read on entry; the
+ * three pairwise distinct; the same lz_cg_opts), but 1 <= b <= 32 (lz_sqrtm_pair's
+ * limit), else LZ_E_ARG.
+ * Start, and every restart: R = B - M X is measured (one SpMM), G = R^T R; gamma_c =
+ * G_cc is column c's squared residual and the column is met when gamma_c <= tol^2
+ * |B_c|^2.  All met: done.  Otherwise G is scaled to a unit diagonal (b x b work
+ * only), (C', C'^-1) = sqrtm_pair of it, C = C' D, Q = R D^-1 C'^-1, S = Q.
+ * Rank guard, on that scaled Gram at a start and on Q^T Q in every end rule:
+ * lambda_min > g lambda_max with g = max(1e-10, 64 b eps(dtype)) and every entry of
+ * the square-root pair finite.  Tripped in an iteration: the iterations stop and the
+ * solve restarts from the measured residual.  Tripped at a start or restart (a zero
+ * column, a duplicated column, b > n, a Krylov space that ran out): the remaining
+ * work goes to lz_cg_solve from the current X with the iterations that are left,
+ * its per-column results are merged and info[3] = 1 -- at most once per solve, so a
+ * rank-deficient block does not fail where the column method succeeds.  What the
+ * fallback does not cover: the block recurrence's attainable residual is worse than
+ * the column method's.  Where tol lies at what the dtype can hold for the right-hand
+ * sides (|x| / |b| near 1 / lambda_min), the column method may still meet it when the
+ * block method ends with status 1 after max_restarts (measured: 4.8e-10 against
+ * 1.2e-10 on the 3162 x 3162 Laplacian in fp64, neither meeting 1e-10).
+ * The state holds a live word; the update, the direction pass and both rules read
+ * it first and return at once when it is 0, so the iterations enqueued behind a
+ * stop (converged by the estimate, max_iter spent, rank, not positive definite)
+ * leave X, C and the counters bit for bit.  The host reads that word once per
+ * check_every iterations; when it is 0 the start step measures the true residual:
+ * all met -- done; not positive definite -- status 2 for every column that is not
+ * met (the block shares one Krylov space, so the diagnosis is the block's, not a
+ * column's); iterations spent -- status 1; otherwise a restart, at most max_restarts
+ * times, then status 1.  On the host: iters[b] (the block's count for every column,
+ * plus the column's own after a fallback), status[b], resid[b] (measured), est[b]
+ * (the recurrence's), info[5] = {iterations enqueued, restarts, SpMMs, fallback,
+ * stop reason (0 none, 1 converged, 2 spent, 3 rank, 4 not positive definite)}.
+ * No preconditioner. */
+int lz_bcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const void *val,
+                 lz_dtype dtype, int b, double shift, const void *B, void *X, void *work, const lz_cg_opts *opts,
+                 int *iters, int *status, double *resid, double *est, int *info);
+
 /* ------------------------- transpose and normal operator (no reference counterpart)
  * The CSR of A^T, built on the device: output row c (c < n_cols) holds the
  * entries of A whose column is c in the order of their positions in A's
@@ -582,7 +651,10 @@ enum {
     LZ_K_PAPPLY16 = 9,  /* panel apply, b = 16 fp64 MFMA (lz_panel_apply) */
     LZ_K_PAPPLY_GEN = 10, /* panel apply, any other shape */
     LZ_K_PCOMP16 = 11,   /* panel compress, b = 16 fp64 MFMA (lz_panel_compress) */
-    LZ_K_PCOMP_GEN = 12  /* panel compress, any other shape */
+    LZ_K_PCOMP_GEN = 12, /* panel compress, any other shape */
+    LZ_K_BCG16 = 13,     /* lz_bcg_update / lz_bcg_direction, b = 16 fp64 MFMA */
+    LZ_K_BCG32F = 14,    /* ... b = 32 fp32 MFMA */
+    LZ_K_BCG_GEN = 15    /* ... any other shape */
 };
 int lz_debug_last_kernel(lz_handle *h, int out[2]);
 

@@ -153,6 +153,34 @@ int lzh_cg_start(int b, int max_iter, int initial, const double *gamma, const do
 int lzh_cg_scalars(int b, int first, int max_iter, const double *gamma, const double *delta, const double *thr,
                    double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters, int *status,
                    double *coef, int *nlive);
+/* ------------------------------------------- block conjugate gradients
+ * The b x b rules of lz_bcg_solve (lz_hip.h), the very code its one-workgroup
+ * kernels run (csrc/lz_bcg.hpp), on host arrays; every matrix b x b row-major fp64, 1
+ * <= b <= 32.  ctl = {live, reason, iters, 0}; reason: 0 none, 1 converged, 2 spent, 3
+ * rank, 4 not positive definite.  A rule whose ctl is not live writes nothing (the
+ * start rule always runs).  Each returns 0, or -1 on a bad argument.
+ *
+ * lzh_bcg_start: G = R^T R measured, thr[c] = tol^2 |B_c|^2.  gamma[c] = G[c][c], d[c]
+ * = sqrt(gamma[c]), Gs = D^-1 sym(G) D^-1 with a unit diagonal (a zero or non-finite
+ * column: a zero row and column).  Every gamma <= thr: live 0, converged; else a
+ * reason of 4 is kept (live 0); else iters >= max_iter: live 0, spent; else live 1.
+ * lzh_bcg_start_finish: (Cp, Cpi) = the square-root pair of Gs, eig its eigenvalues.
+ * Guard: eig finite, min > ratio max, the pair finite; tripped: live 0, rank.  Else C
+ * = Cp D, T = D^-1 Cpi (Q = R T).
+ * lzh_bcg_mid: dis = D^-1/2 and eig of D = sym(S^T W).  min eig <= 0 or anything not
+ * finite: live 0, not positive definite.  Else xi = dis dis, E = xi C.
+ * lzh_bcg_end: (z, zinv) and eig of Q^T Q.  iters += 1; the guard as above (tripped:
+ * live 0, rank, C kept); else C <- z C, est2[c] = sum_k C[k][c]^2; all est2 <= thr:
+ * live 0, converged; else iters >= max_iter: live 0, spent.
+ * lzh_bcg_guard: max(1e-10, 64 b eps). */
+int lzh_bcg_start(int b, int max_iter, const double *G, const double *thr, int *ctl, double *gamma, double *d,
+                  double *Gs);
+int lzh_bcg_start_finish(int b, double ratio, const double *eig, const double *Cp, const double *Cpi, const double *d,
+                         int *ctl, double *C, double *T);
+int lzh_bcg_mid(int b, const double *eig, const double *dis, const double *C, int *ctl, double *xi, double *E);
+int lzh_bcg_end(int b, int max_iter, double ratio, const double *eig, const double *z, const double *zinv,
+                const double *thr, int *ctl, double *C, double *est2);
+double lzh_bcg_guard(int b, double eps);
 /* ------------------------------------------- kernel polynomial method
  * Chebyshev moments mu_k = x^T T_k(Ah) x of Ah = (A - c0) / e, e = (hi - lo) / 2,
  * c0 = (hi + lo) / 2, [lo, hi] enclosing the spectrum; their mean over random +-1
