@@ -46,6 +46,15 @@ int grow_ws(lz_handle *h, void **buf, size_t *cap_bytes, size_t bytes)
     return LZ_OK;
 }
 
+int grow_ws_poisoned(lz_handle *h, void **buf, size_t *cap_bytes, size_t bytes)
+{
+    const size_t had = *cap_bytes;
+    LZ_TRY(grow_ws(h, buf, cap_bytes, bytes));
+    if (const char *pz = getenv("LZ_POISON"); *cap_bytes != had && pz && pz[0] == '1')
+        LZ_HIP_TRY(hipMemsetAsync(*buf, 0xFF, *cap_bytes, h->stream));
+    return LZ_OK;
+}
+
 int ensure_partials(lz_handle *h, size_t doubles)
 {
     return grow_ws(h, &h->partials, &h->partials_cap, doubles * sizeof(double));
@@ -268,15 +277,6 @@ static bool ax3dot_fused()
     return !(e && e[0] == '0');
 }
 
-static int cheb_args(const lz_cheb *f)
-{
-    LZ_ARG_CHECK(f->degree >= 1 && f->degree <= 256, "Chebyshev filter: 1 <= degree <= 256");
-    LZ_ARG_CHECK(std::isfinite(f->lo) && std::isfinite(f->hi) && std::isfinite(f->ref) && f->lo < f->hi,
-                 "Chebyshev filter: lo < hi, finite");
-    LZ_ARG_CHECK(f->ref < f->lo || f->ref > f->hi, "Chebyshev filter: ref outside [lo, hi]");
-    return LZ_OK;
-}
-
 // Y = p(A) X, the Zhou-Saad scaled Chebyshev filter (lz_cheb_apply): `degree`
 // three-term steps, one spmm_axpby each, coefficients on the host.  Step i
 // writes buffer (i + 2 - degree) mod 3 of {work_0, work_1, Y}: the last step
@@ -303,22 +303,12 @@ static int cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, c
     return LZ_OK;
 }
 
-// A Chebyshev series on the enclosure [lo, hi] (lz_cheb_series_apply): gamma is degree + 1 host
-// doubles, work the 2 n b elements of the solve's dtype its steps rotate through
-struct SeriesArgs {
+// A Chebyshev series on the enclosure [lo, hi] (lz_cheb_series_apply): gamma is degree + 1 host doubles
+struct ChebSeries {
     int degree;
     double lo, hi;
     const double *gamma;
-    void *work;
 };
-
-static int series_args(const SeriesArgs *sr)
-{
-    LZ_ARG_CHECK(sr->degree >= 1 && sr->degree <= 65536, "Chebyshev series: 1 <= degree <= 65536");
-    LZ_ARG_CHECK(std::isfinite(sr->lo) && std::isfinite(sr->hi) && sr->lo < sr->hi, "Chebyshev series: lo < hi, finite");
-    LZ_ARG_CHECK(sr->gamma != nullptr, "Chebyshev series: gamma is NULL");
-    return LZ_OK;
-}
 
 // Y = sum_k gamma_k T_k(Ah) X by Clenshaw's recurrence (lz_cheb_series_apply): with D = degree,
 // step 1 is b_{D-1} = gamma_{D-1} X + 2 Ah (gamma_D X), a three-term step on X; step i >= 2 is
@@ -327,7 +317,7 @@ static int series_args(const SeriesArgs *sr)
 // 2 Ah.  Step i writes buffer (i + 2 - D) mod 3 of {work_0, work_1, Y}, as cheb_apply does.
 template <typename T>
 static int cheb_series_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
-                             const T *val, int b, const SeriesArgs &sr, const T *X, T *Y, T *work)
+                             const T *val, int b, const ChebSeries &sr, const T *X, T *Y, T *work)
 {
     const int D = sr.degree;
     const double e = 0.5 * (sr.hi - sr.lo), c0 = 0.5 * (sr.hi + sr.lo);
@@ -352,71 +342,144 @@ static int cheb_series_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t
     return LZ_OK;
 }
 
-// The operator of a kept-basis solve, in one of four forms:
-//   A          f == nullptr, p == 0: the n x n CSR (rp, col, val)
-//   p(A)       f != nullptr: the Chebyshev filter on it, work 2 n b elements
-//   s(A)       sr != nullptr: a Chebyshev series on it, work 2 n b elements
-//   P^T (P Q)  p > 0: (rp, col, val) is P, p x n, and (trp, tcol, tval) its n x p
-//              transpose Pt; work p b elements
-template <typename T>
-struct ReorthOp {
+// ---- the entry points' buffer rules: a buffer is the bytes [p, p + bytes); {nullptr, 0} (an
+// argument the call does not use) is apart from everything
+struct Span {
+    const void *p = nullptr;
+    int64_t bytes = 0;
+};
+
+static int64_t elem_bytes(lz_dtype dtype) { return dtype == LZ_F64 ? 8 : 4; }
+
+// `elems` elements of the dtype at p
+static Span span_of(const void *p, int64_t elems, lz_dtype dtype) { return Span{p, elems * elem_bytes(dtype)}; }
+
+// A basis panel is ONE span, (k - 1) vstride + n b elements from V: the padding between two blocks
+// belongs to it
+static Span panel_span(const void *V, int64_t n, int b, int k, int64_t vstride, lz_dtype dtype)
+{
+    return span_of(V, (int64_t)(k - 1) * vstride + n * b, dtype);
+}
+
+// the overlap rule: one ends where or before the other starts (touching is apart)
+static bool apart(Span a, Span c)
+{
+    const char *p = (const char *)a.p, *q = (const char *)c.p;
+    return p + a.bytes <= q || q + c.bytes <= p;
+}
+
+// a apart from each of `others`
+static bool apart(Span a, std::initializer_list<Span> others)
+{
+    return std::all_of(others.begin(), others.end(), [&](Span o) { return apart(a, o); });
+}
+
+static bool pairwise_apart(std::initializer_list<Span> s)
+{
+    for (const Span *i = s.begin(); i != s.end(); ++i)
+        if (!std::all_of(i + 1, s.end(), [&](Span o) { return apart(*i, o); })) return false;
+    return true;
+}
+
+// The operator of a kept-basis solve or of an apply entry, whatever the dtype, in one of four forms:
+//   Plain   A: the n x n CSR (rp, col, val); no work
+//   Filter  p(A): the Chebyshev filter f on it; work 2 n b elements
+//   Series  s(A): the Chebyshev series sr on it; work 2 n b elements
+//   Normal  P^T (P Q): (rp, col, val) is P, p x n, and (t_rp, t_col, t_val) its n x p transpose;
+//           work the p b elements between the two SpMMs
+struct OpSpec {
+    enum Form { Plain, Filter, Series, Normal } form;
     int64_t nnz;
     const int64_t *rp;
     const int32_t *col;
-    const T *val;
-    const lz_cheb *f = nullptr;
-    T *work = nullptr;
-    const SeriesArgs *sr = nullptr;
-    int64_t p = 0;
-    const int64_t *trp = nullptr;
-    const int32_t *tcol = nullptr;
-    const T *tval = nullptr;
-};
-
-// the normal-operator form of a kept-basis solve: P is the entry point's CSR (p x n), this its
-// transpose and the p b elements between the two SpMMs
-struct NormalArgs {
+    const void *val;
+    void *work;
+    lz_cheb f;
+    ChebSeries sr;
     int64_t p;
     const int64_t *t_rp;
     const int32_t *t_col;
     const void *t_val;
-    void *work;
+
+    // f == NULL: the plain operator (the _cheb entry points' way to say so)
+    static OpSpec filter(int64_t nnz, const int64_t *rp, const int32_t *col, const void *val, const lz_cheb *f, void *work)
+    {
+        return OpSpec{f ? Filter : Plain, nnz, rp, col, val, work, f ? *f : lz_cheb{}, {}, 0, nullptr, nullptr, nullptr};
+    }
+    static OpSpec series(int64_t nnz, const int64_t *rp, const int32_t *col, const void *val, int degree, double lo,
+                         double hi, const double *gamma, void *work)
+    {
+        return OpSpec{Series, nnz, rp, col, val, work, {}, {degree, lo, hi, gamma}, 0, nullptr, nullptr, nullptr};
+    }
+    static OpSpec normal(int64_t p, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                         const int64_t *t_rp, const int32_t *t_col, const void *t_val, void *work)
+    {
+        return OpSpec{Normal, nnz, rp, col, val, work, {}, {}, p, t_rp, t_col, t_val};
+    }
+    // rows of the CSR (rp, col, val) of an operator on n-row blocks
+    int64_t rows(int64_t n) const { return form == Normal ? p : n; }
+    int64_t work_elems(int64_t n, int b) const { return form == Plain ? 0 : form == Normal ? p * b : 2 * n * b; }
 };
 
-template <typename T>
-static ReorthOp<T> make_op(int64_t nnz, const int64_t *rp, const int32_t *col, const void *val, const lz_cheb *f,
-                           void *work, const NormalArgs *nm, const SeriesArgs *sr = nullptr)
+// A spec against the call's other buffers: the form's own parameter rules; then work is there, on 16
+// bytes where the entry asks for that (the solves do, the apply entries never have), and apart from
+// every span of `others` (apart_msg: the entry's wording of that rule)
+static int op_args(const OpSpec &op, int64_t n, int b, lz_dtype dtype, bool work16, const char *apart_msg,
+                   std::initializer_list<Span> others)
 {
-    ReorthOp<T> op{nnz, rp, col, (const T *)val};
-    if (sr) {
-        op.sr = sr, op.work = (T *)sr->work;
-    } else if (nm) {
-        op.p = nm->p, op.trp = nm->t_rp, op.tcol = nm->t_col, op.tval = (const T *)nm->t_val;
-        op.work = (T *)nm->work;
-    } else {
-        op.f = f, op.work = (T *)work;
+    const lz_cheb &f = op.f;
+    const ChebSeries &sr = op.sr;
+    switch (op.form) {
+    case OpSpec::Plain:
+        return LZ_OK;
+    case OpSpec::Filter:
+        LZ_ARG_CHECK(f.degree >= 1 && f.degree <= 256, "Chebyshev filter: 1 <= degree <= 256");
+        LZ_ARG_CHECK(std::isfinite(f.lo) && std::isfinite(f.hi) && std::isfinite(f.ref) && f.lo < f.hi,
+                     "Chebyshev filter: lo < hi, finite");
+        LZ_ARG_CHECK(f.ref < f.lo || f.ref > f.hi, "Chebyshev filter: ref outside [lo, hi]");
+        break;
+    case OpSpec::Series:
+        LZ_ARG_CHECK(sr.degree >= 1 && sr.degree <= 65536, "Chebyshev series: 1 <= degree <= 65536");
+        LZ_ARG_CHECK(std::isfinite(sr.lo) && std::isfinite(sr.hi) && sr.lo < sr.hi, "Chebyshev series: lo < hi, finite");
+        LZ_ARG_CHECK(sr.gamma != nullptr, "Chebyshev series: gamma is NULL");
+        break;
+    case OpSpec::Normal:
+        LZ_ARG_CHECK(op.p >= 1, "normal operator: p >= 1");
+        LZ_ARG_CHECK(op.t_rp != nullptr, "normal operator: the transpose's row_ptr is NULL");
+        LZ_ARG_CHECK(op.t_col != nullptr && op.t_val != nullptr, "normal operator: the transpose's col/val NULL");
+        break;
     }
-    return op;
+    LZ_ARG_CHECK(op.work != nullptr, "work is NULL");
+    LZ_ARG_CHECK(!work16 || reinterpret_cast<uintptr_t>(op.work) % 16 == 0, "work must be on 16 bytes");
+    LZ_ARG_CHECK(apart(span_of(op.work, op.work_elems(n, b), dtype), others), apart_msg);
+    return LZ_OK;
 }
 
-// W = op Q: the operator line of the kept-basis solves
+// W = op Q: the operator line of the kept-basis solves, and the apply entries
 template <typename T>
-static int reorth_op(lz_handle *h, int64_t n, int b, const ReorthOp<T> &op, const T *Q, T *W)
+static int reorth_op(lz_handle *h, int64_t n, int b, const OpSpec &op, const T *Q, T *W)
 {
-    if (op.p > 0) {
-        LZ_TRY(spmm_rm<T>(h, op.p, op.nnz, op.rp, op.col, op.val, b, Q, b, n, op.work, b));
-        return spmm_rm<T>(h, n, op.nnz, op.trp, op.tcol, op.tval, b, op.work, b, op.p, W, b);
+    const T *val = (const T *)op.val;
+    T *work = (T *)op.work;
+    switch (op.form) {
+    case OpSpec::Filter:
+        return cheb_apply<T>(h, n, op.nnz, op.rp, op.col, val, b, op.f, Q, W, work);
+    case OpSpec::Series:
+        return cheb_series_apply<T>(h, n, op.nnz, op.rp, op.col, val, b, op.sr, Q, W, work);
+    case OpSpec::Normal:
+        LZ_TRY(spmm_rm<T>(h, op.p, op.nnz, op.rp, op.col, val, b, Q, b, n, work, b));
+        return spmm_rm<T>(h, n, op.nnz, op.t_rp, op.t_col, (const T *)op.t_val, b, work, b, op.p, W, b);
+    case OpSpec::Plain:
+        break;
     }
-    if (op.sr) return cheb_series_apply<T>(h, n, op.nnz, op.rp, op.col, op.val, b, *op.sr, Q, W, op.work);
-    if (!op.f) return spmm_rm<T>(h, n, op.nnz, op.rp, op.col, op.val, b, Q, b, n, W, b);
-    return cheb_apply<T>(h, n, op.nnz, op.rp, op.col, op.val, b, *op.f, Q, W, op.work);
+    return spmm_rm<T>(h, n, op.nnz, op.rp, op.col, val, b, Q, b, n, W, b);
 }
 
 // Steps j0 .. m - 1 (j0 >= 1; block j0 - 1 holds Q_{j0-1}, W the residual of
 // step j0 - 1), then beta_m of the final residual: the part a first cycle and
 // a resumed one share.
 template <typename T>
-static int reorth_steps(lz_handle *h, int64_t n, const ReorthOp<T> &op, int b, int j0, int m, int64_t lc, T *q,
+static int reorth_steps(lz_handle *h, int64_t n, const OpSpec &op, int b, int j0, int m, int64_t lc, T *q,
                         T *alpha, T *beta, T *V, int64_t vstride, T *W, int passes)
 {
     const int64_t bb = (int64_t)b * b;
@@ -441,52 +504,36 @@ static int reorth_steps(lz_handle *h, int64_t n, const ReorthOp<T> &op, int b, i
     return LZ_OK;
 }
 
+// One cycle on a kept basis: step r, then reorth_steps from r + 1.
+// A first cycle (r == 0, lz_block_lanczos_reorth): Q_0 = B beta_0^-1 with beta_0 = sqrtm(B'B); step 0
+// has no earlier block to subtract, and its row of q is copied as soon as Q_0 stands.
+// A cycle on a thick-restarted basis (r >= 1, lz_block_lanczos_reorth_resume): blocks 0 .. r - 1
+// hold the kept Ritz blocks Y, W the previous cycle's residual, Q_r = W beta_r^-1.  With
+// A Y = Y Theta + Q_r Sigma, step r subtracts Y Sigma^T = sum_i Y_i S_i (sigma holds the S_i, so
+// this is one panel_apply over the r kept blocks) where an ordinary step subtracts Q_{j-1} beta_j;
+// from step r + 1 on the recurrence is the three-term one again.
 template <typename T>
-static int block_lanczos_reorth(lz_handle *h, int64_t n, const ReorthOp<T> &op, int b, int m, int64_t lc, const T *B,
-                                T *q, T *alpha, T *beta, T *V, int64_t vstride, T *W, int passes)
-{
-    T *binv = ScratchT<T>(h, b).binv[0];
-    LZ_TRY(reorth_reserve<T>(h, n, b, m, passes));
-    int P = 0;
-    T *Qj = V;
-    LZ_TRY(gram_partials<T>(h, n, b, B, B, b, &P));
-    LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, beta, binv, nullptr));      // beta_0 = sqrtm(B'B)
-    LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), B, binv, Qj, b));               // Q_0 = B beta_0^-1
-    LZ_TRY(copy_row<T>(h, b, Qj, b, 0, lc, q));
-    LZ_TRY(reorth_op<T>(h, n, b, op, Qj, W));                           // W = op Q_0
-    LZ_TRY(gram_partials<T>(h, n, b, W, Qj, b, &P));
-    LZ_TRY(gram_finish<T>(h, b, P, 1, alpha));                          // alpha_0
-    LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qj, alpha, W, b));             // W -= Q_0 alpha_0
-    LZ_TRY(reorth_rounds<T>(h, n, b, 1, V, vstride, W, passes));
-    return reorth_steps<T>(h, n, op, b, 1, m, lc, q, alpha, beta, V, vstride, W, passes);
-}
-
-// A cycle on a thick-restarted basis (lz_block_lanczos_reorth_resume): blocks
-// 0 .. r - 1 hold the kept Ritz blocks Y, W the previous cycle's residual.  With
-// A Y = Y Theta + Q_r Sigma, step r subtracts Y Sigma^T = sum_i Y_i S_i (sigma
-// holds the S_i, so this is one panel_apply over the r kept blocks) where an
-// ordinary step subtracts Q_{j-1} beta_j; from step r + 1 on the recurrence is
-// the three-term one again.
-template <typename T>
-static int block_lanczos_reorth_resume(lz_handle *h, int64_t n, const ReorthOp<T> &op, int b, int r, int m, int64_t lc,
-                                       const T *sigma, T *q, T *alpha, T *beta, T *V, int64_t vstride, T *W,
-                                       int passes)
+static int reorth_cycle(lz_handle *h, int64_t n, const OpSpec &op, int b, int r, int m, int64_t lc, const T *B,
+                        const T *sigma, T *q, T *alpha, T *beta, T *V, int64_t vstride, T *W, int passes)
 {
     const int64_t bb = (int64_t)b * b;
+    const bool first = r == 0;
     T *binv = ScratchT<T>(h, b).binv[0];
     LZ_TRY(reorth_reserve<T>(h, n, b, m, passes));
     int P = 0;
+    const T *R = first ? B : W;  // what Q_r is normalised from
     T *br = beta + r * bb, *ar = alpha + r * bb, *Qr = V + (int64_t)r * vstride;
-    LZ_TRY(gram_partials<T>(h, n, b, W, W, b, &P));
-    LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, br, binv, nullptr));         // beta_r = sqrtm(W'W)
-    LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), W, binv, Qr, b));               // Q_r = W beta_r^-1
+    LZ_TRY(gram_partials<T>(h, n, b, R, R, b, &P));
+    LZ_TRY(sqrtm_pair<T>(h, b, nullptr, P, br, binv, nullptr));         // beta_r = sqrtm(R'R)
+    LZ_TRY(tsmm<T>(h, n, b, T(0), T(1), R, binv, Qr, b));               // Q_r = R beta_r^-1
+    if (first) LZ_TRY(copy_row<T>(h, b, Qr, b, 0, lc, q));
     LZ_TRY(reorth_op<T>(h, n, b, op, Qr, W));                           // W = op Q_r
-    LZ_TRY(panel_apply<T>(h, n, b, r, 1.0, -1.0, V, vstride, sigma, W)); // W -= sum_i Y_i S_i
+    if (!first) LZ_TRY(panel_apply<T>(h, n, b, r, 1.0, -1.0, V, vstride, sigma, W));  // W -= sum_i Y_i S_i
     LZ_TRY(gram_partials<T>(h, n, b, W, Qr, b, &P));
     LZ_TRY(gram_finish<T>(h, b, P, 1, ar));                             // alpha_r
     LZ_TRY(tsmm<T>(h, n, b, T(1), T(-1), Qr, ar, W, b));                // W -= Q_r alpha_r
     LZ_TRY(reorth_rounds<T>(h, n, b, r + 1, V, vstride, W, passes));
-    LZ_TRY(copy_row<T>(h, b, Qr, b, 0, lc, q + (int64_t)r * b));
+    if (!first) LZ_TRY(copy_row<T>(h, b, Qr, b, 0, lc, q + (int64_t)r * b));
     return reorth_steps<T>(h, n, op, b, r + 1, m, lc, q, alpha, beta, V, vstride, W, passes);
 }
 
@@ -1557,6 +1604,41 @@ static uint64_t comm_issued(const lz_handle *h) { return h && h->comm ? h->comm-
         LZ_HIP_TRY(hipSetDevice((h)->device));                                      \
     } while (0)
 
+// What most entries check first: the dtype is one of the two, n >= n_min, 1 <= b <= b_max (msg: the
+// two bounds in the entry's own words; NULL: "n >= <n_min>, b in [1,<b_max>]")
+static int shape_args(lz_dtype dtype, int64_t n, int64_t n_min, int b, int b_max, const char *msg = nullptr)
+{
+    char text[64];
+    if (!msg) snprintf(text, sizeof(text), "n >= %lld, b in [1,%d]", (long long)n_min, b_max), msg = text;
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n >= n_min && b >= 1 && b <= b_max, msg);
+    return LZ_OK;
+}
+
+// lz_cg_solve and lz_bcg_solve: the same arguments under the same rules but the widest block, b_max;
+// solve(...) is cg_solve or bcg_solve in the dtype
+template <typename Solve>
+static int krylov_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                        lz_dtype dtype, int b, int b_max, double shift, const void *B, void *X, void *work,
+                        const lz_cg_opts *opts, int *iters, int *status, double *resid, double *est, int *info,
+                        Solve solve)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_TRY(shape_args(dtype, n, 1, b, b_max));
+    LZ_ARG_CHECK(B && X && work && opts && iters && status && resid && est && info, "NULL argument");
+    LZ_ARG_CHECK(opts->tol > 0.0 && std::isfinite(opts->tol) && std::isfinite(shift), "tol > 0, tol and shift finite");
+    LZ_ARG_CHECK(opts->max_iter >= 0 && opts->max_restarts >= 0, "max_iter, max_restarts >= 0");
+    const int64_t nb = n * b;
+    LZ_ARG_CHECK(pairwise_apart({span_of(B, nb, dtype), span_of(X, nb, dtype), span_of(work, 4 * nb, dtype)}),
+                 "B, X and work must be pairwise distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return solve(h, n, nnz, rp, col, (const T *)val, b, shift, (const T *)B, (T *)X, (T *)work, *opts, iters, status,
+                     resid, est, info);
+    });
+}
+
 extern "C" {
 
 const char *lz_last_error(void) { return g_err; }
@@ -1933,8 +2015,7 @@ static int panel_args(int64_t n, int b, int k, lz_dtype dtype, const void *V, in
     LZ_ARG_CHECK(k >= 1 && k <= kPanelMaxK, "a basis panel holds 1 <= k <= 64 blocks");
     LZ_ARG_CHECK(V != nullptr, "V is NULL");
     LZ_ARG_CHECK(vstride >= n * b, "vstride >= n*b");
-    const int64_t per16 = dtype == LZ_F64 ? 2 : 4;
-    LZ_ARG_CHECK(vstride % per16 == 0 && reinterpret_cast<uintptr_t>(V) % 16 == 0,
+    LZ_ARG_CHECK(vstride % (16 / elem_bytes(dtype)) == 0 && reinterpret_cast<uintptr_t>(V) % 16 == 0,
                  "V and vstride must be multiples of 16 bytes");
     return LZ_OK;
 }
@@ -1957,70 +2038,11 @@ int lz_panel_apply(lz_handle *h, int64_t n, int b, int k, lz_dtype dtype, double
     LZ_HANDLE_CHECK(h);
     LZ_TRY(panel_args(n, b, k, dtype, V, vstride));
     LZ_ARG_CHECK(S && W, "S/W NULL");
-    {
-        const char *v0 = (const char *)V, *w0 = (const char *)W;
-        const int64_t es = dtype == LZ_F64 ? 8 : 4;
-        LZ_ARG_CHECK(w0 + n * b * es <= v0 || w0 >= v0 + ((int64_t)(k - 1) * vstride + n * b) * es,
-                     "W must not overlap the panel");
-    }
+    LZ_ARG_CHECK(apart(span_of(W, n * b, dtype), panel_span(V, n, b, k, vstride, dtype)), "W must not overlap the panel");
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return panel_apply<T>(h, n, b, k, beta, alpha, (const T *)V, vstride, (const T *)S, (T *)W);
     });
-}
-
-// n x b blocks at p and q (es bytes per element) do not overlap
-static bool blocks_apart(const void *p, int64_t np, const void *q, int64_t nq, int64_t es)
-{
-    const char *a = (const char *)p, *c = (const char *)q;
-    return a + np * es <= c || c + nq * es <= a;
-}
-
-// the filter and its workspace of a solve on p(A): work (2 n b) apart from W, B (may be null) and the panel
-static int cheb_solve_args(const lz_cheb *f, const void *work, int64_t n, int b, int m, lz_dtype dtype,
-                           const void *V, int64_t vstride, const void *W, const void *B)
-{
-    if (!f) return LZ_OK;
-    LZ_TRY(cheb_args(f));
-    LZ_ARG_CHECK(work != nullptr, "work is NULL");
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    LZ_ARG_CHECK(reinterpret_cast<uintptr_t>(work) % 16 == 0, "work must be on 16 bytes");
-    LZ_ARG_CHECK(blocks_apart(work, 2 * nb, W, nb, es) && (!B || blocks_apart(work, 2 * nb, B, nb, es)) &&
-                     blocks_apart(work, 2 * nb, V, (int64_t)(m - 1) * vstride + nb, es),
-                 "work must not overlap B, W or the panel V");
-    return LZ_OK;
-}
-
-// the series and its workspace of a solve on s(A), as cheb_solve_args
-static int series_solve_args(const SeriesArgs *sr, int64_t n, int b, int m, lz_dtype dtype, const void *V,
-                             int64_t vstride, const void *W, const void *B)
-{
-    if (!sr) return LZ_OK;
-    LZ_TRY(series_args(sr));
-    LZ_ARG_CHECK(sr->work != nullptr, "work is NULL");
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    LZ_ARG_CHECK(reinterpret_cast<uintptr_t>(sr->work) % 16 == 0, "work must be on 16 bytes");
-    LZ_ARG_CHECK(blocks_apart(sr->work, 2 * nb, W, nb, es) && (!B || blocks_apart(sr->work, 2 * nb, B, nb, es)) &&
-                     blocks_apart(sr->work, 2 * nb, V, (int64_t)(m - 1) * vstride + nb, es),
-                 "work must not overlap B, W or the panel V");
-    return LZ_OK;
-}
-
-// work (p b) apart from W, B (may be null) and the panel, as cheb_solve_args
-static int normal_solve_args(const NormalArgs *nm, int64_t n, int b, int m, lz_dtype dtype, const void *V,
-                             int64_t vstride, const void *W, const void *B)
-{
-    if (!nm) return LZ_OK;
-    LZ_ARG_CHECK(nm->p >= 1, "normal operator: p >= 1");
-    LZ_ARG_CHECK(nm->t_rp != nullptr, "normal operator: the transpose's row_ptr is NULL");
-    LZ_ARG_CHECK(nm->t_col != nullptr && nm->t_val != nullptr, "normal operator: the transpose's col/val NULL");
-    LZ_ARG_CHECK(nm->work != nullptr, "work is NULL");
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b, pb = nm->p * b;
-    LZ_ARG_CHECK(reinterpret_cast<uintptr_t>(nm->work) % 16 == 0, "work must be on 16 bytes");
-    LZ_ARG_CHECK(blocks_apart(nm->work, pb, W, nb, es) && (!B || blocks_apart(nm->work, pb, B, nb, es)) &&
-                     blocks_apart(nm->work, pb, V, (int64_t)(m - 1) * vstride + nb, es),
-                 "work must not overlap B, W or the panel V");
-    return LZ_OK;
 }
 
 int lz_csr_transpose(lz_handle *h, int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t *rp, const int32_t *col,
@@ -2034,21 +2056,28 @@ int lz_csr_transpose(lz_handle *h, int64_t n_rows, int64_t n_cols, int64_t nnz, 
     LZ_ARG_CHECK(nnz < (1LL << 32) - 1, "nnz < 2^32 - 1");
     LZ_ARG_CHECK(nnz == 0 || n_rows >= 1, "entries without rows");
     LZ_ARG_CHECK(t_rp != nullptr && (nnz == 0 || (t_col != nullptr && t_val != nullptr)), "output NULL");
-    {
-        const int64_t es = dtype == LZ_F64 ? 8 : 4;
-        struct R { const void *p; int64_t bytes; };
-        const R in[3] = {{rp, (n_rows + 1) * 8}, {col, nnz * 4}, {val, nnz * es}};
-        const R out[3] = {{t_rp, (n_cols + 1) * 8}, {t_col, nnz * 4}, {t_val, nnz * es}};
-        bool apart = true;
-        for (int i = 0; i < 3; ++i) {
-            for (int j = 0; j < 3; ++j) apart = apart && blocks_apart(out[i].p, out[i].bytes, in[j].p, in[j].bytes, 1);
-            for (int j = i + 1; j < 3; ++j) apart = apart && blocks_apart(out[i].p, out[i].bytes, out[j].p, out[j].bytes, 1);
-        }
-        LZ_ARG_CHECK(apart, "the outputs must be distinct from each other and from the inputs");
-    }
+    const Span in_rp{rp, (n_rows + 1) * 8}, in_col{col, nnz * 4}, in_val = span_of(val, nnz, dtype);
+    const Span out_rp{t_rp, (n_cols + 1) * 8}, out_col{t_col, nnz * 4}, out_val = span_of(t_val, nnz, dtype);
+    LZ_ARG_CHECK(pairwise_apart({out_rp, out_col, out_val}) && apart(out_rp, {in_rp, in_col, in_val}) &&
+                     apart(out_col, {in_rp, in_col, in_val}) && apart(out_val, {in_rp, in_col, in_val}),
+                 "the outputs must be distinct from each other and from the inputs");
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return csr_transpose<T>(h, n_rows, n_cols, nnz, rp, col, (const T *)val, t_rp, t_col, (T *)t_val);
+    });
+}
+
+// The apply entries' shared end (lz_cheb_apply, lz_cheb_series_apply, lz_normal_apply): X, Y and the
+// spec's work pairwise apart, then Y = op X
+static int apply_entry(lz_handle *h, int64_t n, const OpSpec &op, lz_dtype dtype, int b, const void *X, void *Y)
+{
+    const char *msg = "X, Y and work must be pairwise distinct";
+    const Span x = span_of(X, n * b, dtype), y = span_of(Y, n * b, dtype);
+    LZ_ARG_CHECK(apart(x, y), msg);
+    LZ_TRY(op_args(op, n, b, dtype, false, msg, {x, y}));
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return reorth_op<T>(h, n, b, op, (const T *)X, (T *)Y);
     });
 }
 
@@ -2059,18 +2088,9 @@ int lz_normal_apply(lz_handle *h, int64_t n, int64_t p, int64_t nnz, const int64
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(p, nnz, rp, col, val));
     LZ_TRY(check_csr(n, nnz, t_rp, t_col, t_val));
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(n >= 1 && p >= 1 && b >= 1 && b <= kMaxB, "n, p >= 1, b in [1,64]");
+    LZ_TRY(shape_args(dtype, std::min(n, p), 1, b, kMaxB, "n, p >= 1, b in [1,64]"));
     LZ_ARG_CHECK(X && Y && work, "X/Y/work NULL");
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b, pb = p * b;
-    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && blocks_apart(work, pb, X, nb, es) &&
-                     blocks_apart(work, pb, Y, nb, es),
-                 "X, Y and work must be pairwise distinct");
-    const NormalArgs nm{p, t_rp, t_col, t_val, work};
-    return by_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        return reorth_op<T>(h, n, b, make_op<T>(nnz, rp, col, val, nullptr, nullptr, &nm), (const T *)X, (T *)Y);
-    });
+    return apply_entry(h, n, OpSpec::normal(p, nnz, rp, col, val, t_rp, t_col, t_val, work), dtype, b, X, Y);
 }
 
 // The term steps' entry points (lz_csr_spmm_axpby, _axpby_dots, _axpby4): their shared checks
@@ -2082,14 +2102,14 @@ static int terms_entry(lz_handle *h, int64_t n, bool want_dots, int64_t nnz, con
 {
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(n, nnz, rp, col, val));
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK((n >= 1 || !want_dots) && b >= 1 && b <= kMaxB, "b in [1,64] (and n >= 1 with dots)");
+    LZ_TRY(shape_args(dtype, n, want_dots ? 1 : 0, b, kMaxB, "b in [1,64] (and n >= 1 with dots)"));
     LZ_ARG_CHECK(X && Y && (Z || d == 0.0), "X/Y NULL, or Z NULL with d != 0");
     LZ_ARG_CHECK(U || e == 0.0, "U NULL with e != 0");
     LZ_ARG_CHECK(dots || !want_dots, "dots is NULL");
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && (d == 0.0 || (blocks_apart(Z, nb, Y, nb, es) && Z != X)) &&
-                     (e == 0.0 || blocks_apart(U, nb, Y, nb, es)),
+    const int64_t nb = n * b;
+    const Span z = d == 0.0 ? Span{} : span_of(Z, nb, dtype), u = e == 0.0 ? Span{} : span_of(U, nb, dtype);
+    // Z != X is a pointer-equality test, not an overlap rule: a Z that partly overlaps X is accepted
+    LZ_ARG_CHECK(apart(span_of(Y, nb, dtype), {span_of(X, nb, dtype), z, u}) && (d == 0.0 || Z != X),
                  "Y must be distinct from X, Z and U, and Z from X (no in-place form)");
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -2110,25 +2130,15 @@ int lz_cheb_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const
 {
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(n, nnz, rp, col, val));
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= kMaxB, "n >= 1, b in [1,64]");
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
     LZ_ARG_CHECK(f && X && Y && work, "f/X/Y/work NULL");
-    LZ_TRY(cheb_args(f));
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && blocks_apart(work, 2 * nb, X, nb, es) &&
-                     blocks_apart(work, 2 * nb, Y, nb, es),
-                 "X, Y and work must be pairwise distinct");
-    return by_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        return cheb_apply<T>(h, n, nnz, rp, col, (const T *)val, b, *f, (const T *)X, (T *)Y, (T *)work);
-    });
+    return apply_entry(h, n, OpSpec::filter(nnz, rp, col, val, f, work), dtype, b, X, Y);
 }
 
 int lz_col_dots(lz_handle *h, int64_t n, int b, lz_dtype dtype, const void *Y, const void *X, double *dots)
 {
     LZ_HANDLE_CHECK(h);
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= kMaxB, "n >= 1, b in [1,64]");
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
     LZ_ARG_CHECK(Y && X && dots, "Y/X/dots NULL");
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -2148,13 +2158,11 @@ int lz_cheb_moments(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, con
 {
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(n, nnz, rp, col, val));
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= kMaxB, "n >= 1, b in [1,64]");
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
     LZ_ARG_CHECK(X0 && work && dots, "X0/work/dots NULL");
     LZ_ARG_CHECK(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "Chebyshev moments: lo < hi, finite");
     LZ_ARG_CHECK(K >= 1 && K <= 65536, "Chebyshev moments: 1 <= K <= 65536");
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    LZ_ARG_CHECK(blocks_apart(work, 3 * nb, X0, nb, es), "X0 and work must be distinct");
+    LZ_ARG_CHECK(apart(span_of(work, 3 * n * b, dtype), span_of(X0, n * b, dtype)), "X0 and work must be distinct");
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return cheb_moments<T>(h, n, nnz, rp, col, (const T *)val, b, lo, hi, K, (const T *)X0, (T *)work, dots,
@@ -2166,15 +2174,12 @@ int lz_cg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *c
                  void *S, void *X, double *rr)
 {
     LZ_HANDLE_CHECK(h);
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= kMaxB, "n >= 1, b in [1,64]");
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
     LZ_ARG_CHECK(coef && R && W && P && S && X && rr, "coef/R/W/P/S/X/rr NULL");
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    const void *blk[5] = {R, W, P, S, X};
-    bool apart = true;
-    for (int i = 0; i < 5; ++i)
-        for (int j = i + 1; j < 5; ++j) apart = apart && blocks_apart(blk[i], nb, blk[j], nb, es);
-    LZ_ARG_CHECK(apart, "R, W, P, S and X must be pairwise distinct");
+    const int64_t nb = n * b;
+    LZ_ARG_CHECK(pairwise_apart({span_of(R, nb, dtype), span_of(W, nb, dtype), span_of(P, nb, dtype),
+                                 span_of(S, nb, dtype), span_of(X, nb, dtype)}),
+                 "R, W, P, S and X must be pairwise distinct");
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return cg_update<T>(h, n, b, coef, (T *)R, (const T *)W, (T *)P, (T *)S, (T *)X, rr);
@@ -2185,37 +2190,19 @@ int lz_cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const i
                 lz_dtype dtype, int b, double shift, const void *B, void *X, void *work, const lz_cg_opts *opts,
                 int *iters, int *status, double *resid, double *est, int *info)
 {
-    LZ_HANDLE_CHECK(h);
-    LZ_TRY(check_csr(n, nnz, rp, col, val));
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= kMaxB, "n >= 1, b in [1,64]");
-    LZ_ARG_CHECK(B && X && work && opts && iters && status && resid && est && info, "NULL argument");
-    LZ_ARG_CHECK(opts->tol > 0.0 && std::isfinite(opts->tol) && std::isfinite(shift), "tol > 0, tol and shift finite");
-    LZ_ARG_CHECK(opts->max_iter >= 0 && opts->max_restarts >= 0, "max_iter, max_restarts >= 0");
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    LZ_ARG_CHECK(blocks_apart(B, nb, X, nb, es) && blocks_apart(work, 4 * nb, B, nb, es) &&
-                     blocks_apart(work, 4 * nb, X, nb, es),
-                 "B, X and work must be pairwise distinct");
-    return by_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        return cg_solve<T>(h, n, nnz, rp, col, (const T *)val, b, shift, (const T *)B, (T *)X, (T *)work, *opts, iters,
-                           status, resid, est, info);
-    });
+    return krylov_entry(h, n, nnz, rp, col, val, dtype, b, kMaxB, shift, B, X, work, opts, iters, status, resid, est, info,
+                        [](auto... a) { return cg_solve(a...); });
 }
 
 int lz_bcg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *xi, const double *E, const void *S,
                   const void *W, void *Q, void *X, double *G)
 {
     LZ_HANDLE_CHECK(h);
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= 32, "n >= 1, b in [1,32]");
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxSolveB));
     LZ_ARG_CHECK(xi && E && S && W && Q && X && G, "xi/E/S/W/Q/X/G NULL");
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    const void *blk[4] = {S, W, Q, X};
-    bool apart = true;
-    for (int i = 0; i < 4; ++i)
-        for (int j = i + 1; j < 4; ++j) apart = apart && blocks_apart(blk[i], nb, blk[j], nb, es);
-    LZ_ARG_CHECK(apart, "S, W, Q and X must be pairwise distinct");
+    const int64_t nb = n * b;
+    LZ_ARG_CHECK(pairwise_apart({span_of(S, nb, dtype), span_of(W, nb, dtype), span_of(Q, nb, dtype), span_of(X, nb, dtype)}),
+                 "S, W, Q and X must be pairwise distinct");
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return bcg_update<T>(h, n, b, xi, E, (const T *)S, (const T *)W, (T *)Q, (T *)X, G);
@@ -2226,10 +2213,9 @@ int lz_bcg_direction(lz_handle *h, int64_t n, int b, lz_dtype dtype, const doubl
                      void *S)
 {
     LZ_HANDLE_CHECK(h);
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= 32, "n >= 1, b in [1,32]");
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxSolveB));
     LZ_ARG_CHECK(z && zinv && Q && S, "z/zinv/Q/S NULL");
-    LZ_ARG_CHECK(blocks_apart(Q, n * b, S, n * b, dtype == LZ_F64 ? 8 : 4), "Q and S must be distinct");
+    LZ_ARG_CHECK(apart(span_of(Q, n * b, dtype), span_of(S, n * b, dtype)), "Q and S must be distinct");
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return bcg_direction<T>(h, n, b, z, zinv, (T *)Q, (T *)S);
@@ -2240,21 +2226,37 @@ int lz_bcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const 
                  lz_dtype dtype, int b, double shift, const void *B, void *X, void *work, const lz_cg_opts *opts,
                  int *iters, int *status, double *resid, double *est, int *info)
 {
+    return krylov_entry(h, n, nnz, rp, col, val, dtype, b, kMaxSolveB, shift, B, X, work, opts, iters, status, resid, est,
+                        info, [](auto... a) { return bcg_solve(a...); });
+}
+
+// The eight kept-basis entry points.  r == 0 with B (sigma NULL) is a first cycle, lz_block_lanczos_reorth
+// and its forms; anything else is a resumed one, lz_block_lanczos_reorth_resume and its forms, which
+// needs 1 <= r < m and sigma (its B is NULL).
+static int cycle_entry(lz_handle *h, int64_t n, const OpSpec &op, lz_dtype dtype, int b, int r, int m, int64_t lc,
+                       const void *B, const void *sigma, void *q, void *alpha, void *beta, void *V, int64_t vstride,
+                       void *W, int passes)
+{
+    const bool first = r == 0 && !sigma;
     LZ_HANDLE_CHECK(h);
-    LZ_TRY(check_csr(n, nnz, rp, col, val));
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= 32, "n >= 1, b in [1,32]");
-    LZ_ARG_CHECK(B && X && work && opts && iters && status && resid && est && info, "NULL argument");
-    LZ_ARG_CHECK(opts->tol > 0.0 && std::isfinite(opts->tol) && std::isfinite(shift), "tol > 0, tol and shift finite");
-    LZ_ARG_CHECK(opts->max_iter >= 0 && opts->max_restarts >= 0, "max_iter, max_restarts >= 0");
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    LZ_ARG_CHECK(blocks_apart(B, nb, X, nb, es) && blocks_apart(work, 4 * nb, B, nb, es) &&
-                     blocks_apart(work, 4 * nb, X, nb, es),
-                 "B, X and work must be pairwise distinct");
+    LZ_TRY(check_csr(op.rows(n), op.nnz, op.rp, op.col, op.val));
+    LZ_ARG_CHECK(m >= 1 && m <= kPanelMaxK, "the kept basis holds 1 <= m <= 64 blocks");
+    LZ_ARG_CHECK(first || (r >= 1 && r < m), "a resumed solve keeps 1 <= r < m blocks");
+    LZ_TRY(panel_args(n, b, m, dtype, V, vstride));
+    LZ_ARG_CHECK(passes >= 0 && passes <= 2, "passes in {0, 1, 2}");
+    LZ_ARG_CHECK(lc >= 0 && lc < n, "lc must be a row index");
+    LZ_ARG_CHECK(first || sigma != nullptr, "sigma is NULL");
+    LZ_ARG_CHECK((B || !first) && q && alpha && beta && W, "NULL buffer");
+    const Span panel = panel_span(V, n, b, m, vstride, dtype), w = span_of(W, n * b, dtype);
+    const Span start = first ? span_of(B, n * b, dtype) : Span{};
+    // B != W is a pointer-equality test, not an overlap rule: a B that partly overlaps W is accepted
+    LZ_ARG_CHECK(apart(panel, {w, start}) && B != W,
+                 first ? "B, W and the panel V must be distinct buffers" : "W and the panel V must be distinct buffers");
+    LZ_TRY(op_args(op, n, b, dtype, true, "work must not overlap B, W or the panel V", {w, start, panel}));
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        return bcg_solve<T>(h, n, nnz, rp, col, (const T *)val, b, shift, (const T *)B, (T *)X, (T *)work, *opts,
-                            iters, status, resid, est, info);
+        return reorth_cycle<T>(h, n, op, b, r, m, lc, (const T *)B, (const T *)sigma, (T *)q, (T *)alpha, (T *)beta,
+                               (T *)V, vstride, (T *)W, passes);
     });
 }
 
@@ -2266,43 +2268,13 @@ int lz_block_lanczos_reorth(lz_handle *h, int64_t n, int64_t nnz, const int64_t 
                                         passes, nullptr, nullptr);
 }
 
-// lz_block_lanczos_reorth and its _cheb (f) and _normal (nm) forms
-static int reorth_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
-                        lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q, void *alpha, void *beta,
-                        void *V, int64_t vstride, void *W, int passes, const lz_cheb *f, void *work,
-                        const NormalArgs *nm, const SeriesArgs *sr = nullptr)
-{
-    LZ_HANDLE_CHECK(h);
-    LZ_TRY(check_csr(nm ? nm->p : n, nnz, rp, col, val));
-    LZ_ARG_CHECK(m >= 1 && m <= kPanelMaxK, "the kept basis holds 1 <= m <= 64 blocks");
-    LZ_TRY(panel_args(n, b, m, dtype, V, vstride));
-    LZ_ARG_CHECK(passes >= 0 && passes <= 2, "passes in {0, 1, 2}");
-    LZ_ARG_CHECK(lc >= 0 && lc < n, "lc must be a row index");
-    LZ_ARG_CHECK(B && q && alpha && beta && W, "NULL buffer");
-    {
-        const int64_t es = dtype == LZ_F64 ? 8 : 4;
-        const char *v0 = (const char *)V, *v1 = v0 + ((int64_t)(m - 1) * vstride + n * b) * es;
-        const char *w0 = (const char *)W, *b0 = (const char *)B;
-        LZ_ARG_CHECK((w0 + n * b * es <= v0 || w0 >= v1) && (b0 + n * b * es <= v0 || b0 >= v1) && B != W,
-                     "B, W and the panel V must be distinct buffers");
-    }
-    LZ_TRY(cheb_solve_args(f, work, n, b, m, dtype, V, vstride, W, B));
-    LZ_TRY(normal_solve_args(nm, n, b, m, dtype, V, vstride, W, B));
-    LZ_TRY(series_solve_args(sr, n, b, m, dtype, V, vstride, W, B));
-    return by_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        return block_lanczos_reorth<T>(h, n, make_op<T>(nnz, rp, col, val, f, work, nm, sr), b, m, lc, (const T *)B, (T *)q,
-                                       (T *)alpha, (T *)beta, (T *)V, vstride, (T *)W, passes);
-    });
-}
-
 int lz_block_lanczos_reorth_cheb(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
                                  const void *val, lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q,
                                  void *alpha, void *beta, void *V, int64_t vstride, void *W, int passes,
                                  const lz_cheb *f, void *work)
 {
-    return reorth_entry(h, n, nnz, rp, col, val, dtype, b, m, lc, B, q, alpha, beta, V, vstride, W, passes, f, work,
-                        nullptr);
+    return cycle_entry(h, n, OpSpec::filter(nnz, rp, col, val, f, work), dtype, b, 0, m, lc, B, nullptr, q, alpha, beta,
+                       V, vstride, W, passes);
 }
 
 int lz_block_lanczos_reorth_normal(lz_handle *h, int64_t n, int64_t p, int64_t nnz, const int64_t *rp,
@@ -2310,9 +2282,8 @@ int lz_block_lanczos_reorth_normal(lz_handle *h, int64_t n, int64_t p, int64_t n
                                    const void *t_val, lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q,
                                    void *alpha, void *beta, void *V, int64_t vstride, void *W, int passes, void *work)
 {
-    const NormalArgs nm{p, t_rp, t_col, t_val, work};
-    return reorth_entry(h, n, nnz, rp, col, val, dtype, b, m, lc, B, q, alpha, beta, V, vstride, W, passes, nullptr,
-                        nullptr, &nm);
+    return cycle_entry(h, n, OpSpec::normal(p, nnz, rp, col, val, t_rp, t_col, t_val, work), dtype, b, 0, m, lc, B,
+                       nullptr, q, alpha, beta, V, vstride, W, passes);
 }
 
 int lz_panel_compress(lz_handle *h, int64_t n, int b, int k, int r, lz_dtype dtype, void *V, int64_t vstride,
@@ -2338,45 +2309,13 @@ int lz_block_lanczos_reorth_resume(lz_handle *h, int64_t n, int64_t nnz, const i
                                                vstride, W, passes, nullptr, nullptr);
 }
 
-// lz_block_lanczos_reorth_resume and its _cheb (f) and _normal (nm) forms
-static int resume_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
-                        lz_dtype dtype, int b, int r, int m, int64_t lc, const void *sigma, void *q, void *alpha,
-                        void *beta, void *V, int64_t vstride, void *W, int passes, const lz_cheb *f, void *work,
-                        const NormalArgs *nm, const SeriesArgs *sr = nullptr)
-{
-    LZ_HANDLE_CHECK(h);
-    LZ_TRY(check_csr(nm ? nm->p : n, nnz, rp, col, val));
-    LZ_ARG_CHECK(m >= 1 && m <= kPanelMaxK, "the kept basis holds 1 <= m <= 64 blocks");
-    LZ_ARG_CHECK(r >= 1 && r < m, "a resumed solve keeps 1 <= r < m blocks");
-    LZ_TRY(panel_args(n, b, m, dtype, V, vstride));
-    LZ_ARG_CHECK(passes >= 0 && passes <= 2, "passes in {0, 1, 2}");
-    LZ_ARG_CHECK(lc >= 0 && lc < n, "lc must be a row index");
-    LZ_ARG_CHECK(sigma != nullptr, "sigma is NULL");
-    LZ_ARG_CHECK(q && alpha && beta && W, "NULL buffer");
-    {
-        const int64_t es = dtype == LZ_F64 ? 8 : 4;
-        const char *v0 = (const char *)V, *v1 = v0 + ((int64_t)(m - 1) * vstride + n * b) * es;
-        const char *w0 = (const char *)W;
-        LZ_ARG_CHECK(w0 + n * b * es <= v0 || w0 >= v1, "W and the panel V must be distinct buffers");
-    }
-    LZ_TRY(cheb_solve_args(f, work, n, b, m, dtype, V, vstride, W, nullptr));
-    LZ_TRY(normal_solve_args(nm, n, b, m, dtype, V, vstride, W, nullptr));
-    LZ_TRY(series_solve_args(sr, n, b, m, dtype, V, vstride, W, nullptr));
-    return by_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        return block_lanczos_reorth_resume<T>(h, n, make_op<T>(nnz, rp, col, val, f, work, nm, sr), b, r, m, lc,
-                                              (const T *)sigma, (T *)q, (T *)alpha, (T *)beta, (T *)V, vstride,
-                                              (T *)W, passes);
-    });
-}
-
 int lz_block_lanczos_reorth_resume_cheb(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
                                         const void *val, lz_dtype dtype, int b, int r, int m, int64_t lc,
                                         const void *sigma, void *q, void *alpha, void *beta, void *V, int64_t vstride,
                                         void *W, int passes, const lz_cheb *f, void *work)
 {
-    return resume_entry(h, n, nnz, rp, col, val, dtype, b, r, m, lc, sigma, q, alpha, beta, V, vstride, W, passes, f,
-                        work, nullptr);
+    return cycle_entry(h, n, OpSpec::filter(nnz, rp, col, val, f, work), dtype, b, r, m, lc, nullptr, sigma, q, alpha,
+                       beta, V, vstride, W, passes);
 }
 
 int lz_block_lanczos_reorth_resume_normal(lz_handle *h, int64_t n, int64_t p, int64_t nnz, const int64_t *rp,
@@ -2385,9 +2324,8 @@ int lz_block_lanczos_reorth_resume_normal(lz_handle *h, int64_t n, int64_t p, in
                                           int64_t lc, const void *sigma, void *q, void *alpha, void *beta, void *V,
                                           int64_t vstride, void *W, int passes, void *work)
 {
-    const NormalArgs nm{p, t_rp, t_col, t_val, work};
-    return resume_entry(h, n, nnz, rp, col, val, dtype, b, r, m, lc, sigma, q, alpha, beta, V, vstride, W, passes,
-                        nullptr, nullptr, &nm);
+    return cycle_entry(h, n, OpSpec::normal(p, nnz, rp, col, val, t_rp, t_col, t_val, work), dtype, b, r, m, lc, nullptr,
+                       sigma, q, alpha, beta, V, vstride, W, passes);
 }
 
 int lz_csr_spmm_axpby4(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
@@ -2403,19 +2341,9 @@ int lz_cheb_series_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp
 {
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(n, nnz, rp, col, val));
-    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    LZ_ARG_CHECK(n >= 1 && b >= 1 && b <= kMaxB, "n >= 1, b in [1,64]");
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
     LZ_ARG_CHECK(X && Y && work, "X/Y/work NULL");
-    const SeriesArgs sr{degree, lo, hi, gamma, work};
-    LZ_TRY(series_args(&sr));
-    const int64_t es = dtype == LZ_F64 ? 8 : 4, nb = n * b;
-    LZ_ARG_CHECK(blocks_apart(X, nb, Y, nb, es) && blocks_apart(work, 2 * nb, X, nb, es) &&
-                     blocks_apart(work, 2 * nb, Y, nb, es),
-                 "X, Y and work must be pairwise distinct");
-    return by_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        return cheb_series_apply<T>(h, n, nnz, rp, col, (const T *)val, b, sr, (const T *)X, (T *)Y, (T *)work);
-    });
+    return apply_entry(h, n, OpSpec::series(nnz, rp, col, val, degree, lo, hi, gamma, work), dtype, b, X, Y);
 }
 
 int lz_block_lanczos_reorth_series(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
@@ -2423,9 +2351,8 @@ int lz_block_lanczos_reorth_series(lz_handle *h, int64_t n, int64_t nnz, const i
                                    void *alpha, void *beta, void *V, int64_t vstride, void *W, int passes, int degree,
                                    double lo, double hi, const double *gamma, void *work)
 {
-    const SeriesArgs sr{degree, lo, hi, gamma, work};
-    return reorth_entry(h, n, nnz, rp, col, val, dtype, b, m, lc, B, q, alpha, beta, V, vstride, W, passes, nullptr,
-                        nullptr, nullptr, &sr);
+    return cycle_entry(h, n, OpSpec::series(nnz, rp, col, val, degree, lo, hi, gamma, work), dtype, b, 0, m, lc, B,
+                       nullptr, q, alpha, beta, V, vstride, W, passes);
 }
 
 int lz_block_lanczos_reorth_resume_series(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
@@ -2434,9 +2361,8 @@ int lz_block_lanczos_reorth_resume_series(lz_handle *h, int64_t n, int64_t nnz, 
                                           int64_t vstride, void *W, int passes, int degree, double lo, double hi,
                                           const double *gamma, void *work)
 {
-    const SeriesArgs sr{degree, lo, hi, gamma, work};
-    return resume_entry(h, n, nnz, rp, col, val, dtype, b, r, m, lc, sigma, q, alpha, beta, V, vstride, W, passes,
-                        nullptr, nullptr, nullptr, &sr);
+    return cycle_entry(h, n, OpSpec::series(nnz, rp, col, val, degree, lo, hi, gamma, work), dtype, b, r, m, lc, nullptr,
+                       sigma, q, alpha, beta, V, vstride, W, passes);
 }
 
 int lz_vector_lanczos(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,

@@ -46,11 +46,7 @@ struct BcgBlock {
 
 static int bcg_reserve(lz_handle *h, int b)
 {
-    const size_t had = h->bcg_cap;
-    LZ_TRY(grow_ws(h, &h->bcg_ws, &h->bcg_cap, sizeof(BcgState)));
-    // test support, as lz_init's: a workspace grown under LZ_POISON=1 starts NaN-filled
-    if (const char *pz = getenv("LZ_POISON"); h->bcg_cap != had && pz && pz[0] == '1')
-        LZ_HIP_TRY(hipMemsetAsync(h->bcg_ws, 0xFF, h->bcg_cap, h->stream));
+    LZ_TRY(grow_ws_poisoned(h, &h->bcg_ws, &h->bcg_cap, sizeof(BcgState)));
     // one b x b slab per block of the update
     return ensure_partials(h, (size_t)kBcgGridCap * b * b);
 }

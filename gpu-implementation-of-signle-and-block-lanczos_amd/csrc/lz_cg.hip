@@ -30,11 +30,7 @@ struct CgState {
 
 static int cg_reserve(lz_handle *h, int64_t n, int b)
 {
-    const size_t had = h->cg_cap;
-    LZ_TRY(grow_ws(h, &h->cg_ws, &h->cg_cap, sizeof(CgState)));
-    // test support, as lz_init's: a workspace grown under LZ_POISON=1 starts NaN-filled
-    if (const char *pz = getenv("LZ_POISON"); h->cg_cap != had && pz && pz[0] == '1')
-        LZ_HIP_TRY(hipMemsetAsync(h->cg_ws, 0xFF, h->cg_cap, h->stream));
+    LZ_TRY(grow_ws_poisoned(h, &h->cg_ws, &h->cg_cap, sizeof(CgState)));
     // the update's slabs are b doubles per block: half a dots slab each
     return dots_reserve(h, n, b, kCgGridCap);
 }

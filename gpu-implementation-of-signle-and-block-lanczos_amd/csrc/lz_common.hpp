@@ -167,6 +167,15 @@ inline int grow_ws(lz_handle *h, P **buf, size_t *cap_bytes, size_t bytes)
 {
     return grow_ws(h, reinterpret_cast<void **>(buf), cap_bytes, bytes);
 }
+// grow_ws for a workspace the tests want to start NaN-filled: under LZ_POISON=1 (test support, as
+// lz_init's) the buffer is filled whenever it grew.  Not grow_ws itself: its other workspaces are
+// not poisoned.
+int grow_ws_poisoned(lz_handle *h, void **buf, size_t *cap_bytes, size_t bytes);
+template <typename P>
+inline int grow_ws_poisoned(lz_handle *h, P **buf, size_t *cap_bytes, size_t bytes)
+{
+    return grow_ws_poisoned(h, reinterpret_cast<void **>(buf), cap_bytes, bytes);
+}
 // grow h->partials to hold at least `doubles`
 int ensure_partials(lz_handle *h, size_t doubles);
 // pass 1's 16-bit columns (col16_plan, wf_plan16): nnz int16 + the dword the kernel's range may end in

@@ -32,12 +32,7 @@ static int col_dots_grid(const lz_handle *h, int64_t n, int b)
 int dots_reserve(lz_handle *h, int64_t n, int b, int64_t min_slabs)
 {
     const int64_t P = std::max<int64_t>({ceil_div(n, (int64_t)48), (int64_t)col_dots_grid(h, n, b), min_slabs});
-    const size_t had = h->dots_cap;
-    LZ_TRY(grow_ws(h, &h->dots_ws, &h->dots_cap, sizeof(double) * (size_t)(P + kDotsFoldBlocks) * 2 * (size_t)b));
-    // test support, as lz_init's: a workspace grown under LZ_POISON=1 starts NaN-filled
-    if (const char *pz = getenv("LZ_POISON"); h->dots_cap != had && pz && pz[0] == '1')
-        LZ_HIP_TRY(hipMemsetAsync(h->dots_ws, 0xFF, h->dots_cap, h->stream));
-    return LZ_OK;
+    return grow_ws_poisoned(h, &h->dots_ws, &h->dots_cap, sizeof(double) * (size_t)(P + kDotsFoldBlocks) * 2 * (size_t)b);
 }
 
 // Block q of G sums rows [q n / G, (q + 1) n / G): row lane r takes rows r, r +
