@@ -592,18 +592,35 @@ static int store_beta_m(lz_handle *h, T *beta, int m, int64_t bb, T *const binv[
     return LZ_OK;
 }
 
-// the wavefront step's alpha products from the folded [S1 | S2 | G] at slab (lc: a local row, or -1)
-static WfAlpha wf_alpha(const double *slab, double *alpha, double *P2, const double *V, int64_t lc, double *qrow)
-{
-    return WfAlpha{slab, 1, alpha, P2, V, lc, qrow};
-}
+// How both wavefront loops end step j (made once per solve): the launches'
+// slab sets folded into slab = [S1 | S2 | G] and summed over the ranks (cm: a
+// distributed solve's), then one sqrtm launch for beta_j, its inverse, P1 =
+// beta_{j-1}^-1 beta_j (j > 0), alpha_j, P2 and q_j = V[lc] beta_j^-1 (lc: a
+// local row, or -1).  j = 0 follows a first launch that summed beta_0's Gram.
+struct WfTail {
+    lz_handle *h;
+    double *slab;
+    double *const *binv;
+    double *P1, *P2, *alpha, *beta, *q;
+    int64_t lc;
+    Comm *cm = nullptr;
+    int operator()(int j, const WfSlabs &sl, const double *V) const
+    {
+        constexpr int64_t bb = 256;
+        LZ_TRY(wf_fold16(h, sl, slab));
+        if (cm) LZ_TRY(cm->allreduce_sum(slab, 3 * bb, h->stream));
+        const WfAlpha wa{slab, 1, alpha + j * bb, P2, V, lc, q + j * 16};
+        return sqrtm_pair<double>(h, 16, nullptr, 1, beta + j * bb, binv[j & 1], nullptr, slab + 2 * bb,
+                                  j ? binv[(j - 1) & 1] : nullptr, j ? P1 : nullptr, &wa);
+    }
+};
 
-// fold one launch's P slab sets at h->partials2 into slab
-static int wf_fold_launch(lz_handle *h, int P, double *slab)
+// one launch's slab sets
+static WfSlabs wf_one_set(const double *part, int P)
 {
     WfSlabs sl;
-    sl.add(h->partials2, P);
-    return wf_fold16(h, sl, slab);
+    sl.add(part, P);
+    return sl;
 }
 
 // B^T B's per-block slabs (b = 16 fp64) on the handle's side stream, forked
@@ -638,28 +655,24 @@ static int block_lanczos_wf16(lz_handle *h, int64_t n, int64_t nnz, const int64_
     // else B^T B's slabs (Pg of them) were made beside the plan (gram_beside)
     if (!g0) LZ_TRY(sqrtm_pair<double>(h, 16, nullptr, Pg, beta, binv[0], nullptr));
     LZ_TRY(wf_reset16(h, n, wp));
+    const WfSolve ws{n, rp, col, val, pl.pairs, wp, n};
+    const WfTail tail{h, slab, binv, P1, P2, alpha, beta, q, lcl};
+    double *part = h->partials2;
     // Y_0 = A B, S1_0 = B^T Y_0 (g0: and G_0 = B^T B)
-    LZ_TRY(wf_step16(h, n, rp, col, pl.col16, val, pl.pairs, wp, nullptr, nullptr, g0 ? B : nullptr, nullptr,
-                     nullptr, nullptr, nullptr, B, Q0, 0, &P));
-    if (g0) {  // beta_0, its inverse, alpha_0, P2 and q_0 in one kernel, as every later step's
-        LZ_TRY(wf_fold_launch(h, P, slab));
-        const WfAlpha wa = wf_alpha(slab, alpha, P2, B, lcl, q);
-        LZ_TRY(sqrtm_pair<double>(h, 16, nullptr, 1, beta, binv[0], nullptr, slab + 512, nullptr, nullptr, &wa));
-    } else {
-        LZ_TRY(alpha_wf16(h, h->partials2, P, binv[0], nullptr, alpha, P2, B, lc, n, q));
-    }
+    LZ_TRY(wf_step16(h, ws, ws.first(B, Q0, g0), part, &P));
+    // g0: beta_0, its inverse, alpha_0, P2 and q_0 in one kernel, as every later step's
+    if (g0) LZ_TRY(tail(0, wf_one_set(part, P), B));
+    else LZ_TRY(alpha_wf16(h, part, P, binv[0], nullptr, alpha, P2, B, lc, n, q));
     const double *Vm1 = nullptr, *V0 = B;
+    // step j's pass 2: V_{j+1} into Vn (j = m - 1: the post-call state's W_m)
+    auto pass2 = [&](int j, double *Vn) { return WfPass2{Q0, Vm1, V0, Vn, binv[j & 1], j ? P1 : nullptr, P2}; };
     for (int j = 0; j + 1 < m; ++j) {
         double *Vn = j == 0 ? W : j == 1 ? Q1 : const_cast<double *>(Vm1);
-        LZ_TRY(wf_step16(h, n, rp, col, pl.col16, val, pl.pairs, wp, Q0, Vm1, V0, Vn, binv[j & 1], j ? P1 : nullptr,
-                         P2, Vn, Q0, j + 1, &P));
+        LZ_TRY(wf_step16(h, ws, ws.step(pass2(j, Vn), ws.all(), {Vn, Q0, ws.all()}, j + 1), part, &P));
         // the block slabs folded by 12 workgroups (one workgroup reading all
         // 1.5 MB took ~20 us), then beta_{j+1}, its inverse and P1 = beta_j^-1
         // beta_{j+1} from G, and (same launch) alpha_{j+1}, P2 and the row probe
-        LZ_TRY(wf_fold_launch(h, P, slab));
-        const WfAlpha wa = wf_alpha(slab, alpha + (j + 1) * bb, P2, Vn, lcl, q + (j + 1) * 16);
-        LZ_TRY(sqrtm_pair<double>(h, 16, nullptr, 1, beta + (j + 1) * bb, binv[(j + 1) & 1], nullptr, slab + 512,
-                                  binv[j & 1], P1, &wa));
+        LZ_TRY(tail(j + 1, wf_one_set(part, P), Vn));
         Vm1 = V0;
         V0 = Vn;
     }
@@ -670,15 +683,12 @@ static int block_lanczos_wf16(lz_handle *h, int64_t n, int64_t nnz, const int64_
     // pass-2-only step launch whose updaters also store Q (QO; the LDS-DMA
     // streams of pass 2, 4 waves per CU); otherwise the MFMA strip kernel
     if (h->final_state) {
-        if (wp.var == 111) {
-            int Pq = 0;
-            LZ_TRY(wf_step16(h, n, rp, col, pl.col16, val, pl.pairs, wp, Q0, Vm1, V0, W, binv[(m - 1) & 1],
-                             Vm1 ? P1 : nullptr, P2, W, m >= 2 ? Q1 : nullptr, m, &Pq, -1, 0, 0, nullptr, nullptr,
-                             Q0, true));
-        } else {
-            LZ_TRY(final_state<double>(h, n, 16, Q0, Vm1, V0, nullptr, binv[(m - 1) & 1], Vm1 ? P1 : nullptr, P2, W,
-                                       Q0, m >= 2 ? Q1 : nullptr));
-        }
+        const WfPass2 p2 = pass2(m - 1, W);
+        if (wp.var == 111)
+            LZ_TRY(wf_step16(h, ws, ws.post_call(p2, m, Q0, m >= 2 ? Q1 : nullptr), part, &P));
+        else
+            LZ_TRY(final_state<double>(h, n, 16, p2.Yj, p2.Vprev, p2.Vj, nullptr, p2.binv, p2.P1, p2.P2, W, Q0,
+                                       m >= 2 ? Q1 : nullptr));
     }
     return LZ_OK;
 }
@@ -1454,7 +1464,6 @@ static int dist_solve_wf16(const DistCtx &cx, const int64_t *rp, const int32_t *
     // shape), summed by the first launch's consumers
     // and all-reduced with its S1; otherwise a Gram, its own all-reduce and
     // sqrtm first.  V_0 = B with its halo / in every slot
-    LZ_ARG_CHECK(!g0 || wp.var == 111, "beta_0's Gram in the first launch: the default shape only (internal)");
     if (!g0) {
         int np = 0;
         LZ_TRY(gram_partials<double>(h, n, 16, B, B, 16, &np));
@@ -1471,18 +1480,18 @@ static int dist_solve_wf16(const DistCtx &cx, const int64_t *rp, const int32_t *
     }
     LZ_TRY(wf_reset16(h, n, wp));
     // ---- Y_0 = A V_0 (pass 1 only, every tile; g0: and G_0), alpha_0
-    int G = 0;
-    LZ_TRY(wf_step16(h, n, rp, col, wp.col16, val, pairs, wp, nullptr, nullptr, g0 ? X0 : nullptr, nullptr, nullptr,
-                     nullptr, nullptr, X0, Y, 0, &G, nx, 0, T, h->partials2));
-    LZ_TRY(wf_fold_launch(h, G, slab));
-    LZ_TRY(cx.allreduce(3 * bb));
-    if (g0) {  // beta_0, its inverse, alpha_0, P2 and q_0 in one kernel
-        const WfAlpha wa = wf_alpha(slab, alpha, P2, ag ? slot : X0, lcl, q);
-        LZ_TRY(sqrtm_pair<double>(h, 16, nullptr, 1, beta, binv[0], nullptr, slab + 2 * bb, nullptr, nullptr, &wa));
-    } else {
-        LZ_TRY(alpha_wf16(h, slab, 1, binv[0], nullptr, alpha, P2, ag ? slot : X0, lcl, n, q));
-    }
+    const WfSolve ws{n, rp, col, val, pairs, wp, nx};
+    const WfTail tail{h, slab, binv, P1, P2, alpha, beta, q, lcl, cx.reduce ? cm : nullptr};
     const double *Vm1 = nullptr, *V0 = ag ? slot : X0;
+    int G = 0;
+    LZ_TRY(wf_step16(h, ws, ws.first(X0, Y, g0), h->partials2, &G));
+    if (g0) {  // beta_0, its inverse, alpha_0, P2 and q_0 in one kernel
+        LZ_TRY(tail(0, wf_one_set(h->partials2, G), V0));
+    } else {
+        LZ_TRY(wf_fold16(h, wf_one_set(h->partials2, G), slab));
+        LZ_TRY(cx.allreduce(3 * bb));
+        LZ_TRY(alpha_wf16(h, slab, 1, binv[0], nullptr, alpha, P2, V0, lcl, n, q));
+    }
     // all-gather form at N > 1: V_{j+1} into the slot over V_j, V_j into X1 (=
     // W) over V_{j-1}, so the slot can be all-gathered in place.  At one rank
     // there is no all-gather: V_{j+1} goes over V_{j-1}, alternating between
@@ -1492,26 +1501,25 @@ static int dist_solve_wf16(const DistCtx &cx, const int64_t *rp, const int32_t *
         double *Vn = sw ? slot : ((j & 1) ? X0 : X1);
         double *Vg = sw ? X0 : Vn;
         const double *Vprev = sw ? (j ? X1 : nullptr) : Vm1;
-        double *Vsave = sw ? X1 : nullptr;
+        const WfPass2 p2{Y, Vprev, V0, Vn, binv[j & 1], j ? P1 : nullptr, P2, sw ? X1 : nullptr};
         WfSlabs sl;
         double *part = h->partials2;
-        int Gp = 0, Gk = 0, G1 = 0, G2 = 0;
+        // one launch, its slab sets behind the earlier launches'
+        auto launch = [&](const WfLaunch &L) -> int {
+            int g = 0;
+            LZ_TRY(wf_step16(h, ws, L, part, &g));
+            sl.add(part, g);
+            part += 3 * (int64_t)g * 256;
+            return LZ_OK;
+        };
         if (pre) {  // pass 2 of the requested rows' tiles, then their exchange beside the step launch
-            const int64_t qa[4] = {0, sh, st, T};
-            LZ_TRY(wf_step16(h, n, rp, col, wp.col16, val, pairs, wp, Y, Vprev, V0, Vn, binv[j & 1],
-                             j ? P1 : nullptr, P2, Vg, Y, j + 1, &Gp, nx, 0, 0, part, qa, Vsave));
-            sl.add(part, Gp);
-            part += 3 * (int64_t)Gp * 256;
+            LZ_TRY(launch(ws.pass2(p2, {0, sh}, {st, T}, j + 1)));
             LZ_TRY(stream_fork(h, h->ev_cx, h->xstream));
             LZ_TRY(cx.exchange(Vg, h->xstream));
             LZ_HIP_TRY(hipEventRecord(h->ev_xd, h->xstream));
         }
         // the step launch: pass 2 (the other tiles) + pass 1 of the interior tiles
-        const int64_t qk[4] = {pre ? sh : 0, pre ? st : T, T, T};
-        LZ_TRY(wf_step16(h, n, rp, col, wp.col16, val, pairs, wp, Y, Vprev, V0, Vn, binv[j & 1], j ? P1 : nullptr,
-                         P2, Vg, Y, j + 1, &Gk, nx, t0, t1, part, qk, Vsave));
-        sl.add(part, Gk);
-        part += 3 * (int64_t)Gk * 256;
+        LZ_TRY(launch(ws.step(p2, pre ? WfTiles{sh, st} : ws.all(), {Vg, Y, {t0, t1}}, j + 1)));
         if (exch) {
             // V_{j+1}'s halo rows / peers' slots, then pass 1 of the boundary
             // tiles: [0, t0) on the handle's stream and [t1, T) beside it on the
@@ -1522,28 +1530,14 @@ static int dist_solve_wf16(const DistCtx &cx, const int64_t *rp, const int32_t *
             else LZ_TRY(cx.exchange(Vg, h->stream));
             const bool two = t0 > 0 && t1 < T;
             if (two) LZ_TRY(stream_fork(h, h->ev_cx, h->xstream));
-            LZ_TRY(wf_step16(h, n, rp, col, wp.col16, val, pairs, wp, nullptr, nullptr, nullptr, nullptr, nullptr,
-                             nullptr, nullptr, Vg, Y, 0, &G1, nx, 0, t0, part));
-            sl.add(part, G1);
-            part += 3 * (int64_t)G1 * 256;
-            if (two) {
-                {
-                    StreamScope on_x(h, h->xstream);
-                    LZ_TRY(wf_step16(h, n, rp, col, wp.col16, val, pairs, wp, nullptr, nullptr, nullptr, nullptr,
-                                     nullptr, nullptr, nullptr, Vg, Y, 0, &G2, nx, t1, T, part));
-                }
-                LZ_TRY(stream_join(h, h->ev_bd, h->xstream));
-            } else {
-                LZ_TRY(wf_step16(h, n, rp, col, wp.col16, val, pairs, wp, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, Vg, Y, 0, &G2, nx, t1, T, part));
+            LZ_TRY(launch(ws.boundary(Vg, Y, {0, t0})));
+            {
+                StreamScope on_x(h, two ? h->xstream : h->stream);
+                LZ_TRY(launch(ws.boundary(Vg, Y, {t1, T})));
             }
-            sl.add(part, G2);
+            if (two) LZ_TRY(stream_join(h, h->ev_bd, h->xstream));
         }
-        LZ_TRY(wf_fold16(h, sl, slab));
-        LZ_TRY(cx.allreduce(3 * bb));
-        const WfAlpha wa = wf_alpha(slab, alpha + (j + 1) * bb, P2, Vn, lcl, q + (j + 1) * 16);
-        LZ_TRY(sqrtm_pair<double>(h, 16, nullptr, 1, beta + (j + 1) * bb, binv[(j + 1) & 1], nullptr, slab + 2 * bb,
-                                  binv[j & 1], P1, &wa));
+        LZ_TRY(tail(j + 1, sl, Vn));
         Vm1 = V0;
         V0 = Vn;
     }

@@ -210,8 +210,8 @@ int fused_update16_swap(lz_handle *h, int64_t n, double *Wn, double *Xown, const
 // C = A*B, 16 x 16 row-major fp64, on the stream
 int mm16(lz_handle *h, const double *A, const double *B, double *C);
 
-// ---- wavefront step, b = 16 fp64, one GPU (lz_wf.hip): pass 2 of step j and
-// pass 1 of step j + 1 in one launch (see the file header)
+// ---- wavefront step, b = 16 fp64, one GPU and the distributed forms (lz_wf.hip):
+// pass 2 of step j and pass 1 of step j + 1 in one launch (see the file header)
 struct WfPlan {
     bool ok = false;       // the wavefront step applies (n < 2^24, narrow column spans)
     int hback = 0, hfwd = 0;  // max tiles a tile's columns reach below / above it
@@ -231,24 +231,83 @@ int wf_plan16(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int
 // read through per-strip windows, checked here)
 // zero the pass-2 flags (start of a solve; epochs 1, 2, ... follow)
 int wf_reset16(lz_handle *h, int64_t n, const WfPlan &pl);
-// P2 == nullptr: pass 1 only (Y = A Vg, S1 slabs).  Otherwise V_{j+1} = Yj binv
-// - Vprev P1 - Vj P2 into Vout (== Vg; P1 == nullptr: no Vprev term), Y_{j+1}
-// = A Vout into Yo (may be Yj).  Slabs at h->partials2: S1 [0, G), S2 [G, 2G),
-// G [2G, 3G) of 256 doubles, *nparts = G.
-int wf_step16(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, const int16_t *col16,
-              const double *val, const uint64_t *pairs, const WfPlan &pl, const double *Yj, const double *Vprev,
-              const double *Vj, double *Vout, const double *binv, const double *P1, const double *P2,
-              const double *Vg, double *Yo, int epoch, int *nparts, int64_t nx = -1, int64_t p1a = 0,
-              int64_t p1b = -1, double *part = nullptr, const int64_t *q = nullptr, double *Vsave = nullptr,
-              bool qo = false);
-// (qo: the one-GPU solve's post-call state -- a pass-2-only launch, Q =
-// V_j beta^-1 also stored into Vsave and, when not null, Yo; the default shape
-// only, else LZ_E_ARG)
-// (nx: rows of Vg, default n; pass 1 over tiles [p1a, p1b), default all; slabs
-// at part, default h->partials2; q: pass-2 tiles [q[0], q[1]) u [q[2], q[3]),
-// default all -- two ranges only without pass-1 tiles; Vout = Vg + 16 xoff;
-// Vsave: pass 2 also stores V_j's rows there (the all-gather form), 111 / wide
-// shapes only)
+struct WfTiles {  // tiles [a, b)
+    int64_t a, b;
+};
+// Pass 2: V_{j+1} = Yj binv - Vprev P1 - Vj P2 into Vout (P1 == nullptr: no
+// Vprev term, step 0; Vprev and Vout may alias), S2 and G slabs
+struct WfPass2 {
+    const double *Yj, *Vprev, *Vj;
+    double *Vout;
+    const double *binv, *P1, *P2;
+    double *Vsave = nullptr;  // SW: V_j's rows are also stored there (the all-gather form; 111 / wide shapes only)
+};
+// Pass 1: Yo = A Vg over the tiles t (Yo may be pass 2's Yj), S1 slabs
+struct WfPass1 {
+    const double *Vg;
+    double *Yo;
+    WfTiles t;
+    bool gram = false;  // the consumers also sum G = Vg^T Vg (a first launch)
+};
+// one launch: the caller states its role through WfSolve's functions below
+struct WfLaunch {
+    enum Role { kFirst, kBoundary, kStep, kPass2, kPostCall } role;
+    WfPass1 p1;
+    WfPass2 p2;
+    WfTiles q, q2;  // pass 2's tiles: q u q2
+    int epoch = 0;  // of pass 2's flags (1, 2, ... after wf_reset16; pass 1 alone polls none)
+    double *Q0 = nullptr, *Q1 = nullptr;  // kPostCall's Q stores
+};
+// What is fixed for a solve: the operator, the strips' row orders
+// (strip_pairs), the plan (with col16, xoff and tr) and the gather source's
+// row count nx (a rank's own + halo rows, or the all-gather form's n_pad * N;
+// one GPU: n)
+struct WfSolve {
+    int64_t n;
+    const int64_t *rp;
+    const int32_t *col;
+    const double *val;
+    const uint64_t *pairs;
+    const WfPlan &pl;
+    int64_t nx;
+    int64_t T() const { return (n + pl.tr - 1) / pl.tr; }
+    WfTiles all() const { return {0, T()}; }
+    WfTiles none() const { return {T(), T()}; }
+    // a solve's first launch: pass 1 over every tile on Vg = V_0; gram: and
+    // beta_0's Gram (the default shape only, wf_first_gram; else LZ_E_ARG)
+    WfLaunch first(const double *Vg, double *Yo, bool gram) const
+    {
+        return {WfLaunch::kFirst, {Vg, Yo, all(), gram}, {}, all(), none()};
+    }
+    // a rank's boundary tiles t, once the exchange has landed: pass 1 alone
+    WfLaunch boundary(const double *Vg, double *Yo, WfTiles t) const
+    {
+        return {WfLaunch::kBoundary, {Vg, Yo, t}, {}, all(), none()};
+    }
+    // a step: pass 2 of step j over the tiles q and pass 1 of step j + 1 over
+    // p1.t, gathering from Vg with Vout = Vg + 16 xoff
+    WfLaunch step(const WfPass2 &p2, WfTiles q, const WfPass1 &p1, int epoch) const
+    {
+        return {WfLaunch::kStep, p1, p2, q, none(), epoch};
+    }
+    // pass 2 alone over qa u qb (the requested rows' tiles, ahead of their
+    // exchange; the step launch that follows takes the tiles between them).
+    // (No pass-1 tiles: the kernel still gets the step's gather source and Y)
+    WfLaunch pass2(const WfPass2 &p2, WfTiles qa, WfTiles qb, int epoch) const
+    {
+        return {WfLaunch::kPass2, {p2.Vout - 16 * pl.xoff, const_cast<double *>(p2.Yj), {0, 0}}, p2, qa, qb, epoch};
+    }
+    // the one-GPU solve's post-call state: pass 2 alone over every tile (W_m
+    // into Vout) that also stores Q = Vj binv into Q0 and, when not null, Q1.
+    // The default shape on the whole source, without SW, else LZ_E_ARG
+    WfLaunch post_call(const WfPass2 &p2, int epoch, double *Q0, double *Q1) const
+    {
+        return {WfLaunch::kPostCall, {p2.Vout, nullptr, {0, 0}}, p2, all(), none(), epoch, Q0, Q1};
+    }
+};
+// Slabs at part: S1 [0, G), S2 [G, 2G), G [2G, 3G) of 256 doubles each, one per
+// block; *nparts = G (0: the launch had no tiles and did not run)
+int wf_step16(lz_handle *h, const WfSolve &ws, const WfLaunch &L, double *part, int *nparts);
 // one step's slab sets (set t: [S1 | S2 | G] of g[t] block slabs at p[t]);
 // wf_fold16: out[0..768) = [S1 | S2 | G] summed over every set, in order
 struct WfSlabs {

@@ -1,4 +1,5 @@
-// lz_wf.hip -- the wavefront block-Lanczos step: b = 16, fp64, one GPU.
+// lz_wf.hip -- the wavefront block-Lanczos step: b = 16, fp64, on one GPU and
+// per rank of the distributed forms (halo and all-gather).
 //
 // The two-pass Q-free step (lz_fused.hip) runs pass 1 (the SpMM plus its MFMA
 // epilogue) and pass 2 (W'' = W' - W_j P2) as separate launches, because pass
@@ -841,32 +842,32 @@ int wf_plan16(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int
     return LZ_OK;
 }
 
-int wf_step16(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, const int16_t *col16,
-              const double *val, const uint64_t *pairs, const WfPlan &pl, const double *Yj, const double *Vprev,
-              const double *Vj, double *Vout, const double *binv, const double *P1, const double *P2,
-              const double *Vg, double *Yo, int epoch, int *nparts, int64_t nx, int64_t p1a, int64_t p1b,
-              double *part, const int64_t *q, double *Vsave, bool qo)
+int wf_step16(lz_handle *h, const WfSolve &ws, const WfLaunch &L, double *part, int *nparts)
 {
-    const int64_t T = ceil_div(n, (int64_t)pl.tr);
-    const int64_t xoff = pl.xoff;
-    if (nx < 0) nx = n;
-    if (p1b < 0) p1b = T;
-    if (!part) part = h->partials2;
-    // pass-2 tiles [q0, q1) u [q2, q3) (default: all of them)
-    const int64_t q0 = q ? q[0] : 0, q1 = q ? q[1] : T, q2 = q ? q[2] : T, q3 = q ? q[3] : T;
+    const WfPlan &pl = ws.pl;
+    const WfPass1 &p1 = L.p1;
+    const WfPass2 &p2 = L.p2;
+    const int64_t n = ws.n, nx = ws.nx, T = ws.T(), xoff = pl.xoff;
+    const int64_t p1a = p1.t.a, p1b = p1.t.b, q0 = L.q.a, q1 = L.q.b, q2 = L.q2.a, q3 = L.q2.b;
+    const bool has_p2 = L.role >= WfLaunch::kStep, qo = L.role == WfLaunch::kPostCall;
+    // (beta_0's Gram in a first launch: the default shape only, wf_first_gram)
+    const bool g0 = L.role == WfLaunch::kFirst && p1.gram;
+    const bool sw = has_p2 && p2.Vsave != nullptr;
+    const int16_t *col16 = pl.col16;
     LZ_ARG_CHECK(xoff >= 0 && xoff + n <= nx && 0 <= p1a && p1a <= p1b && p1b <= T, "wavefront step ranges");
-    LZ_ARG_CHECK(0 <= q0 && q0 <= q1 && q1 <= q2 && q2 <= q3 && q3 <= T && (p1a == p1b || q2 == q3),
-                 "wavefront step pass-2 ranges");
+    LZ_ARG_CHECK(0 <= q0 && q0 <= q1 && q1 <= q2 && q2 <= q3 && q3 <= T, "wavefront step pass-2 ranges");
     LZ_ARG_CHECK(pl.ok && n < (1 << 24), "wavefront step: wf_plan16 first");
-    LZ_ARG_CHECK(pairs != nullptr, "strip row orders (strip_pairs) missing");
-    LZ_ARG_CHECK(P2 == nullptr || (Yj && Vj && Vout && binv && Vout == Vg + 16 * xoff), "wavefront step buffers");
-    LZ_ARG_CHECK(qo || Vsave == nullptr || (P2 && pl.var != 0), "wavefront step: SW stores (the 111 / wide shapes)");
-    LZ_ARG_CHECK(!qo || (P2 && Vsave && pl.var == 111 && p1a == p1b && xoff == 0 && (nx < 0 || nx == n) && !q),
-                 "wavefront post-call state: a one-GPU pass-2-only launch of the default shape");
+    LZ_ARG_CHECK(ws.pairs != nullptr, "strip row orders (strip_pairs) missing");
+    LZ_ARG_CHECK(!has_p2 || (p2.Yj && p2.Vj && p2.Vout && p2.binv && p2.P2 && p2.Vout == p1.Vg + 16 * xoff),
+                 "wavefront step buffers");
+    LZ_ARG_CHECK(!sw || (pl.var != 0 && !qo), "wavefront step: SW stores (the 111 / wide shapes)");
+    LZ_ARG_CHECK(!qo || (L.Q0 && pl.var == 111 && xoff == 0 && nx == n),
+                 "wavefront post-call state: a one-GPU launch of the default shape");
+    LZ_ARG_CHECK(!g0 || pl.var == 111, "wavefront first launch with beta_0's Gram: the default shape only (internal)");
     static_assert(12 <= kPairPad, "row orders must cover the last tile's strips");
     // pass 2 covers its tile ranges when it runs; a pass-1-only launch its range
     const int64_t nq = (q1 - q0) + (q3 - q2);
-    const int64_t work = P2 ? std::max(nq, p1b - p1a) : p1b - p1a;
+    const int64_t work = has_p2 ? std::max(nq, p1b - p1a) : p1b - p1a;
     if (work <= 0) {
         *nparts = 0;
         return LZ_OK;
@@ -889,10 +890,6 @@ int wf_step16(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, co
 #else
     constexpr int dbg = 0;
 #endif
-    if (P2 && nq == 0 && p1a == p1b) {  // nothing to do
-        *nparts = 0;
-        return LZ_OK;
-    }
     // the updaters' pace (tiles ahead of the block's pass 1): at least the
     // tiles a pass-1 tile reaches ahead in the block's order, plus two
     const int KB = grid < 8 ? grid : grid / 8;
@@ -948,27 +945,17 @@ int wf_step16(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, co
             rc = LZ_E_HIP;
             return;
         }
-        const int2 *deps = static_cast<const int2 *>(h->wf_deps);
-        int *flags = h->wf_flags, *err = h->err_flag;
-        int64_t a_n = n, a_hb = pl.hback, a_nx = nx, a_p1a = p1a, a_p1b = p1b, a_T = T, a_xo = xoff, a_q0 = q0,
-                a_q1 = q1, a_q2 = q2, a_q3 = q3;
-        int a_ep = epoch, a_lead = lead, a_dbg = dbg, a_cp = cpol;
-        double *a_sv = Vsave;
-        const int64_t *a_rp = rp;
-        const int32_t *a_col = col;
-        const int16_t *a_c16 = col16;
-        const double *a_val = val, *a_Yj = Yj, *a_Vp = Vprev, *a_Vj = Vj, *a_bi = binv, *a_P1 = P1, *a_P2 = P2,
-                     *a_Vg = Vg;
-        const uint64_t *a_pr = pairs;
-        double *a_Vo = Vout, *a_Yo = Yo, *a_part = part;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * waves), 0, h->stream, a_n, a_rp, a_col, a_c16, a_val, a_pr,
-                           a_Yj, a_Vp, a_Vj, a_Vo, a_bi, a_P1, a_P2, a_Vg, a_Yo, deps, flags, a_ep, a_hb, a_lead,
-                           a_part, err, a_dbg, a_nx, a_p1a, a_p1b, a_T, a_cp, a_xo, a_q0, a_q1, a_q2, a_q3, a_sv);
+        // the kernel's Vj doubles as the first launch's Gram switch; Yo and
+        // Vsave carry Q1 and Q0 in the post-call state (XO 2)
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * waves), 0, h->stream, n, ws.rp, ws.col, col16, ws.val, ws.pairs,
+                           p2.Yj, p2.Vprev, g0 ? p1.Vg : p2.Vj, p2.Vout, p2.binv, p2.P1, p2.P2, p1.Vg,
+                           qo ? L.Q1 : p1.Yo, static_cast<const int2 *>(h->wf_deps), h->wf_flags, L.epoch,
+                           (int64_t)pl.hback, lead, part, h->err_flag, dbg, nx, p1a, p1b, T, cpol, xoff, q0, q1, q2, q3,
+                           qo ? L.Q0 : p2.Vsave);
     };
     // LDS (<= 160 KB): strip slots per updater DU + 1, fewer with 32-bit columns
     constexpr int cap12 = 12 * 16 * kWfCapPerRow, cap11 = 11 * 16 * kWfCapPerRow, cap10 = 10 * 16 * kWfCapPerRow;
     // (the instantiation must match pl.tr: the tile count above is the host's)
-    const bool sw = Vsave != nullptr && !qo;
     // the one-GPU solve's launches (every pass-2 tile, whole source, no SW) take
     // the specialised form (GEN = false) of the default shapes
     const bool one = !sw && xoff == 0 && nx == n && q0 == 0 && q1 == T && q2 == T && q3 == T;
@@ -978,12 +965,7 @@ int wf_step16(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, co
 #else
     const bool spec = one;
 #endif
-    // (beta_0's Gram in a first launch: the default shape only, wf_first_gram)
-    const bool g0 = !P2 && Vj != nullptr;
-    if (g0 && pl.var != 111) {
-        set_error("wavefront first launch with beta_0's Gram: the default shape only (internal)");
-        rc = LZ_E_ARG;
-    } else if (qo && col16) go(k_wf16<11, cap11, kWfK, 1, 4, 1, true, false, false, 2>, 11 + 1 + 4);
+    if (qo && col16) go(k_wf16<11, cap11, kWfK, 1, 4, 1, true, false, false, 2>, 11 + 1 + 4);
     else if (qo) go(k_wf16<11, cap11, kWfK, 1, 4, 1, false, false, false, 2>, 11 + 1 + 4);
     else if (g0 && col16 && spec) go(k_wf16<11, cap11, kWfK, 1, 4, 1, true, false, false, 1>, 11 + 1 + 4);
     else if (g0 && col16) go(k_wf16<11, cap11, kWfK, 1, 4, 1, true, false, true, 1>, 11 + 1 + 4);
