@@ -1610,12 +1610,13 @@ static int shape_args(lz_dtype dtype, int64_t n, int64_t n_min, int b, int b_max
 }
 
 // lz_cg_solve and lz_bcg_solve: the same arguments under the same rules but the widest block, b_max;
-// solve(...) is cg_solve or bcg_solve in the dtype
+// solve(...) is cg_solve or bcg_solve in the dtype.  lz_pcg_solve: work_blocks = 5 and `also`, its
+// dinv's span, apart from the three like they are from each other
 template <typename Solve>
 static int krylov_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
                         lz_dtype dtype, int b, int b_max, double shift, const void *B, void *X, void *work,
                         const lz_cg_opts *opts, int *iters, int *status, double *resid, double *est, int *info,
-                        Solve solve)
+                        Solve solve, int work_blocks = 4, Span also = {})
 {
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(n, nnz, rp, col, val));
@@ -1624,8 +1625,9 @@ static int krylov_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp,
     LZ_ARG_CHECK(opts->tol > 0.0 && std::isfinite(opts->tol) && std::isfinite(shift), "tol > 0, tol and shift finite");
     LZ_ARG_CHECK(opts->max_iter >= 0 && opts->max_restarts >= 0, "max_iter, max_restarts >= 0");
     const int64_t nb = n * b;
-    LZ_ARG_CHECK(pairwise_apart({span_of(B, nb, dtype), span_of(X, nb, dtype), span_of(work, 4 * nb, dtype)}),
-                 "B, X and work must be pairwise distinct");
+    LZ_ARG_CHECK(pairwise_apart({span_of(B, nb, dtype), span_of(X, nb, dtype), span_of(work, work_blocks * nb, dtype),
+                                 also}),
+                 also.p ? "B, X, work and dinv must be pairwise distinct" : "B, X and work must be pairwise distinct");
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return solve(h, n, nnz, rp, col, (const T *)val, b, shift, (const T *)B, (T *)X, (T *)work, *opts, iters, status,
@@ -2186,6 +2188,56 @@ int lz_cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const i
 {
     return krylov_entry(h, n, nnz, rp, col, val, dtype, b, kMaxB, shift, B, X, work, opts, iters, status, resid, est, info,
                         [](auto... a) { return cg_solve(a...); });
+}
+
+int lz_pcg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *coef, const void *dinv, void *R,
+                  const void *W, void *P, void *S, void *X, void *Z, double *dots)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
+    LZ_ARG_CHECK(coef && dinv && R && W && P && S && X && Z && dots, "coef/dinv/R/W/P/S/X/Z/dots NULL");
+    const int64_t nb = n * b;
+    LZ_ARG_CHECK(pairwise_apart({span_of(R, nb, dtype), span_of(W, nb, dtype), span_of(P, nb, dtype),
+                                 span_of(S, nb, dtype), span_of(X, nb, dtype), span_of(Z, nb, dtype),
+                                 span_of(dinv, n, dtype)}),
+                 "R, W, P, S, X, Z and dinv must be pairwise distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return pcg_update<T>(h, n, b, coef, (const T *)dinv, (T *)R, (const T *)W, (T *)P, (T *)S, (T *)X, (T *)Z, dots);
+    });
+}
+
+int lz_csr_jacobi(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                  lz_dtype dtype, double shift, void *dinv, int64_t *n_bad)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    LZ_ARG_CHECK(n >= 1 && n < (1LL << 31), "1 <= n < 2^31 (32-bit columns)");
+    LZ_ARG_CHECK(dinv && n_bad && std::isfinite(shift), "dinv/n_bad NULL, or shift not finite");
+    LZ_ARG_CHECK(apart(span_of(dinv, n, dtype), {Span{rp, (n + 1) * 8}, Span{col, nnz * 4}, span_of(val, nnz, dtype)}),
+                 "dinv must not overlap the operator");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return csr_jacobi<T>(h, n, rp, col, (const T *)val, shift, (T *)dinv, n_bad);
+    });
+}
+
+int lz_pcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                 lz_dtype dtype, int b, double shift, const void *dinv, const void *B, void *X, void *work,
+                 const lz_cg_opts *opts, int *iters, int *status, double *resid, double *est, int *info)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_ARG_CHECK(dinv != nullptr, "dinv is NULL (lz_cg_solve is the solve without a preconditioner)");
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    return krylov_entry(
+        h, n, nnz, rp, col, val, dtype, b, kMaxB, shift, B, X, work, opts, iters, status, resid, est, info,
+        [dinv](lz_handle *hh, int64_t nn, int64_t nz, const int64_t *r, const int32_t *c, auto *v, int bb, double sh,
+               auto *Bt, auto *Xt, auto *wk, const lz_cg_opts &o, int *it, int *stt, double *rs, double *es, int *inf) {
+            using T = std::remove_cv_t<std::remove_pointer_t<decltype(Xt)>>;
+            return pcg_solve<T>(hh, nn, nz, r, c, v, bb, sh, (const T *)dinv, Bt, Xt, wk, o, it, stt, rs, es, inf);
+        },
+        kPcgWorkBlocks, span_of(dinv, std::max<int64_t>(n, 0), dtype));
 }
 
 int lz_bcg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *xi, const double *E, const void *S,

@@ -87,4 +87,35 @@ LZ_CG_HD inline void cg_step_rule(double gamma, double delta, double thr, bool f
     s.iters += 1;
 }
 
+// The same step with a diagonal preconditioner: z = D^-1 r, rz = r.z,
+// rr = r.r, delta = (M z).z.  The freeze test and est2 are on rr, the true residual
+// norm; the coefficients come from rz (beta = rz / rz_prev, kept in gamma_prev).  One
+// more breakdown: rz <= 0 or not finite on a live column -- the preconditioner is not
+// positive on this residual -- is status 2 like a bad denominator.
+LZ_CG_HD inline void pcg_step_rule(double rz, double rr, double delta, double thr, bool first, int max_iter, CgCol &s,
+                                   double &alpha, double &beta)
+{
+    alpha = 0.0;
+    beta = 0.0;
+    if (!s.live) return;
+    if (rr <= thr || s.iters >= max_iter) {
+        s.live = 0;
+        s.est2 = rr;
+        return;
+    }
+    const double bt = first ? 0.0 : rz / s.gamma_prev;
+    const double den = first ? delta : delta - bt * rz / s.alpha_prev;
+    if (!(rz > 0.0) || !std::isfinite(rz) || !(den > 0.0) || !std::isfinite(den)) {
+        s.live = 0;
+        s.status = kCgNotPd;
+        s.est2 = rr;
+        return;
+    }
+    alpha = rz / den;
+    beta = bt;
+    s.gamma_prev = rz;
+    s.alpha_prev = alpha;
+    s.iters += 1;
+}
+
 }  // namespace lz

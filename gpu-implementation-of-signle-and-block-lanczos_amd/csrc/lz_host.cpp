@@ -689,6 +689,25 @@ int lzh_cg_scalars(int b, int first, int max_iter, const double *gamma, const do
     return 0;
 }
 
+// the preconditioned step rule, as k_pcg_scalars applies it
+int lzh_pcg_scalars(int b, int first, int max_iter, const double *rz, const double *rr, const double *delta,
+                    const double *thr, double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters,
+                    int *status, double *coef, int *nlive)
+{
+    if (b < 1 || !rz || !rr || !delta || !thr || !gamma_prev || !alpha_prev || !est2 || !live || !iters || !status ||
+        !coef || !nlive)
+        return -1;
+    *nlive = 0;
+    for (int c = 0; c < b; ++c) {
+        lz::CgCol s{gamma_prev[c], alpha_prev[c], est2[c], live[c], iters[c], status[c]};
+        lz::pcg_step_rule(rz[c], rr[c], delta[c], thr[c], first != 0, max_iter, s, coef[c], coef[b + c]);
+        gamma_prev[c] = s.gamma_prev, alpha_prev[c] = s.alpha_prev, est2[c] = s.est2;
+        live[c] = s.live, iters[c] = s.iters, status[c] = s.status;
+        *nlive += s.live;
+    }
+    return 0;
+}
+
 // ---- block conjugate gradients: the b x b rules of lz_bcg.hpp, as the one-workgroup kernels of
 // lz_bcg.hip apply them, on host arrays; ctl = {live, reason, iters, 0}
 static bool bcg_args(int b, const int *ctl) { return b >= 1 && b <= lz::kBcgMaxB && ctl; }

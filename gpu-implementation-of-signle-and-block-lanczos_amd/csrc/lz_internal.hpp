@@ -64,6 +64,24 @@ template <typename T>
 int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
              double shift, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status, double *resid,
              double *est, int *info);
+// ---- diagonally preconditioned conjugate gradients (lz_cg.hip)
+// k_pcg_update: k_cg_update's two forms and constants, one slab of 2 b doubles per block.
+// k_csr_jacobi: kJacobiLanes lanes per row, kJacobiRows rows per workgroup pass.
+// lz_pcg_solve's work: kPcgWorkBlocks blocks, [R | W | P | S | Z].
+constexpr int kJacobiLanes = 8, kJacobiRows = kCgThreads / kJacobiLanes, kPcgWorkBlocks = 5;
+// lz_pcg_update (include/lz_hip.h)
+template <typename T>
+int pcg_update(lz_handle *h, int64_t n, int b, const double *coef, const T *dinv, T *R, const T *W, T *P, T *S, T *X,
+               T *Z, double *dots);
+// lz_csr_jacobi (include/lz_hip.h); synchronises the stream once (the count)
+template <typename T>
+int csr_jacobi(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, const T *val, double shift, T *dinv,
+               int64_t *n_bad);
+// lz_pcg_solve (include/lz_hip.h)
+template <typename T>
+int pcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+              double shift, const T *dinv, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status,
+              double *resid, double *est, int *info);
 // ---- block conjugate gradients (lz_bcg.hip)
 // k_bcg_update / k_bcg_direction: kBcgThreads threads per block; the b = 16 fp64 MFMA
 // form covers kBcgRows16 rows per block pass (one 16-row tile per wave), the b = 32 fp32

@@ -445,6 +445,50 @@ int lz_cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, co
                 lz_dtype dtype, int b, double shift, const void *B, void *X, void *work, const lz_cg_opts *opts,
                 int *iters, int *status, double *resid, double *est, int *info);
 
+/* ------------- diagonally preconditioned conjugate gradients (no reference counterpart)
+ * lz_cg_solve's method with z = D^-1 r, D^-1 = diag(dinv), per column:
+ *   gamma = r.z, rho = r.r, delta = (M z).z, beta = gamma / gamma_prev,
+ *   alpha = gamma / (delta - beta gamma / alpha_prev),
+ *   p = z + beta p, s = M z + beta s, x += alpha p, r -= alpha s, z = D^-1 r.
+ * Jacobi (dinv from lz_csr_jacobi) pays on operators whose diagonal varies over orders
+ * of magnitude; on a constant diagonal it changes nothing but the cost.
+ *
+ * lz_pcg_update: lz_cg_update's pass with the preconditioner, on the same shapes.  With
+ * dv = dinv[row] (n elements of the dtype, device, read only), element by element:
+ *   z0 = dv * R (one rounded product: the bits the last pass stored in Z, so Z is not read)
+ *   P = fma(beta, P, z0),  S = fma(beta, S, W),  X = fma(alpha, P, X),  R = fma(-alpha, S, R),
+ *   Z = dv * R
+ * under lz_cg_update's zero-coefficient rules (a frozen column keeps X and R bit for bit
+ * and its Z is rewritten with the same bits), and dots[c] = sum_i R[i][c] Z[i][c],
+ * dots[b + c] = sum_i R[i][c]^2 of the stored values (2 b doubles, device; fp64, fixed
+ * order, no atomics).  Five blocks and the n-vector read, five blocks written.  The same
+ * two forms, LZ_CG_GENERIC and LZ_CG_NT switches; Z is stored with non-temporal stores,
+ * as measured (LZ_PCG_Z_NT=0, measurement: plain like R's).  The six blocks and dinv must
+ * not overlap: LZ_E_ARG. */
+int lz_pcg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *coef, const void *dinv, void *R,
+                  const void *W, void *P, void *S, void *X, void *Z, double *dots);
+/* dinv[i] = 1 / d_i in the dtype, d_i = (the sum of the stored entries of row i whose
+ * column is i, in the order of their positions, in fp64) + shift rounded once to the
+ * dtype; a row without a stored diagonal has d_i = shift.  Columns need not be sorted;
+ * an empty row and nnz = 0 are valid; 1 <= n < 2^31.  A row whose d_i is <= 0 or not
+ * finite, or whose 1 / d_i the dtype cannot hold, stores 0 and is counted: *n_bad (host)
+ * receives the count, the call's one host synchronisation.  dinv: n elements, device,
+ * apart from the operator's arrays.  The same bits run to run. */
+int lz_csr_jacobi(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const void *val,
+                  lz_dtype dtype, double shift, void *dinv, int64_t *n_bad);
+/* lz_cg_solve with the preconditioner diag(dinv): the same arguments, options, results,
+ * status codes and info[3], but work is 5 n b elements ([R | W | P | S | Z]) and dinv (n
+ * elements of the dtype, device, positive and finite: the caller's promise) is apart
+ * from B, X and work; dinv NULL is LZ_E_ARG.  A column stops on the true residual norm
+ * r.r <= tol^2 |B_c|^2; resid is measured, est the recurrence's last r.r.  Start and
+ * every restart: R = B - M X with its dots, one row-local launch for Z = D^-1 R and
+ * r.z, the start rule.  Per iteration: the SpMM with dots on Z, one one-workgroup
+ * launch, one lz_pcg_update.  Status 2 also when r.z <= 0 or is not finite on a live
+ * column: the preconditioner is not positive on this residual. */
+int lz_pcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const void *val,
+                 lz_dtype dtype, int b, double shift, const void *dinv, const void *B, void *X, void *work,
+                 const lz_cg_opts *opts, int *iters, int *status, double *resid, double *est, int *info);
+
 /* ----------------------------- block conjugate gradients (no reference counterpart)
  * The b columns share one Krylov space: Dubrulle's BCGrQ with the symmetric
  * orthonormalisation of lz_sqrtm_pair in place of the QR.  M = A + shift I; the

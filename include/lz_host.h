@@ -153,6 +153,15 @@ int lzh_cg_start(int b, int max_iter, int initial, const double *gamma, const do
 int lzh_cg_scalars(int b, int first, int max_iter, const double *gamma, const double *delta, const double *thr,
                    double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters, int *status,
                    double *coef, int *nlive);
+/* lzh_pcg_scalars: one iteration of lz_pcg_solve (diagonal preconditioner, z = D^-1 r).
+ * rz[c] = R_c.Z_c, rr[c] = R_c.R_c, delta[c] = (M Z_c).Z_c.  lzh_cg_scalars with the
+ * freeze test and est2 on rr and the coefficients from rz (gamma_prev keeps the last
+ * rz): beta = first ? 0 : rz / gamma_prev, den = delta - beta rz / alpha_prev, alpha =
+ * rz / den.  rz <= 0 or not finite on a live column that is not frozen by rr is status
+ * 2 like a bad den: the preconditioner is not positive on this residual. */
+int lzh_pcg_scalars(int b, int first, int max_iter, const double *rz, const double *rr, const double *delta,
+                    const double *thr, double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters,
+                    int *status, double *coef, int *nlive);
 /* ------------------------------------------- block conjugate gradients
  * The b x b rules of lz_bcg_solve (lz_hip.h), the very code its one-workgroup
  * kernels run (csrc/lz_bcg.hpp), on host arrays; every matrix b x b row-major fp64, 1
