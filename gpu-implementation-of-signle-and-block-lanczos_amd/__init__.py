@@ -1020,6 +1020,28 @@ class Handle:
                                       lo, hi, K, _ptr(X0), _ptr(work), _ptr(dots)), "lz_cheb_moments")
         return dots.view(-1, 2, b)
 
+    @staticmethod
+    def _cg_update_args(what: str, names: str, blocks, coef, dots_name: str, dots, k: int, dinv=None):
+        """cg_update's and pcg_update's checks: the blocks, coef, dinv when there is one, and the dots
+        (k b fp64, allocated when None), which it returns."""
+        torch = _torch()
+        like = blocks[0]
+        n, b = like.shape
+        for t in blocks:
+            if tuple(t.shape) != (n, b) or t.dtype != like.dtype or not t.is_contiguous():
+                raise LanczosError(f"{what}: {names} (n, b) contiguous (ld = b), of one dtype")
+        if coef.dtype != torch.float64 or not coef.is_contiguous() or coef.numel() != 2 * b:
+            raise LanczosError(f"{what}: coef is a contiguous fp64 tensor of 2 b elements")
+        if dinv is not None and (dinv.dim() != 1 or dinv.numel() != n or dinv.dtype != like.dtype
+                                 or not dinv.is_contiguous()):
+            raise LanczosError(f"{what}: dinv is a contiguous 1-D tensor of n elements of the blocks' dtype")
+        if dots is None:
+            dots = torch.empty(k * b, dtype=torch.float64, device=like.device)
+        if dots.dtype != torch.float64 or not dots.is_contiguous() or dots.numel() != k * b:
+            size = "2 b" if k == 2 else "b"
+            raise LanczosError(f"{what}: {dots_name} is a contiguous fp64 tensor of {size} elements")
+        return dots
+
     def cg_update(self, coef, R, W, P, S, X, rr=None):
         """The row-local half of one conjugate-gradient step with per-column device coefficients
         (lz_cg_update): P = R + beta P, S = W + beta S, X += alpha P, R -= alpha S, each element
@@ -1027,17 +1049,8 @@ class Handle:
         coef: 2 b fp64 on the device, [alpha(b) | beta(b)], read only, rounded once to the blocks'
         dtype; R, W (read only), P, S, X: (n, b) contiguous, of one dtype, pairwise distinct; a zero
         coefficient skips its product.  Returns rr (b fp64 on the device; allocated when None)."""
-        torch = _torch()
         n, b = R.shape
-        for t in (R, W, P, S, X):
-            if tuple(t.shape) != (n, b) or t.dtype != R.dtype or not t.is_contiguous():
-                raise LanczosError("cg_update: R, W, P, S, X (n, b) contiguous (ld = b), of one dtype")
-        if coef.dtype != torch.float64 or not coef.is_contiguous() or coef.numel() != 2 * b:
-            raise LanczosError("cg_update: coef is a contiguous fp64 tensor of 2 b elements")
-        if rr is None:
-            rr = torch.empty(b, dtype=torch.float64, device=R.device)
-        if rr.dtype != torch.float64 or not rr.is_contiguous() or rr.numel() != b:
-            raise LanczosError("cg_update: rr is a contiguous fp64 tensor of b elements")
+        rr = self._cg_update_args("cg_update", "R, W, P, S, X", (R, W, P, S, X), coef, "rr", rr, 1)
         _check(self.L.lz_cg_update(self.ptr, n, b, _dt(R), _ptr(coef), _ptr(R), _ptr(W), _ptr(P), _ptr(S), _ptr(X),
                                    _ptr(rr)), "lz_cg_update")
         return rr
@@ -1049,19 +1062,8 @@ class Handle:
         the blocks' dtype, read only; R, W (read only), P, S, X, Z: (n, b) contiguous, of one dtype, all
         seven pairwise distinct.  Returns dots (2 b fp64 on the device, [R.Z (b) | R.R (b)] of the
         stored values; allocated when None)."""
-        torch = _torch()
         n, b = R.shape
-        for t in (R, W, P, S, X, Z):
-            if tuple(t.shape) != (n, b) or t.dtype != R.dtype or not t.is_contiguous():
-                raise LanczosError("pcg_update: R, W, P, S, X, Z (n, b) contiguous (ld = b), of one dtype")
-        if coef.dtype != torch.float64 or not coef.is_contiguous() or coef.numel() != 2 * b:
-            raise LanczosError("pcg_update: coef is a contiguous fp64 tensor of 2 b elements")
-        if dinv.dim() != 1 or dinv.numel() != n or dinv.dtype != R.dtype or not dinv.is_contiguous():
-            raise LanczosError("pcg_update: dinv is a contiguous 1-D tensor of n elements of the blocks' dtype")
-        if dots is None:
-            dots = torch.empty(2 * b, dtype=torch.float64, device=R.device)
-        if dots.dtype != torch.float64 or not dots.is_contiguous() or dots.numel() != 2 * b:
-            raise LanczosError("pcg_update: dots is a contiguous fp64 tensor of 2 b elements")
+        dots = self._cg_update_args("pcg_update", "R, W, P, S, X, Z", (R, W, P, S, X, Z), coef, "dots", dots, 2, dinv)
         _check(self.L.lz_pcg_update(self.ptr, n, b, _dt(R), _ptr(coef), _ptr(dinv), _ptr(R), _ptr(W), _ptr(P),
                                     _ptr(S), _ptr(X), _ptr(Z), _ptr(dots)), "lz_pcg_update")
         return dots
@@ -1193,25 +1195,22 @@ class Handle:
         opts = CgOpts(tol, max_iter, 0 if check_every is None else int(check_every), int(max_restarts))
         iters, status = np.zeros(b, np.int32), np.zeros(b, np.int32)
         resid, est, info = np.zeros(b), np.zeros(b), np.zeros(3, np.int32)
+        args = (self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b, float(shift))
+        tail = (_ptr(B), _ptr(X), _ptr(work), ctypes.addressof(opts), _p(iters), _p(status), _p(resid), _p(est))
         if method == "block":
             info = np.zeros(5, np.int32)
-            _check(self.L.lz_bcg_solve(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
-                                       float(shift), _ptr(B), _ptr(X), _ptr(work), ctypes.addressof(opts), _p(iters),
-                                       _p(status), _p(resid), _p(est), _p(info)), "lz_bcg_solve")
-            return {"X": X, "iters": iters, "status": status, "converged": status == 0, "resid": resid, "est": est,
-                    "iterations": int(info[0]), "restarts": int(info[1]), "n_spmm": int(info[2]),
-                    "fallback": int(info[3]), "stop": int(info[4])}
-        if dinv is not None:
-            _check(self.L.lz_pcg_solve(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
-                                       float(shift), _ptr(dinv), _ptr(B), _ptr(X), _ptr(work), ctypes.addressof(opts),
-                                       _p(iters), _p(status), _p(resid), _p(est), _p(info)), "lz_pcg_solve")
-            return {"X": X, "iters": iters, "status": status, "converged": status == 0, "resid": resid, "est": est,
-                    "iterations": int(info[0]), "restarts": int(info[1]), "n_spmm": int(info[2]), "precond": kind}
-        _check(self.L.lz_cg_solve(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
-                                  float(shift), _ptr(B), _ptr(X), _ptr(work), ctypes.addressof(opts), _p(iters),
-                                  _p(status), _p(resid), _p(est), _p(info)), "lz_cg_solve")
-        return {"X": X, "iters": iters, "status": status, "converged": status == 0, "resid": resid, "est": est,
-                "iterations": int(info[0]), "restarts": int(info[1]), "n_spmm": int(info[2])}
+            _check(self.L.lz_bcg_solve(*args, *tail, _p(info)), "lz_bcg_solve")
+        elif dinv is not None:
+            _check(self.L.lz_pcg_solve(*args, _ptr(dinv), *tail, _p(info)), "lz_pcg_solve")
+        else:
+            _check(self.L.lz_cg_solve(*args, *tail, _p(info)), "lz_cg_solve")
+        out = {"X": X, "iters": iters, "status": status, "converged": status == 0, "resid": resid, "est": est,
+               "iterations": int(info[0]), "restarts": int(info[1]), "n_spmm": int(info[2])}
+        if method == "block":
+            out.update(fallback=int(info[3]), stop=int(info[4]))
+        elif dinv is not None:
+            out["precond"] = kind
+        return out
 
     @staticmethod
     def _work4(what: str, work, n: int, b: int, like, blocks: int = 4):

@@ -1635,6 +1635,16 @@ static int krylov_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp,
     });
 }
 
+// cg_solve as krylov_entry calls it, for lz_cg_solve (dinv NULL) and lz_pcg_solve: dinv goes in
+// behind shift, in the operator's dtype
+static auto cg_solve_with(const void *dinv)
+{
+    return [dinv](lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, auto *val, int b,
+                  double shift, auto... rest) {
+        return cg_solve(h, n, nnz, rp, col, val, b, shift, (decltype(val))dinv, rest...);
+    };
+}
+
 extern "C" {
 
 const char *lz_last_error(void) { return g_err; }
@@ -2178,7 +2188,7 @@ int lz_cg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *c
                  "R, W, P, S and X must be pairwise distinct");
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        return cg_update<T>(h, n, b, coef, (T *)R, (const T *)W, (T *)P, (T *)S, (T *)X, rr);
+        return cg_update<T>(h, n, b, coef, (T *)R, (const T *)W, (T *)P, (T *)S, (T *)X, nullptr, nullptr, rr);
     });
 }
 
@@ -2187,7 +2197,7 @@ int lz_cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const i
                 int *iters, int *status, double *resid, double *est, int *info)
 {
     return krylov_entry(h, n, nnz, rp, col, val, dtype, b, kMaxB, shift, B, X, work, opts, iters, status, resid, est, info,
-                        [](auto... a) { return cg_solve(a...); });
+                        cg_solve_with(nullptr));
 }
 
 int lz_pcg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *coef, const void *dinv, void *R,
@@ -2203,7 +2213,7 @@ int lz_pcg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *
                  "R, W, P, S, X, Z and dinv must be pairwise distinct");
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        return pcg_update<T>(h, n, b, coef, (const T *)dinv, (T *)R, (const T *)W, (T *)P, (T *)S, (T *)X, (T *)Z, dots);
+        return cg_update<T>(h, n, b, coef, (T *)R, (const T *)W, (T *)P, (T *)S, (T *)X, (const T *)dinv, (T *)Z, dots);
     });
 }
 
@@ -2230,14 +2240,8 @@ int lz_pcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const 
     LZ_HANDLE_CHECK(h);
     LZ_ARG_CHECK(dinv != nullptr, "dinv is NULL (lz_cg_solve is the solve without a preconditioner)");
     LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
-    return krylov_entry(
-        h, n, nnz, rp, col, val, dtype, b, kMaxB, shift, B, X, work, opts, iters, status, resid, est, info,
-        [dinv](lz_handle *hh, int64_t nn, int64_t nz, const int64_t *r, const int32_t *c, auto *v, int bb, double sh,
-               auto *Bt, auto *Xt, auto *wk, const lz_cg_opts &o, int *it, int *stt, double *rs, double *es, int *inf) {
-            using T = std::remove_cv_t<std::remove_pointer_t<decltype(Xt)>>;
-            return pcg_solve<T>(hh, nn, nz, r, c, v, bb, sh, (const T *)dinv, Bt, Xt, wk, o, it, stt, rs, es, inf);
-        },
-        kPcgWorkBlocks, span_of(dinv, std::max<int64_t>(n, 0), dtype));
+    return krylov_entry(h, n, nnz, rp, col, val, dtype, b, kMaxB, shift, B, X, work, opts, iters, status, resid, est, info,
+                        cg_solve_with(dinv), kPcgWorkBlocks, span_of(dinv, std::max<int64_t>(n, 0), dtype));
 }
 
 int lz_bcg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *xi, const double *E, const void *S,

@@ -1,6 +1,7 @@
 // lz_cg.hpp -- the per-column scalar rules of the batched conjugate gradients
-// (DESIGN.md 23), one definition for the device (k_cg_start, k_cg_scalars in
-// lz_cg.hip) and the host library (lzh_cg_start, lzh_cg_scalars in lz_host.cpp).
+// (DESIGN.md 23, 25), one definition for the device (k_cg_start, k_cg_scalars in
+// lz_cg.hip) and the host library (lzh_cg_start, lzh_cg_scalars, lzh_pcg_scalars in
+// lz_host.cpp).
 // Chronopoulos-Gear CG on M = A + shift I, column by column:
 //   gamma = r.r, delta = (M r).r, beta = gamma / gamma_prev,
 //   alpha = gamma / (delta - beta gamma / alpha_prev),
@@ -56,44 +57,17 @@ LZ_CG_HD inline void cg_start_rule(double gamma, double rec, double thr, int max
     }
 }
 
-// One iteration's scalars: gamma = r.r (the recurrence's), delta = (M r).r.
-// A live column whose gamma has reached thr, or whose iterations are spent, is
-// frozen here (est2 = gamma); a frozen column gets alpha = beta = 0 and its
-// state is not touched.  den <= 0 or not finite: status 2, frozen for good,
-// alpha = beta = 0, iters not advanced.
-LZ_CG_HD inline void cg_step_rule(double gamma, double delta, double thr, bool first, int max_iter, CgCol &s,
-                                  double &alpha, double &beta)
-{
-    alpha = 0.0;
-    beta = 0.0;
-    if (!s.live) return;
-    if (gamma <= thr || s.iters >= max_iter) {
-        s.live = 0;
-        s.est2 = gamma;
-        return;
-    }
-    const double bt = first ? 0.0 : gamma / s.gamma_prev;
-    const double den = first ? delta : delta - bt * gamma / s.alpha_prev;
-    if (!(den > 0.0) || !std::isfinite(den)) {
-        s.live = 0;
-        s.status = kCgNotPd;
-        s.est2 = gamma;
-        return;
-    }
-    alpha = gamma / den;
-    beta = bt;
-    s.gamma_prev = gamma;
-    s.alpha_prev = alpha;
-    s.iters += 1;
-}
-
-// The same step with a diagonal preconditioner: z = D^-1 r, rz = r.z,
-// rr = r.r, delta = (M z).z.  The freeze test and est2 are on rr, the true residual
-// norm; the coefficients come from rz (beta = rz / rz_prev, kept in gamma_prev).  One
-// more breakdown: rz <= 0 or not finite on a live column -- the preconditioner is not
-// positive on this residual -- is status 2 like a bad denominator.
-LZ_CG_HD inline void pcg_step_rule(double rz, double rr, double delta, double thr, bool first, int max_iter, CgCol &s,
-                                   double &alpha, double &beta)
+// One iteration's scalars: rr = r.r (the recurrence's), delta = (M r).r; rz is rr again.
+// A live column whose rr has reached thr, or whose iterations are spent, is frozen here
+// (est2 = rr); a frozen column gets alpha = beta = 0 and its state is not touched.
+// den <= 0 or not finite: status 2, frozen for good, alpha = beta = 0, iters not advanced.
+// pre: the same step with a diagonal preconditioner: z = D^-1 r, rz = r.z,
+// delta = (M z).z.  The freeze test and est2 stay on rr, the true residual norm; the
+// coefficients come from rz (beta = rz / rz_prev, kept in gamma_prev).  One more
+// breakdown, tested only here: rz <= 0 or not finite on a live column -- the
+// preconditioner is not positive on this residual -- is status 2 like a bad denominator.
+LZ_CG_HD inline void cg_step_rule(bool pre, double rz, double rr, double delta, double thr, bool first, int max_iter,
+                                  CgCol &s, double &alpha, double &beta)
 {
     alpha = 0.0;
     beta = 0.0;
@@ -105,7 +79,8 @@ LZ_CG_HD inline void pcg_step_rule(double rz, double rr, double delta, double th
     }
     const double bt = first ? 0.0 : rz / s.gamma_prev;
     const double den = first ? delta : delta - bt * rz / s.alpha_prev;
-    if (!(rz > 0.0) || !std::isfinite(rz) || !(den > 0.0) || !std::isfinite(den)) {
+    const bool rz_bad = pre && (!(rz > 0.0) || !std::isfinite(rz));
+    if (rz_bad || !(den > 0.0) || !std::isfinite(den)) {
         s.live = 0;
         s.status = kCgNotPd;
         s.est2 = rr;

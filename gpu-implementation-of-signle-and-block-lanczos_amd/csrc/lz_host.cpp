@@ -681,7 +681,7 @@ int lzh_cg_scalars(int b, int first, int max_iter, const double *gamma, const do
     *nlive = 0;
     for (int c = 0; c < b; ++c) {
         lz::CgCol s{gamma_prev[c], alpha_prev[c], est2[c], live[c], iters[c], status[c]};
-        lz::cg_step_rule(gamma[c], delta[c], thr[c], first != 0, max_iter, s, coef[c], coef[b + c]);
+        lz::cg_step_rule(false, gamma[c], gamma[c], delta[c], thr[c], first != 0, max_iter, s, coef[c], coef[b + c]);
         gamma_prev[c] = s.gamma_prev, alpha_prev[c] = s.alpha_prev, est2[c] = s.est2;
         live[c] = s.live, iters[c] = s.iters, status[c] = s.status;
         *nlive += s.live;
@@ -689,7 +689,7 @@ int lzh_cg_scalars(int b, int first, int max_iter, const double *gamma, const do
     return 0;
 }
 
-// the preconditioned step rule, as k_pcg_scalars applies it
+// the step rule with a preconditioner, as k_cg_scalars then applies it
 int lzh_pcg_scalars(int b, int first, int max_iter, const double *rz, const double *rr, const double *delta,
                     const double *thr, double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters,
                     int *status, double *coef, int *nlive)
@@ -700,7 +700,7 @@ int lzh_pcg_scalars(int b, int first, int max_iter, const double *rz, const doub
     *nlive = 0;
     for (int c = 0; c < b; ++c) {
         lz::CgCol s{gamma_prev[c], alpha_prev[c], est2[c], live[c], iters[c], status[c]};
-        lz::pcg_step_rule(rz[c], rr[c], delta[c], thr[c], first != 0, max_iter, s, coef[c], coef[b + c]);
+        lz::cg_step_rule(true, rz[c], rr[c], delta[c], thr[c], first != 0, max_iter, s, coef[c], coef[b + c]);
         gamma_prev[c] = s.gamma_prev, alpha_prev[c] = s.alpha_prev, est2[c] = s.est2;
         live[c] = s.live, iters[c] = s.iters, status[c] = s.status;
         *nlive += s.live;

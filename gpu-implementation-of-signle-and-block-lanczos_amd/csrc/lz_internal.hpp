@@ -50,38 +50,29 @@ int dots_fold(lz_handle *h, int64_t P, int b, double *dots, bool zero_cross = fa
 // the same fold for P slabs of bb <= 128 doubles (the partials behind them at h->dots_ws + P bb)
 int slabs_fold(lz_handle *h, int64_t P, int bb, double *out, int zero_from = -1);
 
-// ---- batched conjugate gradients (lz_cg.hip)
+// ---- batched conjugate gradients, with or without a diagonal preconditioner (lz_cg.hip,
+// DESIGN.md 23, 25)
 // k_cg_update: kCgThreads threads per block; the 128-byte-row form (b = 16 fp64, b = 32
 // fp32) covers kCgRows128 rows per block pass, the generic form kCgThreads / b; at most
-// kCgGridCap blocks, one slab of b doubles each, then grid-stride.  kCgCheckEvery: the
-// iterations lz_cg_solve enqueues between two reads of the live count by default.
+// kCgGridCap blocks, one slab each (b doubles, 2 b with a preconditioner), then grid-stride.
+// kCgCheckEvery: the iterations the solve enqueues between two reads of the live count by
+// default.  k_csr_jacobi: kJacobiLanes lanes per row, kJacobiRows rows per workgroup pass.
+// The solve's work: 4 blocks, [R | W | P | S]; kPcgWorkBlocks with a preconditioner, Z behind them.
 constexpr int kCgThreads = 256, kCgRows128 = 32, kCgGridCap = 2048, kCgCheckEvery = 8;
-// lz_cg_update (include/lz_hip.h)
-template <typename T>
-int cg_update(lz_handle *h, int64_t n, int b, const double *coef, T *R, const T *W, T *P, T *S, T *X, double *rr);
-// lz_cg_solve (include/lz_hip.h)
-template <typename T>
-int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
-             double shift, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status, double *resid,
-             double *est, int *info);
-// ---- diagonally preconditioned conjugate gradients (lz_cg.hip)
-// k_pcg_update: k_cg_update's two forms and constants, one slab of 2 b doubles per block.
-// k_csr_jacobi: kJacobiLanes lanes per row, kJacobiRows rows per workgroup pass.
-// lz_pcg_solve's work: kPcgWorkBlocks blocks, [R | W | P | S | Z].
 constexpr int kJacobiLanes = 8, kJacobiRows = kCgThreads / kJacobiLanes, kPcgWorkBlocks = 5;
-// lz_pcg_update (include/lz_hip.h)
+// lz_cg_update (dinv = Z = NULL, dots: b) and lz_pcg_update (dots: 2 b) (include/lz_hip.h)
 template <typename T>
-int pcg_update(lz_handle *h, int64_t n, int b, const double *coef, const T *dinv, T *R, const T *W, T *P, T *S, T *X,
-               T *Z, double *dots);
+int cg_update(lz_handle *h, int64_t n, int b, const double *coef, T *R, const T *W, T *P, T *S, T *X, const T *dinv,
+              T *Z, double *dots);
 // lz_csr_jacobi (include/lz_hip.h); synchronises the stream once (the count)
 template <typename T>
 int csr_jacobi(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, const T *val, double shift, T *dinv,
                int64_t *n_bad);
-// lz_pcg_solve (include/lz_hip.h)
+// lz_cg_solve (dinv = NULL) and lz_pcg_solve (include/lz_hip.h)
 template <typename T>
-int pcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
-              double shift, const T *dinv, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status,
-              double *resid, double *est, int *info);
+int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+             double shift, const T *dinv, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status,
+             double *resid, double *est, int *info);
 // ---- block conjugate gradients (lz_bcg.hip)
 // k_bcg_update / k_bcg_direction: kBcgThreads threads per block; the b = 16 fp64 MFMA
 // form covers kBcgRows16 rows per block pass (one 16-row tile per wave), the b = 32 fp32

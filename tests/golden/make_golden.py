@@ -7,6 +7,7 @@ against an independent numpy restatement before anything is written.
 
     python tests/golden/make_golden.py            (both files)
     python tests/golden/make_golden.py ref_host   (golden_ref_host.npz only)
+    python tests/golden/make_golden.py cg_rules   (golden_cg_rules.npz only; see cg_rules)
 """
 import os
 import sys
@@ -150,8 +151,23 @@ def ref_host():
     print("wrote", os.path.join(HERE, "golden_ref_host.npz"), len(out), "arrays")
 
 
+def cg_rules():
+    """golden_cg_rules.npz: what lzh_cg_start, lzh_cg_scalars and lzh_pcg_scalars of the built
+    liblz_host.so return on test_cg_host.rule_grid() (special values of every dot).  Recorded from
+    the commit before csrc/lz_cg.hpp's two step rules became one body; regenerate it only from a
+    library whose rules are meant to be the new truth."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import __graft_entry__ as ge
+    from test_cg_host import rule_outputs
+    out = rule_outputs(ge.load_package())
+    np.savez_compressed(os.path.join(HERE, "golden_cg_rules.npz"), **out)
+    print("wrote", os.path.join(HERE, "golden_cg_rules.npz"), len(out), "arrays")
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["ref_host"]:  # only golden_ref_host.npz
+    if sys.argv[1:] == ["cg_rules"]:  # only golden_cg_rules.npz (needs no reference tree)
+        cg_rules()
+    elif sys.argv[1:] == ["ref_host"]:  # only golden_ref_host.npz
         assert oracle.ref_available(4), "build oracle/_ref first (make -C oracle)"
         ref_host()
     else:

@@ -190,6 +190,82 @@ def test_iterations_spent(lz):
     assert st.start(lz, np.array([4.0]), np.array([1e-20]), 2, False) == 0 and st.status[0] == SPENT
 
 
+# ------------------------------------------------------------ the rules on special values
+RULE_VALS = (0.0, 5e-324, 1.0, 1e308, np.inf, -1.0, np.nan)
+RULE_PREV = (1.0, 0.0, np.inf)
+RULE_MAX_ITER = 5
+RULE_FIELDS = ("gamma_prev", "alpha_prev", "est2", "live", "iters", "status", "coef", "nlive")
+
+
+def rule_grid():
+    """One row per combination of gamma (the preconditioned rule's rz, the start rule's measured
+    value), rr (the start rule's rec), delta, thr in {1e-20, 0}, live, iterations spent or not,
+    gamma_prev and alpha_prev; the start rule, which reads no delta, takes its status from delta's
+    index (0, 1, 2 in turn)."""
+    k = np.arange(len(RULE_VALS))
+    ax = np.meshgrid(k, k, k, (1e-20, 0.0), (0, 1), (0, 1), RULE_PREV, RULE_PREV, indexing="ij")
+    gi, ri, di, thr, live, spent, gp, ap = (a.ravel() for a in ax)
+    v = np.array(RULE_VALS)
+    return {"gamma": v[gi.astype(int)], "rr": v[ri.astype(int)], "delta": v[di.astype(int)], "thr": thr,
+            "live": live.astype(np.int32), "iters": np.where(spent == 1, RULE_MAX_ITER, 2).astype(np.int32),
+            "status": (di.astype(int) % 3).astype(np.int32), "gamma_prev": gp, "alpha_prev": ap}
+
+
+def rule_outputs(lz):
+    """lzh_cg_start, lzh_cg_scalars and lzh_pcg_scalars on rule_grid(), first / initial 0 and 1:
+    {"<rule><first>_<field>": array}, the whole state, coef and the live count after the call."""
+    import ctypes
+    g = rule_grid()
+    n = g["gamma"].size
+    out = {}
+    for rule in ("start", "cg", "pcg"):
+        for first in (0, 1):
+            st = Cols(n)
+            st.gamma_prev[:], st.alpha_prev[:], st.est2[:] = g["gamma_prev"], g["alpha_prev"], 7.0
+            st.live[:], st.iters[:], st.status[:] = g["live"], g["iters"], g["status"] if rule == "start" else SPENT
+            st.coef[:] = 7.0
+            if rule == "start":
+                nl = st.start(lz, g["gamma"], g["thr"], RULE_MAX_ITER, first, rec=g["rr"])
+            elif rule == "cg":
+                nl = st.step(lz, g["gamma"], g["delta"], g["thr"], first, RULE_MAX_ITER)
+            else:
+                c = ctypes.c_int(-1)
+                rc = lz.host_lib().lzh_pcg_scalars(n, first, RULE_MAX_ITER, lz._p(g["gamma"]), lz._p(g["rr"]),
+                                                   lz._p(g["delta"]), lz._p(g["thr"]), *st._state(lz), lz._p(st.coef),
+                                                   ctypes.addressof(c))
+                assert rc == 0
+                nl = c.value
+            st.nlive = np.array([nl], np.int32)
+            for f in RULE_FIELDS:
+                out[f"{rule}{first}_{f}"] = getattr(st, f)
+    return out
+
+
+def test_rules_on_special_values(lz):
+    """Both step rules and the start rule on zeros, a denormal, huge, infinite, negative and NaN
+    dots: every output equals what the library gave before the two step rules became one body
+    (tests/golden/golden_cg_rules.npz, make_golden.py cg_rules), bit for bit, a NaN matching any
+    NaN.  Among the rows: a plain column with gamma = inf on a first step with a finite positive
+    delta stays live with alpha = inf; the preconditioned rule gives it status 2."""
+    import os
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_cg_rules.npz"))
+    got = rule_outputs(lz)
+    assert sorted(want.files) == sorted(got)
+    for key in want.files:
+        w, g = want[key], got[key]
+        assert w.dtype == g.dtype and w.shape == g.shape, key
+        if w.dtype == F64:
+            same = (w.view(np.uint64) == g.view(np.uint64)) | (np.isnan(w) & np.isnan(g))
+        else:
+            same = w == g
+        assert same.all(), f"{key}: {np.flatnonzero(~same)[:8]}"
+    g = rule_grid()
+    row = np.flatnonzero(np.isposinf(g["gamma"]) & (g["rr"] == 1.0) & (g["delta"] == 1.0) & (g["live"] == 1)
+                         & (g["iters"] == 2) & (g["thr"] == 0.0))[0]
+    assert got["cg1_live"][row] == 1 and np.isposinf(got["cg1_coef"][row]) and got["cg1_status"][row] == SPENT
+    assert got["pcg1_live"][row] == 0 and got["pcg1_status"][row] == NOT_PD and got["pcg1_coef"][row] == 0.0
+
+
 # ------------------------------------------------------------ the restated loop
 @pytest.fixture(scope="module")
 def lap(lz):

@@ -1,5 +1,5 @@
 """Diagonally preconditioned conjugate gradients on the device: lz_pcg_update (both forms of
-k_pcg_update), lz_csr_jacobi and Handle.solve(precond=...) (lz_pcg_solve).
+k_cg_update with PRE), lz_csr_jacobi and Handle.solve(precond=...) (lz_pcg_solve).
 
 pcg_update: test_gpu_cg's forward bounds with z0 = dv r in P's expression, extended to Z (3 eps of
 dv r' plus dv times R's bound); both dots against the device's own R and Z.  jacobi: the fp64

@@ -1,7 +1,7 @@
 """Diagonally preconditioned conjugate gradients without a GPU: the step rule (lzh_pcg_scalars: the
-code k_pcg_scalars runs, csrc/lz_cg.hpp), the operators Jacobi is for, and a NumPy restatement of
-lz_pcg_solve's loop on the exported rules, `pcg_restated`, the GPU tests' yardstick for iteration
-counts."""
+code k_cg_scalars runs with a preconditioner, csrc/lz_cg.hpp), the operators Jacobi is for, and a
+NumPy restatement of lz_pcg_solve's loop on the exported rules, `pcg_restated`, the GPU tests'
+yardstick for iteration counts."""
 import ctypes
 
 import numpy as np
