@@ -93,13 +93,11 @@ struct lz_handle {
     // (one row-local pass per solve); lz_set_final_state(h, 0) skips that pass
     int final_state = 1;
     int dbg_setup_fail = 0;       // lz_debug_fail_next_setup: the next distributed set-up's forced status
-    // fixed-nnz SpMM format (experiment, lz_spmm.hip fnz_prepare): the operator's
-    // columns with row-end flags and each tile's first row, keyed by the operator
     void *c16buf = nullptr;       // pass 1's 16-bit columns (col16_plan), nnz int16
     size_t c16_cap = 0;           // bytes
+    // fixed-nnz SpMM format (experiment, lz_spmm.hip fnz_prepare): the operator's
+    // columns with row-end flags and each tile's first row, rebuilt by every call
     int32_t *fnz_colf = nullptr, *fnz_trow = nullptr;
-    int64_t fnz_key[4] = {0, 0, 0, 0};
-    bool fnz_ok = false;
     // wavefront step (lz_wf.hip): per-tile dependency ranges (int2) and
     // pass-2 tile flags, T + 64 entries each
     void *wf_deps = nullptr;

@@ -1417,9 +1417,13 @@ __global__ __launch_bounds__(256) void k_spmm_fnz(int64_t nnz, const int32_t *__
     }
 }
 
-// Build (or reuse) the fixed-nnz format of an operator (cached on the handle
-// by its pointers and sizes; experiment: a caller changing the arrays in
-// place behind the same pointers would see stale flags).  false: the operator
+// Build the fixed-nnz format of the operator this call was given: every call
+// derives colf and trow anew from rp and col (an experiment, off by default,
+// pays a synchronisation and two allocations per SpMM for it).  Nothing is
+// kept by address: two operators of equal n and nnz can sit behind the same
+// pointers (arrays overwritten in place, or an allocator handing a freed
+// operator's blocks to the next), and a format reused by pointers and sizes
+// multiplied the second with the first one's columns.  false: the operator
 // has a shape the kernel does not cover (empty rows, rows past S + 1 entries,
 // more than RMAX rows in a tile).
 static int fnz_prepare(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, bool *ok)
@@ -1427,17 +1431,11 @@ static int fnz_prepare(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, 
     *ok = false;
     const int64_t ntiles = ceil_div(nnz, (int64_t)kFnzK);
     if (nnz <= 0 || n >= (1LL << 31) || ntiles + 1 >= (1LL << 31)) return LZ_OK;
-    if (h->fnz_key[0] == (int64_t)(uintptr_t)rp && h->fnz_key[1] == (int64_t)(uintptr_t)col && h->fnz_key[2] == n &&
-        h->fnz_key[3] == nnz) {
-        *ok = h->fnz_ok;
-        return LZ_OK;
-    }
     LZ_HIP_TRY(hipStreamSynchronize(h->stream));
     (void)hipFree(h->fnz_colf);
     (void)hipFree(h->fnz_trow);
     h->fnz_colf = nullptr;
     h->fnz_trow = nullptr;
-    h->fnz_key[0] = 0;
     LZ_HIP_TRY(hipMalloc(&h->fnz_colf, sizeof(int32_t) * (size_t)nnz));
     LZ_HIP_TRY(hipMalloc(&h->fnz_trow, sizeof(int32_t) * (size_t)(ntiles + 1)));
     int *stats = flag_word(h, kFlagPlanStats);  // [0] max row length, [1] empty / negative, [2] max rows per tile
@@ -1450,12 +1448,7 @@ static int fnz_prepare(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, 
     int st[3] = {0, 0, 0};
     LZ_HIP_TRY(hipMemcpyAsync(st, stats, sizeof(st), hipMemcpyDeviceToHost, h->stream));
     LZ_HIP_TRY(hipStreamSynchronize(h->stream));
-    h->fnz_ok = st[1] == 0 && st[0] <= kFnzS + 1 && st[2] <= kFnzRmax;
-    h->fnz_key[0] = (int64_t)(uintptr_t)rp;
-    h->fnz_key[1] = (int64_t)(uintptr_t)col;
-    h->fnz_key[2] = n;
-    h->fnz_key[3] = nnz;
-    *ok = h->fnz_ok;
+    *ok = st[1] == 0 && st[0] <= kFnzS + 1 && st[2] <= kFnzRmax;
     return LZ_OK;
 }
 

@@ -551,15 +551,21 @@ def test_block_large_properties(lz, orc, handle, torch_cuda):
 
 
 def test_block_b16_long_runs(lz, orc, handle, torch_cuda):
-    """Fused pass with 128-row tiles whose CSR run exceeds the LDS staging
-    buffer (power-law rows up to 5000 nnz): chunked staging path, fp64."""
+    """The wavefront step on tiles whose CSR run exceeds its LDS stage (power-law
+    rows up to 5000 nnz, fp64).  At 11.9 entries per row the wide shape runs
+    this operator: 160-row tiles and a 4400-entry stage, which the largest
+    tile's run (5292 entries) overflows, so that tile takes the global-gather
+    path.  No update-pass launch: the wavefront step ran, not the two-pass one."""
     A = lz.gen_powerlaw(30011, 12.0, 1.8, 5000, seed=13, dtype=np.float64)
+    assert 10.2 * A.n < A.nnz <= 27.0 * A.n, "the wide wavefront shape's row density"
     rp = np.asarray(A.row_ptr)
-    tile_runs = rp[np.minimum(np.arange(0, A.n + 128, 128), A.n)]
-    assert np.diff(tile_runs).max() > 2048, "test operator must overflow the staging buffer"
+    tile_runs = rp[np.minimum(np.arange(0, A.n + 160, 160), A.n)]
+    assert np.diff(tile_runs).max() > 4400, "test operator must overflow the wide shape's stage"
     B = lz.uniform_B(A.n, 16, seed=14)
     m, lc = 6, 4321
-    got = gpu_block(lz, handle, torch_cuda, A, B, m, lc)
+    got, upd = _update_launches(lz, handle, torch_cuda, lz.CsrDevice.from_host(A), torch_cuda.from_numpy(B).cuda(),
+                                m, lc)
+    assert upd == 0, "the wavefront step has no update pass"
     assert_close_run(lz, m, 16, got, orc.block_lanczos(A, B, m, lc))
     # the persistent pass-1 kernels' bounded spins never timed out
     assert handle.device_error() == 0
