@@ -61,6 +61,9 @@ CG_MET, CG_SPENT, CG_NOT_PD = 0, 1, 2  # Handle.solve's status per column
 # lz_pcg_solve's work is PCG_WORK_BLOCKS blocks of n b elements; lz_csr_jacobi (csrc/lz_internal.hpp
 # kJacobi*) gives a row JACOBI_LANES lanes, a workgroup pass JACOBI_ROWS rows
 PCG_WORK_BLOCKS, JACOBI_LANES, JACOBI_ROWS = 5, 8, 32
+# lz_minres_solve's work is MINRES_WORK_BLOCKS blocks of n b elements (csrc/lz_internal.hpp kMinresWorkBlocks);
+# lz_minres_update's coef has MINRES_COEFS rows of b; MINRES_BREAKDOWN: its status 2 (LZ_MINRES_BREAKDOWN)
+MINRES_WORK_BLOCKS, MINRES_COEFS, MINRES_BREAKDOWN = 5, 7, 2
 # lz_bcg_update / lz_bcg_direction (csrc/lz_internal.hpp kBcg*): BCG_THREADS threads per block; the b = 16
 # fp64 MFMA form covers BCG_ROWS_16 rows per block pass (16-row tiles), the b = 32 fp32 one BCG_ROWS_32
 # (32-row tiles), the generic form BCG_ROWS_GEN; at
@@ -147,6 +150,10 @@ HIP_SYMBOLS = [
     ("lz_bcg_direction", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_bcg_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp,
                               _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lz_minres_update", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                  _c_vp]),
+    ("lz_minres_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp,
+                                 _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_block_lanczos_reorth_cheb", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int,
                                               _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int,
                                               _c_vp, _c_vp]),
@@ -229,6 +236,8 @@ HOST_SYMBOLS = [
                                 _c_vp, _c_vp]),
     ("lzh_pcg_scalars", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                  _c_vp, _c_vp, _c_vp]),
+    ("lzh_minres_start", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lzh_minres_scalars", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_bcg_start", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_bcg_start_finish", _c_int, [_c_int, _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_bcg_mid", _c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -1119,6 +1128,29 @@ class Handle:
         _check(self.L.lz_bcg_direction(self.ptr, n, b, _dt(Q), _ptr(z), _ptr(zinv), _ptr(Q), _ptr(S)),
                "lz_bcg_direction")
 
+    def minres_update(self, coef, W, U, Uo, D1, D2, X, uu=None):
+        """The row-local half of one MINRES pass with per-column device coefficients (lz_minres_update):
+        u' = a_w W + a_u U + a_o Uo, d' = g_o Uo + g_1 D1 + g_2 D2, X += tau d', each element finished as
+        a product and fmas in that order, u' stored into Uo and d' into D2, and uu[c] = the column sums
+        of the stored u' * u' in fp64.  coef: 7 b fp64 on the device, [a_w | a_u | a_o | g_o | g_1 | g_2 |
+        tau] of b entries each, read only, rounded once to the blocks' dtype; W, U, D1 (read only), Uo,
+        D2, X: (n, b) contiguous, of one dtype, pairwise distinct; a zero coefficient skips its term
+        whatever its operand holds.  Returns uu (b fp64 on the device; allocated when None)."""
+        torch = _torch()
+        n, b = W.shape
+        for t in (W, U, Uo, D1, D2, X):
+            if tuple(t.shape) != (n, b) or t.dtype != W.dtype or not t.is_contiguous():
+                raise LanczosError("minres_update: W, U, Uo, D1, D2, X (n, b) contiguous (ld = b), of one dtype")
+        if coef.dtype != torch.float64 or not coef.is_contiguous() or coef.numel() != MINRES_COEFS * b:
+            raise LanczosError("minres_update: coef is a contiguous fp64 tensor of 7 b elements")
+        if uu is None:
+            uu = torch.empty(b, dtype=torch.float64, device=W.device)
+        if uu.dtype != torch.float64 or not uu.is_contiguous() or uu.numel() != b:
+            raise LanczosError("minres_update: uu is a contiguous fp64 tensor of b elements")
+        _check(self.L.lz_minres_update(self.ptr, n, b, _dt(W), _ptr(coef), _ptr(W), _ptr(U), _ptr(Uo), _ptr(D1),
+                                       _ptr(D2), _ptr(X), _ptr(uu)), "lz_minres_update")
+        return uu
+
     def solve(self, A: CsrDevice, B, shift: float = 0.0, tol: Optional[float] = None, max_iter: Optional[int] = None,
               X0=None, check_every: Optional[int] = None, max_restarts: int = 3, work=None,
               method: str = "columns", precond=None):
@@ -1157,6 +1189,19 @@ class Handle:
         with a near-constant diagonal -- Jacobi gains nothing: the same iterations, each a little
         slower.  work is then 5 n b elements (PCG_WORK_BLOCKS), and the device holds 7 blocks and dinv.
 
+        method="minres" (lz_minres_solve, b <= 64): MINRES, for a symmetric A + shift I that may be
+        indefinite (a Helmholtz-type operator, a saddle-point block, A - sigma I at a sigma inside the
+        spectrum); the columns in lock step, each by its own scalars, as method="columns".  Same
+        arguments and defaults; no preconditioner (a MINRES preconditioner must be positive definite,
+        and Jacobi of an indefinite operator is not): precond raises.  The solution runs one pass
+        behind the Lanczos step, so a column that takes k steps runs k + 1 passes; iterations counts
+        the passes and n_spmm = iterations + 2 + restarts.  work is 5 n b elements
+        (MINRES_WORK_BLOCKS), and the device holds 7 blocks.  est is the recurrence's last |phibar| /
+        |B_c|, which never grows within a phase.  Status 2 (MINRES_BREAKDOWN) is a breakdown: a scalar
+        that is not finite (a NaN in B_c) or gamma = 0 (A + shift I singular on this Krylov space),
+        X_c untouched from then on.  The iterations grow as sigma nears an eigenvalue; a singular
+        inconsistent system ends with status 1 or 2.  The dict carries method: "minres".
+
         Returns a dict: X; iters, status (0 met tol on the measured residual, 1 iterations or
         restarts spent, 2 not positive definite), converged (status == 0), resid (measured), est
         (the recurrence's last value) -- NumPy arrays of b entries; restarts, n_spmm, iterations;
@@ -1164,10 +1209,10 @@ class Handle:
         it always was, so out.get("precond") is None); with method="block" also fallback (0 / 1)
         and stop (BCG_* reason of the last stop)."""
         torch = _torch()
-        if method not in ("columns", "block"):
-            raise LanczosError('solve: method is "columns" or "block"')
-        if precond is not None and method == "block":
-            raise LanczosError('solve: method="block" takes no preconditioner')
+        if method not in ("columns", "block", "minres"):
+            raise LanczosError('solve: method is "columns", "block" or "minres"')
+        if precond is not None and method != "columns":
+            raise LanczosError(f'solve: method="{method}" takes no preconditioner')
         n, b = self._blocks("solve", A, B)
         dinv, kind = None, None
         if isinstance(precond, str):
@@ -1189,7 +1234,8 @@ class Handle:
         else:
             self._blocks("solve", A, B, X0)
             X = X0.clone()
-        work = self._work4("solve", work, n, b, B, 4 if dinv is None else PCG_WORK_BLOCKS)
+        blocks = MINRES_WORK_BLOCKS if method == "minres" else 4 if dinv is None else PCG_WORK_BLOCKS
+        work = self._work4("solve", work, n, b, B, blocks)
         if check_every is not None and check_every < 1:
             raise LanczosError("solve: check_every >= 1")
         opts = CgOpts(tol, max_iter, 0 if check_every is None else int(check_every), int(max_restarts))
@@ -1200,6 +1246,8 @@ class Handle:
         if method == "block":
             info = np.zeros(5, np.int32)
             _check(self.L.lz_bcg_solve(*args, *tail, _p(info)), "lz_bcg_solve")
+        elif method == "minres":
+            _check(self.L.lz_minres_solve(*args, *tail, _p(info)), "lz_minres_solve")
         elif dinv is not None:
             _check(self.L.lz_pcg_solve(*args, _ptr(dinv), *tail, _p(info)), "lz_pcg_solve")
         else:
@@ -1208,6 +1256,8 @@ class Handle:
                "iterations": int(info[0]), "restarts": int(info[1]), "n_spmm": int(info[2])}
         if method == "block":
             out.update(fallback=int(info[3]), stop=int(info[4]))
+        elif method == "minres":
+            out["method"] = "minres"
         elif dinv is not None:
             out["precond"] = kind
         return out

@@ -2280,6 +2280,30 @@ int lz_bcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const 
                         info, [](auto... a) { return bcg_solve(a...); });
 }
 
+int lz_minres_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *coef, const void *W, const void *U,
+                     void *Uo, const void *D1, void *D2, void *X, double *uu)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
+    LZ_ARG_CHECK(coef && W && U && Uo && D1 && D2 && X && uu, "coef/W/U/Uo/D1/D2/X/uu NULL");
+    const int64_t nb = n * b;
+    LZ_ARG_CHECK(pairwise_apart({span_of(W, nb, dtype), span_of(U, nb, dtype), span_of(Uo, nb, dtype),
+                                 span_of(D1, nb, dtype), span_of(D2, nb, dtype), span_of(X, nb, dtype)}),
+                 "W, U, Uo, D1, D2 and X must be pairwise distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return minres_update<T>(h, n, b, coef, (const T *)W, (const T *)U, (T *)Uo, (const T *)D1, (T *)D2, (T *)X, uu);
+    });
+}
+
+int lz_minres_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                    lz_dtype dtype, int b, double shift, const void *B, void *X, void *work, const lz_cg_opts *opts,
+                    int *iters, int *status, double *resid, double *est, int *info)
+{
+    return krylov_entry(h, n, nnz, rp, col, val, dtype, b, kMaxB, shift, B, X, work, opts, iters, status, resid, est, info,
+                        [](auto... a) { return minres_solve(a...); }, kMinresWorkBlocks);
+}
+
 // The eight kept-basis entry points.  r == 0 with B (sigma NULL) is a first cycle, lz_block_lanczos_reorth
 // and its forms; anything else is a resumed one, lz_block_lanczos_reorth_resume and its forms, which
 // needs 1 <= r < m and sigma (its B is NULL).

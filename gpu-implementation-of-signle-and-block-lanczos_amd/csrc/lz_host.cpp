@@ -6,6 +6,7 @@
 
 #include "lz_bcg.hpp"
 #include "lz_cg.hpp"
+#include "lz_minres.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -703,6 +704,51 @@ int lzh_pcg_scalars(int b, int first, int max_iter, const double *rz, const doub
         lz::cg_step_rule(true, rz[c], rr[c], delta[c], thr[c], first != 0, max_iter, s, coef[c], coef[b + c]);
         gamma_prev[c] = s.gamma_prev, alpha_prev[c] = s.alpha_prev, est2[c] = s.est2;
         live[c] = s.live, iters[c] = s.iters, status[c] = s.status;
+        *nlive += s.live;
+    }
+    return 0;
+}
+
+// ---- batched MINRES: the per-column rules of lz_minres.hpp, as k_minres_start and
+// k_minres_scalars apply them, on host arrays: state = 8 rows of b doubles [beta_prev |
+// alpha_prev | c1 | s1 | c2 | s2 | phibar | est2], ctl = 4 rows of b ints [live | iters |
+// status | pass]
+static lz::MinresCol minres_load(int b, int c, const double *st, const int *ctl)
+{
+    return {st[c], st[b + c], st[2 * b + c], st[3 * b + c], st[4 * b + c], st[5 * b + c], st[6 * b + c], st[7 * b + c],
+            ctl[c], ctl[b + c], ctl[2 * b + c], ctl[3 * b + c]};
+}
+
+static void minres_store(int b, int c, const lz::MinresCol &s, double *st, int *ctl)
+{
+    st[c] = s.beta_prev, st[b + c] = s.alpha_prev, st[2 * b + c] = s.c1, st[3 * b + c] = s.s1;
+    st[4 * b + c] = s.c2, st[5 * b + c] = s.s2, st[6 * b + c] = s.phibar, st[7 * b + c] = s.est2;
+    ctl[c] = s.live, ctl[b + c] = s.iters, ctl[2 * b + c] = s.status, ctl[3 * b + c] = s.pass;
+}
+
+int lzh_minres_start(int b, int max_iter, int initial, const double *uu, const double *thr, double *state, int *ctl,
+                     int *nlive)
+{
+    if (b < 1 || !uu || !thr || !state || !ctl || !nlive) return -1;
+    *nlive = 0;
+    for (int c = 0; c < b; ++c) {
+        lz::MinresCol s = minres_load(b, c, state, ctl);
+        lz::minres_start_rule(uu[c], thr[c], max_iter, initial != 0, s);
+        minres_store(b, c, s, state, ctl);
+        *nlive += s.live;
+    }
+    return 0;
+}
+
+int lzh_minres_scalars(int b, int max_iter, const double *uu, const double *wu, const double *thr, double *state,
+                       int *ctl, double *coef, int *nlive)
+{
+    if (b < 1 || !uu || !wu || !thr || !state || !ctl || !coef || !nlive) return -1;
+    *nlive = 0;
+    for (int c = 0; c < b; ++c) {
+        lz::MinresCol s = minres_load(b, c, state, ctl);
+        lz::minres_step_rule(uu[c], wu[c], thr[c], max_iter, s, coef + c, b);
+        minres_store(b, c, s, state, ctl);
         *nlive += s.live;
     }
     return 0;

@@ -73,6 +73,19 @@ template <typename T>
 int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
              double shift, const T *dinv, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status,
              double *resid, double *est, int *info);
+// ---- batched MINRES (lz_minres.hip): k_minres_update runs k_cg_update's
+// shapes (kCgThreads, kCgRows128, kCgGridCap; one slab of b doubles per block).
+// The solve's work: kMinresWorkBlocks blocks, [U0 | U1 | W | D0 | D1].
+constexpr int kMinresWorkBlocks = 5;
+// lz_minres_update (include/lz_hip.h)
+template <typename T>
+int minres_update(lz_handle *h, int64_t n, int b, const double *coef, const T *W, const T *U, T *Uo, const T *D1, T *D2,
+                  T *X, double *uu);
+// lz_minres_solve (include/lz_hip.h)
+template <typename T>
+int minres_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                 double shift, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status, double *resid,
+                 double *est, int *info);
 // ---- block conjugate gradients (lz_bcg.hip)
 // k_bcg_update / k_bcg_direction: kBcgThreads threads per block; the b = 16 fp64 MFMA
 // form covers kBcgRows16 rows per block pass (one 16-row tile per wave), the b = 32 fp32

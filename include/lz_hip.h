@@ -558,6 +558,62 @@ int lz_bcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, c
                  lz_dtype dtype, int b, double shift, const void *B, void *X, void *work, const lz_cg_opts *opts,
                  int *iters, int *status, double *resid, double *est, int *info);
 
+/* ------------- MINRES for symmetric indefinite systems (no reference counterpart)
+ * Paige-Saunders MINRES on M = A + shift I, symmetric and nonsingular but not
+ * necessarily definite, per column, on unnormalised Lanczos vectors u_k = beta_k v_k:
+ *   u_1 = b - M x, W = M u_k, alpha_k = (W.u_k) / beta_k^2,
+ *   u_{k+1} = W / beta_k - (alpha_k / beta_k) u_k - (beta_k / beta_{k-1}) u_{k-1},
+ *   beta_{k+1}^2 = u_{k+1}.u_{k+1} of the stored vector.
+ * The direction d and x run one pass behind (the rotation of step k - 1 needs beta_k):
+ * pass k stores d_{k-1} = (u_{k-1} / beta_{k-1} - delta d_{k-2} - eps d_{k-3}) / gamma and
+ * x += tau d_{k-1}.
+ *
+ * lz_minres_update: the row-local half of one pass on n x b row-major blocks with ld =
+ * b, n >= 1, 1 <= b <= 64, either dtype.  coef: 7 b doubles on the device, read only,
+ * [a_w | a_u | a_o | g_o | g_1 | g_2 | tau] with b entries each, rounded once to the
+ * blocks' dtype.  Element by element, in this order,
+ *   u' = a_w * W;  u' = fma(a_u, U, u');  u' = fma(a_o, Uo, u');
+ *   d' = g_o * Uo; d' = fma(g_1, D1, d');  d' = fma(g_2, D2, d');
+ *   X = fma(tau, d', X)
+ * and uu[c] = sum_i u'[i][c]^2 of the stored u', products and sums in fp64 in a fixed
+ * order (b doubles, device; no atomics: two runs give the same bits).  u' is stored
+ * into Uo and d' into D2 (Uo is read once for both); W, U and D1 are read only.  A
+ * coefficient that is zero skips its line, whatever its operand holds (the product
+ * lines then give 0): a first pass (a_o = g_o = g_1 = g_2 = tau = 0) reads neither Uo,
+ * D1 nor D2; tau == 0 leaves column c of X bit for bit; seven zeros (a frozen column)
+ * store u' = d' = 0 and keep X.  Six blocks read, three written, one fold; no host
+ * synchronisation once the slab workspace has its size.  The two forms and the
+ * LZ_CG_GENERIC / LZ_CG_NT switches of lz_cg_update: both forms give the same bits in
+ * u', d' and X (uu sums in another order).  The 128-byte-row form moves W, Uo, D1, D2
+ * and X with non-temporal loads and d' and X with non-temporal stores; U and u', which
+ * an SpMM gathers, with plain ones.  The six blocks must not overlap: LZ_E_ARG. */
+int lz_minres_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *coef, const void *W, const void *U,
+                     void *Uo, const void *D1, void *D2, void *X, double *uu);
+/* Solves (A + shift I) X = B for a symmetric A + shift I that may be indefinite.
+ * lz_cg_solve's arguments, options and results exactly, but work is 5 n b elements
+ * ([U0 | U1 | W | D0 | D1], not read on entry; the two U and the two D change places
+ * after every pass, nothing is copied).  Start, and every restart: U = B - M X with its
+ * dots (one SpMM), the start rule.  Per pass: one lz_csr_spmm_axpby_dots (W = M U, with
+ * W.U), one one-workgroup launch for the scalars, one lz_minres_update; one 4-byte
+ * read of the live count per check_every passes.  The first pass of a phase is the
+ * Lanczos step alone; every later one also applies a step to x, so a column that
+ * takes k steps runs k + 1 passes.  A column is frozen (seven zero coefficients: its X
+ * does not change by a bit) in the pass that stores its last x: when the recurrence's
+ * residual |phibar| reaches tol |B_c|, its steps reach max_iter, or beta_{k+1} = 0 (the
+ * Krylov space is exhausted; nothing is divided by it).  When no column is live the
+ * residual is measured: columns that fail tol and have steps left run again from it,
+ * at most max_restarts times.  status[b]: 0 met tol on the measured residual; 1
+ * iterations or restarts spent; 2 (LZ_MINRES_BREAKDOWN) a scalar that is not finite or
+ * gamma = 0 -- a NaN in B_c, or M singular on this Krylov space -- with X_c untouched
+ * from then on.  resid[b]: measured; est[b]: the recurrence's last |phibar| / |B_c|;
+ * info[3] = {passes enqueued, restarts, SpMMs}: SpMMs = passes + 2 + restarts when a
+ * pass ran, else 1.  No preconditioner.  One column's arithmetic depends on no other
+ * column's data. */
+#define LZ_MINRES_BREAKDOWN 2
+int lz_minres_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const void *val,
+                    lz_dtype dtype, int b, double shift, const void *B, void *X, void *work, const lz_cg_opts *opts,
+                    int *iters, int *status, double *resid, double *est, int *info);
+
 /* ------------------------- transpose and normal operator (no reference counterpart)
  * The CSR of A^T, built on the device: output row c (c < n_cols) holds the
  * entries of A whose column is c in the order of their positions in A's

@@ -162,6 +162,37 @@ int lzh_cg_scalars(int b, int first, int max_iter, const double *gamma, const do
 int lzh_pcg_scalars(int b, int first, int max_iter, const double *rz, const double *rr, const double *delta,
                     const double *thr, double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters,
                     int *status, double *coef, int *nlive);
+/* ------------------------------------------- batched MINRES
+ * The per-column scalar rules of lz_minres_solve (lz_hip.h), the very code its
+ * one-workgroup kernels run (csrc/lz_minres.hpp), on host arrays.  state: 8 rows of b
+ * doubles, [beta_prev | alpha_prev | c1 | s1 | c2 | s2 | phibar | est2] -- beta_{k-1} and
+ * alpha_{k-1} of the phase's last pass, the rotations of steps k - 2 and k - 3, the
+ * recurrence's signed residual norm, and phibar^2 when the column last froze.  ctl: 4
+ * rows of b ints, [live | iters | status | pass] -- status 0 met tol, 1 not shown to, 2
+ * breakdown; pass: the passes of this phase so far.  thr[c] = tol^2 |B_c|^2.  Both
+ * return 0 and the live count in *nlive, or -1 on a bad argument.
+ *
+ * lzh_minres_start: uu[c] is the measured |B_c - M X_c|^2.  initial != 0 clears iters
+ * and sets est2 = uu first.  A status-2 column stays frozen; uu <= thr: frozen, status 0
+ * (a zero column passes with 0 <= 0, nothing is divided); else status 1, live while
+ * iters < max_iter.  The recurrence is set to a phase's first pass: pass = 0, both
+ * rotations the identity, phibar = sqrt(uu) (0 for a column that is not live).
+ * lzh_minres_scalars: one pass.  uu[c] = beta_k^2 (a start's measured dot, else the dot
+ * of the stored u_k), wu[c] = (M u_k).u_k.  coef: 7 rows of b doubles, [a_w | a_u | a_o
+ * | g_o | g_1 | g_2 | tau] of lz_minres_update.  A frozen column gets seven zeros and
+ * its state is untouched.  pass == 0: the Lanczos step alone, alpha = wu / uu, a_w = 1 /
+ * beta_k, a_u = -alpha / beta_k, the other five zero.  pass > 0: step k - 1's rotation
+ * (see lz_hip.h), g_o = 1 / (beta_{k-1} gamma), g_1 = -delta / gamma, g_2 = -eps /
+ * gamma, tau = c phibar, phibar <- -s phibar, iters += 1; when phibar^2 <= thr, iters
+ * reaches max_iter or beta_k == 0 the column is frozen with est2 = phibar^2 and a_w =
+ * a_u = a_o = 0 (nothing is divided by beta_k); else the Lanczos coefficients with a_o
+ * = -beta_k / beta_{k-1}.  A value that is not finite, gamma == 0, or uu <= 0 where
+ * the Lanczos step needs it: status 2, frozen for good, seven zeros, iters not
+ * advanced. */
+int lzh_minres_start(int b, int max_iter, int initial, const double *uu, const double *thr, double *state, int *ctl,
+                     int *nlive);
+int lzh_minres_scalars(int b, int max_iter, const double *uu, const double *wu, const double *thr, double *state,
+                       int *ctl, double *coef, int *nlive);
 /* ------------------------------------------- block conjugate gradients
  * The b x b rules of lz_bcg_solve (lz_hip.h), the very code its one-workgroup
  * kernels run (csrc/lz_bcg.hpp), on host arrays; every matrix b x b row-major fp64, 1
