@@ -41,6 +41,7 @@ LZ_ROW_MAJOR, LZ_COL_MAJOR = 0, 1
  LZ_K_SPMV) = range(1, 10)
 LZ_K_WIN, LZ_K_YCM, LZ_K_EPI, LZ_K_AX3, LZ_K_DOT = 0x100, 0x200, 0x400, 0x800, 0x1000
 LZ_K_AX4 = 0x2000
+LZ_K_RESID = 0x4000  # lz_csr_spmm_resid's fused residual store
 LZ_K_GRAM16, LZ_K_GRAM32F, LZ_K_GRAM_GEN, LZ_K_TSMM16, LZ_K_TSMM32F, LZ_K_TSMM_GEN = range(1, 7)
 LZ_K_PGRAM16, LZ_K_PGRAM_GEN, LZ_K_PAPPLY16, LZ_K_PAPPLY_GEN = range(7, 11)
 # blocks per group of the panel Gram kernels (W is re-read once per group): b = 16 fp64 MFMA, generic
@@ -136,6 +137,8 @@ HIP_SYMBOLS = [
     ("lz_col_dots", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     ("lz_csr_spmm_axpby_dots", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp,
                                         _c_dbl, _c_dbl, _c_vp, _c_vp, _c_vp]),
+    ("lz_csr_spmm_resid", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp,
+                                   _c_vp]),
     ("lz_cheb_moments", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_dbl, _c_int,
                                  _c_vp, _c_vp, _c_vp]),
     ("lz_cg_update", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -179,6 +182,14 @@ HIP_SYMBOLS = [
     ("lz_block_lanczos_reorth_resume_normal", _c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp,
                                                        _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_vp,
                                                        _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int, _c_vp]),
+    ("lz_inverse_apply", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp,
+                                  _c_vp, _c_vp]),
+    ("lz_block_lanczos_reorth_inverse", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int,
+                                                 _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int,
+                                                 _c_vp, _c_vp, _c_vp]),
+    ("lz_block_lanczos_reorth_resume_inverse", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int,
+                                                        _c_int, _c_int, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                                        _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
     ("lz_vector_lanczos", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_i64,
                                    _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_fdtd_block", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp,
@@ -229,6 +240,8 @@ HOST_SYMBOLS = [
     ("lzh_ritz_pairs_dense", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     ("lzh_restart_coeffs", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_restart_fill", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
+    ("lzh_ritz_pairs_dense_mag", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    ("lzh_restart_coeffs_mag", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_gershgorin", _c_int, [_c_i64, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_cg_start", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                               _c_vp]),
@@ -517,6 +530,27 @@ class CgOpts(ctypes.Structure):
     _fields_ = [("tol", _c_dbl), ("max_iter", _c_int), ("check_every", _c_int), ("max_restarts", _c_int)]
 
 
+class Inverse(ctypes.Structure):
+    """lz_inverse (include/lz_hip.h): (A - sigma I)^-1 through an inner solve; method 0 MINRES,
+    1 column CG, 2 block CG."""
+    _fields_ = [("sigma", _c_dbl), ("method", _c_int), ("opts", CgOpts)]
+
+
+class InverseInfo(ctypes.Structure):
+    """lz_inverse_info (include/lz_hip.h): what the inner solves of an inverse operator did.
+    Every call that takes one accumulates into it; a fresh one is zero."""
+    _fields_ = [("solves", _c_i64), ("passes", _c_i64), ("n_spmm", _c_i64), ("not_met", _c_i64),
+                ("breakdown", _c_i64), ("worst", _c_dbl)]
+
+
+INNER_METHODS = {"minres": 0, "columns": 1, "block": 2}
+# Handle.eigsh(sigma=...): the default inner tolerance is this multiple of tol (DESIGN.md 27: the
+# largest power of ten at which the stand-in's cases keep the exact-solve cycle count), clipped
+# from below at INNER_TOL_FLOOR_EPS * eps of the operator's dtype
+INNER_TOL_FACTOR = 1.0
+INNER_TOL_FLOOR_EPS = 64.0
+
+
 def _cheb(filt):
     """A ChebFilter from a (degree, lo, hi, ref) tuple (or one passed through)."""
     if isinstance(filt, ChebFilter):
@@ -620,23 +654,32 @@ def ritz_pairs(m: int, b: int, alpha: np.ndarray, beta: np.ndarray, nev: int, wh
     return theta, S, resid
 
 
-def _which(which: str) -> int:
+def _which(which: str, magnitude: bool = False) -> int:
+    """lzh_*'s `which` of "smallest" / "largest"; magnitude: "magnitude" is accepted too (-1: the
+    _mag functions, which take no `which`)."""
+    if magnitude and which == "magnitude":
+        return -1
     if which not in ("smallest", "largest"):
-        raise ValueError("which must be 'smallest' or 'largest'")
+        raise ValueError("which must be 'smallest' or 'largest'" + (" or 'magnitude'" if magnitude else ""))
     return 0 if which == "smallest" else 1
 
 
 def ritz_pairs_dense(m: int, b: int, T: np.ndarray, beta_m: np.ndarray, nev: int, which: str = "largest"):
     """ritz_pairs for a dense symmetric projected matrix T ((m*b, m*b), what a restarted
     solve has) and the b x b true beta_m of the final residual (lzh_ritz_pairs_dense):
-    (theta[nev], S (m*b, nev), resid[nev])."""
-    w = _which(which)
+    (theta[nev], S (m*b, nev), resid[nev]).  which = "magnitude" (lzh_ritz_pairs_dense_mag):
+    |theta| descending, ties by theta ascending -- the wanted end of a shift-and-invert
+    operator."""
+    w = _which(which, magnitude=True)
     T = np.ascontiguousarray(T, np.float64)
     beta_m = np.ascontiguousarray(beta_m, np.float64)
     if T.shape != (m * b, m * b) or beta_m.size != b * b:
         raise ValueError("T must be (m*b, m*b) and beta_m (b, b)")
     theta, S, resid = np.empty(nev), np.empty((m * b, nev)), np.empty(nev)
-    if host_lib().lzh_ritz_pairs_dense(m, b, _p(T), _p(beta_m), nev, w, _p(theta), _p(S), _p(resid)):
+    if w < 0:
+        if host_lib().lzh_ritz_pairs_dense_mag(m, b, _p(T), _p(beta_m), nev, _p(theta), _p(S), _p(resid)):
+            raise LanczosError("lzh_ritz_pairs_dense_mag failed (1 <= nev <= m*b)")
+    elif host_lib().lzh_ritz_pairs_dense(m, b, _p(T), _p(beta_m), nev, w, _p(theta), _p(S), _p(resid)):
         raise LanczosError("lzh_ritz_pairs_dense failed (1 <= nev <= m*b)")
     return theta, S, resid
 
@@ -645,8 +688,9 @@ def restart_coeffs(m: int, b: int, r: int, T: np.ndarray, beta_m: np.ndarray, wh
     """The host side of a thick restart that keeps the first r*b Ritz pairs of T
     (lzh_restart_coeffs): (theta_k[r*b], Z (r, m, b, b) in the layout of panel_compress,
     sigma (r, b, b) for block_lanczos_reorth_resume, T_next (m*b, m*b) with diag(theta_k)
-    and the mirrored arrow block; restart_fill adds the resumed cycle's alpha / beta)."""
-    w = _which(which)
+    and the mirrored arrow block; restart_fill adds the resumed cycle's alpha / beta).
+    which = "magnitude" (lzh_restart_coeffs_mag): the r*b pairs largest in |theta|."""
+    w = _which(which, magnitude=True)
     T = np.ascontiguousarray(T, np.float64)
     beta_m = np.ascontiguousarray(beta_m, np.float64)
     if T.shape != (m * b, m * b) or beta_m.size != b * b:
@@ -654,7 +698,10 @@ def restart_coeffs(m: int, b: int, r: int, T: np.ndarray, beta_m: np.ndarray, wh
     if not 1 <= r < m:
         raise LanczosError("lzh_restart_coeffs: 1 <= r < m")
     theta_k, Z, sigma, Tn = np.empty(r * b), np.empty((r, m, b, b)), np.empty((r, b, b)), np.empty((m * b, m * b))
-    if host_lib().lzh_restart_coeffs(m, b, r, _p(T), _p(beta_m), w, _p(theta_k), _p(Z), _p(sigma), _p(Tn)):
+    if w < 0:
+        if host_lib().lzh_restart_coeffs_mag(m, b, r, _p(T), _p(beta_m), _p(theta_k), _p(Z), _p(sigma), _p(Tn)):
+            raise LanczosError("lzh_restart_coeffs_mag failed")
+    elif host_lib().lzh_restart_coeffs(m, b, r, _p(T), _p(beta_m), w, _p(theta_k), _p(Z), _p(sigma), _p(Tn)):
         raise LanczosError("lzh_restart_coeffs failed")
     return theta_k, Z, sigma, Tn
 
@@ -800,8 +847,8 @@ class _ReorthOp(NamedTuple):
     """What Handle._reorth_op makes of A / filt / work / normal: fn(handle, *head, b, ..., passes, *tail)."""
     name: str                    # the ABI function
     head: tuple                  # n [, P.n], nnz, the CSR pointers [and the transpose's], dtype
-    tail: tuple                  # nothing | &filt, work | work | degree, lo, hi, gamma, work
-    filt: object                 # the ChebFilter or gamma array tail points to: alive as long as this description
+    tail: tuple                  # nothing | &filt, work | work | degree, lo, hi, gamma, work | &inv, work, &info
+    filt: object                 # the ChebFilter, gamma array or Inverse tail points to: alive as long as this description
 
 
 def _f64(t) -> np.ndarray:
@@ -846,8 +893,10 @@ def _restart_sizes(who: str, count: str, nev: int, b: int, m: Optional[int], kee
 class _Restart:
     """The thick-restart loop that eigsh, its filtered form and svds share, as steps: it owns
     the panel V (m blocks of (n, b), vstride apart), W, q / al / be with their host copies
-    alpha / beta, the projected matrix T, the operator keywords op (filt + work, or normal:
-    one operator for every cycle of a solve) and the counters.
+    alpha / beta, the projected matrix T, the operator keywords op (filt + work, series + work,
+    inverse + work, or normal: one operator for every cycle of a solve; only the keywords the
+    caller set are passed on) and the counters.  which: "smallest", "largest" or, on an
+    inverse, "magnitude".
 
         first(B)         block_lanczos_reorth from B, copy back, Assemble_T
         ritz(which)      all m*b Ritz pairs of T: theta, S, resid, max|theta|
@@ -1012,6 +1061,22 @@ class Handle:
         _check(self.L.lz_csr_spmm_axpby_dots(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
                                              a, _ptr(X), c, d, _ptr(Z), _ptr(Y), _ptr(dots)), "lz_csr_spmm_axpby_dots")
         return Y, dots.view(2, b)
+
+    def spmm_resid(self, A: CsrDevice, X, theta, R, dots=None):
+        """R = A X - X diag(theta) and the column dots of the stored R with itself and with X
+        (lz_csr_spmm_resid): the residual block of b Ritz pairs in one pass.  theta: b fp64
+        elements on the device, each rounded to A's dtype once; X (read only) and R (n, b)
+        contiguous and distinct.  With every theta equal it is spmm_axpby_dots(A, 1, X, -theta, 0,
+        None, R) bit for bit.  Returns (R, dots); dots[0] = the squared residual norms."""
+        torch = _torch()
+        n, b = self._blocks("spmm_resid", A, X, R)
+        if not torch.is_tensor(theta) or theta.dtype != torch.float64 or not theta.is_contiguous() \
+                or theta.numel() != b or theta.device != X.device:
+            raise LanczosError("spmm_resid: theta is a contiguous fp64 device tensor of b elements")
+        dots = self._dots("spmm_resid", dots, 1, b, R)
+        _check(self.L.lz_csr_spmm_resid(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                        _ptr(theta), _ptr(X), _ptr(R), _ptr(dots)), "lz_csr_spmm_resid")
+        return R, dots.view(2, b)
 
     def cheb_moments(self, A: CsrDevice, X0, K: int, lo: float, hi: float, work=None, dots=None):
         """The raw dots of K Chebyshev steps from X0 on (A - c0) / e, [lo, hi] = [c0 - e, c0 + e]
@@ -1377,11 +1442,39 @@ class Handle:
             raise LanczosError(f"{what}: series = (degree, lo, hi, gamma) with degree >= 1 and degree + 1 coefficients")
         return int(degree), float(lo), float(hi), gamma
 
-    def _reorth_op(self, what: str, A, n: int, b: int, like, filt, work, normal, series=None) -> "_ReorthOp":
-        """The operator of a kept-basis solve (A, p(A), Pt (P .) or a Chebyshev series s(A):
-        block_lanczos_reorth's docstring), validated, as the ABI function
-        lz_<what>[_cheb | _normal | _series] with the arguments that differ between the four."""
+    @staticmethod
+    def _inverse(what: str, inverse, work, n: int, b: int, like):
+        """(Inverse, InverseInfo) of inverse = (sigma, inner, tol, max_iter, info) on n x b blocks:
+        inner "minres", "columns" or "block"; max_iter None: min(10 n, 10000), solve's default;
+        info an InverseInfo that the call accumulates into; work flat, MINRES_WORK_BLOCKS*n*b
+        elements of the blocks' dtype."""
+        sigma, inner, tol, max_iter, info = inverse
+        if inner not in INNER_METHODS:
+            raise LanczosError(f'{what}: inner is "minres", "columns" or "block"')
+        if not isinstance(info, InverseInfo):
+            raise LanczosError(f"{what}: inverse = (sigma, inner, tol, max_iter, info) with info an InverseInfo")
+        if inner == "block" and b > BCG_MAX_B:
+            raise LanczosError(f'{what}: inner="block" takes b <= {BCG_MAX_B}')
+        k = MINRES_WORK_BLOCKS
+        if work is None or work.dim() != 1 or not work.is_contiguous() or work.numel() < k * n * b \
+                or work.dtype != like.dtype:
+            raise LanczosError(f"{what}: work is a flat contiguous tensor of {k}*n*b elements of the solve's dtype")
+        max_iter = min(10 * n, 10000) if max_iter is None else int(max_iter)
+        return Inverse(float(sigma), INNER_METHODS[inner], CgOpts(float(tol), max_iter, 0, 3)), info
+
+    def _reorth_op(self, what: str, A, n: int, b: int, like, filt, work, normal, series=None,
+                   inverse=None) -> "_ReorthOp":
+        """The operator of a kept-basis solve (A, p(A), Pt (P .), a Chebyshev series s(A) or the
+        inverse (A - sigma I)^-1: block_lanczos_reorth's docstring), validated, as the ABI function
+        lz_<what>[_cheb | _normal | _series | _inverse] with the arguments that differ between
+        the five."""
         csr = lambda M: (_ptr(M.row_ptr), _ptr(M.col), _ptr(M.val))
+        if inverse is not None:
+            if filt is not None or normal is not None or series is not None:
+                raise LanczosError(f"{what}: inverse= is mutually exclusive with filt=, normal= and series=")
+            inv, info = self._inverse(what, inverse, work, n, b, like)
+            return _ReorthOp(f"lz_{what}_inverse", (n, A.nnz, *csr(A), A.dtype),
+                             (ctypes.addressof(inv), _ptr(work), ctypes.addressof(info)), inv)
         if series is not None:
             if filt is not None or normal is not None:
                 raise LanczosError(f"{what}: series= is mutually exclusive with filt= and normal=")
@@ -1411,6 +1504,21 @@ class Handle:
         _check(self.L.lz_normal_apply(self.ptr, n, P.n, P.nnz, _ptr(P.row_ptr), _ptr(P.col), _ptr(P.val),
                                       _ptr(Pt.row_ptr), _ptr(Pt.col), _ptr(Pt.val), P.dtype, b, _ptr(X), _ptr(Y),
                                       _ptr(work)), "lz_normal_apply")
+        return Y
+
+    def inverse_apply(self, A: CsrDevice, inverse, X, Y, work):
+        """Y = (A - sigma I)^-1 X by one inner solve from a zero start block (lz_inverse_apply),
+        the operator line of eigsh(sigma=...): inverse = (sigma, inner, tol, max_iter, info) with
+        inner "minres" (any sigma), "columns" or "block" (conjugate gradients: A - sigma I
+        positive definite), tol the relative residual of a column, info an InverseInfo the call
+        accumulates into.  X (read only), Y (n, b) contiguous and distinct; work flat,
+        MINRES_WORK_BLOCKS*n*b elements.  A column that misses tol is counted in info.not_met, not
+        raised.  Synchronises the stream."""
+        n, b = self._blocks("inverse_apply", A, X, Y)
+        inv, info = self._inverse("inverse_apply", inverse, work, n, b, X)
+        _check(self.L.lz_inverse_apply(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                       _ptr(X), _ptr(Y), ctypes.addressof(inv), _ptr(work), ctypes.addressof(info)),
+               "lz_inverse_apply")
         return Y
 
     def to_row_major(self, Xcm, Y):
@@ -1510,7 +1618,7 @@ class Handle:
         return W
 
     def block_lanczos_reorth(self, A: CsrDevice, B, m: int, lc: int, q, alpha, beta, V, vstride: int, W,
-                             passes: int = 2, filt=None, work=None, normal=None, series=None):
+                             passes: int = 2, filt=None, work=None, normal=None, series=None, inverse=None):
         """Block Lanczos on a kept basis with `passes` rounds of full reorthogonalisation
         per step (lz_block_lanczos_reorth).  q[m*b], alpha[m,b,b], beta[m+1,b,b] (beta[m]
         = the true beta_m), the panel V (m blocks) and W (the final residual) are written
@@ -1520,10 +1628,14 @@ class Handle:
         the same solve on G = P^T P (lz_block_lanczos_reorth_normal); A is not used then (None)
         and filt must be None.  series = (degree, lo, hi, gamma) with work as for filt: the
         same solve on the Chebyshev series sum_k gamma_k T_k((A - c0) / e) of cheb_series_apply
-        (lz_block_lanczos_reorth_series); filt and normal must be None."""
+        (lz_block_lanczos_reorth_series); filt and normal must be None.  inverse = (sigma, inner,
+        tol, max_iter, info) with work flat, MINRES_WORK_BLOCKS*n*b elements: the same solve on
+        (A - sigma I)^-1, every operator line one inner solve as inverse_apply runs it
+        (lz_block_lanczos_reorth_inverse); filt, normal and series must be None.  Such a cycle
+        synchronises the stream at every step."""
         n, b = B.shape
         self._panel(V, vstride, n, b, max(m, 1))
-        op = self._reorth_op("block_lanczos_reorth", A, n, b, W, filt, work, normal, series)
+        op = self._reorth_op("block_lanczos_reorth", A, n, b, W, filt, work, normal, series, inverse)
         _check(getattr(self.L, op.name)(self.ptr, *op.head, b, m, lc, _ptr(B), _ptr(q), _ptr(alpha), _ptr(beta),
                                         _ptr(V), vstride, _ptr(W), passes, *op.tail), op.name)
 
@@ -1569,25 +1681,27 @@ class Handle:
 
     def block_lanczos_reorth_resume(self, A: CsrDevice, r: int, m: int, lc: int, sigma, q, alpha, beta, V,
                                     vstride: int, W, passes: int = 2, filt=None, work=None, normal=None,
-                                    series=None):
+                                    series=None, inverse=None):
         """Steps r .. m-1 of block_lanczos_reorth on a thick-restarted basis
         (lz_block_lanczos_reorth_resume): blocks 0 .. r-1 of V hold the kept Ritz blocks
         (panel_compress), W the previous cycle's residual, sigma (r, b, b) the device copy of
         restart_coeffs' sigma.  Writes alpha[r:], beta[r:], q[r*b:], blocks r .. m-1 and W.
-        filt, work, normal, series: as block_lanczos_reorth (the same operator for every cycle of a
-        solve)."""
+        filt, work, normal, series, inverse: as block_lanczos_reorth (the same operator for every
+        cycle of a solve)."""
         n, b = W.shape
         self._panel(V, vstride, n, b, max(m, 1))
         if not sigma.is_contiguous() or sigma.numel() < max(r, 0) * b * b or sigma.dtype != W.dtype \
                 or V.dtype != W.dtype or not W.is_contiguous():
             raise LanczosError("block_lanczos_reorth_resume: W (n, b) and sigma (r, b, b) contiguous, one dtype")
-        op = self._reorth_op("block_lanczos_reorth_resume", A, n, b, W, filt, work, normal, series)
+        op = self._reorth_op("block_lanczos_reorth_resume", A, n, b, W, filt, work, normal, series, inverse)
         _check(getattr(self.L, op.name)(self.ptr, *op.head, b, r, m, lc, _ptr(sigma), _ptr(q), _ptr(alpha),
                                         _ptr(beta), _ptr(V), vstride, _ptr(W), passes, *op.tail), op.name)
 
     def eigsh(self, A: CsrDevice, nev: int, which: str = "largest", b: int = 16, m: Optional[int] = None,
               keep: Optional[int] = None, tol: float = 1e-10, max_cycles: int = 100, B=None, lc: int = 0,
-              passes: int = 2, filter_degree: Optional[int] = None, cut: Optional[float] = None):
+              passes: int = 2, filter_degree: Optional[int] = None, cut: Optional[float] = None,
+              sigma: Optional[float] = None, inner: str = "minres", inner_tol: Optional[float] = None,
+              inner_max_iter: Optional[int] = None):
         """The nev outermost eigenpairs of A by thick-restart block Lanczos in a fixed panel
         of m blocks.  Cycle 1 is block_lanczos_reorth from B (default uniform_B); every later
         cycle keeps the first keep*b Ritz pairs (restart_coeffs), compresses the panel onto
@@ -1616,7 +1730,37 @@ class Handle:
         of each pair, which need not be the first nev: V is not re-packed), filter = (degree,
         lo, hi, ref), n_steps (Lanczos steps, the unfiltered solve included); resid is the
         measured residual on A, cycles counts the filtered cycles, n_spmm every SpMM
-        (bounds, filter steps and checks).  Needs 2 n b more elements of device memory."""
+        (bounds, filter steps and checks).  Needs 2 n b more elements of device memory.
+
+        sigma given: the nev eigenpairs nearest sigma, anywhere in the spectrum, by the same restart
+        on (A - sigma I)^-1 (shift-and-invert), whose Ritz values nu = 1 / (lambda - sigma) of
+        largest magnitude are the wanted ones.  which must stay at its default and filter_degree
+        None.  Every operator line is one inner solve of b columns from a zero start (inverse_apply):
+        inner = "minres" for any sigma; "columns" or "block" (conjugate gradients) for a sigma
+        below the spectrum -- a solve in which a column reports "not positive definite" raises and
+        names inner="minres".  inner_tol: the relative residual of an inner column, default
+        max(INNER_TOL_FACTOR * tol, INNER_TOL_FLOOR_EPS * eps); inner_max_iter: default min(10 n,
+        10000).  An inner column that misses inner_tol does not stop the solve (inner_not_met
+        counts it): the stop test is measured on A.  After every cycle's compress ("magnitude"):
+        Rayleigh-Ritz on A over the keep kept blocks as eigsh_interval does it (H = Y^T A Y by one
+        spmm and one panel_gram per block, eigh on the host, the rotated blocks by panel_apply) with
+        the residuals ||A x - lambda x|| of each rotated block from one spmm_resid; the panel is
+        not rotated.  Converged when the nev kept pairs nearest sigma have residuals <= tol *
+        scale, scale = max(|lo|, |hi|) of gershgorin(A); else max_cycles (converged = False).  One
+        panel_compress packs the nev vectors, ordered by |lambda - sigma| ascending.  The dict:
+        theta, resid (measured on A), V, vstride, cycles, converged, history, scale as above, and
+        sigma, inner, inner_tol, inner_solves, inner_passes, inner_not_met, inner_worst,
+        inner_breakdown (the InverseInfo counts), n_steps (Lanczos steps = inner solves), n_spmm
+        (every SpMM: the inner solves' and 2 keep per check).  Needs 5 n b more elements of device
+        memory.  The cost of an inner solve grows as sigma nears an eigenvalue; there is no
+        preconditioner."""
+        if sigma is not None:
+            if which != "largest":
+                raise LanczosError("eigsh: sigma= selects the pairs nearest sigma; which must stay at its default")
+            if filter_degree is not None or cut is not None:
+                raise LanczosError("eigsh: sigma= and filter_degree= / cut= are mutually exclusive")
+            return self._eigsh_sigma(A, nev, float(sigma), b, m, keep, tol, max_cycles, B, lc, passes, inner,
+                                     inner_tol, inner_max_iter)
         _which(which)
         if filter_degree is not None and not 1 <= int(filter_degree) <= 256:
             raise LanczosError("eigsh: 1 <= filter_degree <= 256")
@@ -1639,6 +1783,77 @@ class Handle:
         d.pack(S, nev)  # the wanted Ritz vectors, in place, into the first ceil(nev / b) blocks
         return dict(theta=theta, resid=resid, V=d.V, vstride=d.vstride, cycles=d.cycles, n_spmm=d.steps,
                     converged=converged, history=history, scale=scale)
+
+    def _eigsh_sigma(self, A, nev, sigma, b, m, keep, tol, max_cycles, B, lc, passes, inner, inner_tol,
+                     inner_max_iter):
+        """eigsh(sigma=...): see eigsh's docstring."""
+        torch = _torch()
+        if inner not in INNER_METHODS:
+            raise LanczosError('eigsh: inner is "minres", "columns" or "block"')
+        if not np.isfinite(sigma):
+            raise LanczosError("eigsh: sigma must be finite")
+        m, r = _restart_sizes("eigsh", "nev", nev, b, m, keep)
+        n = A.n
+        eps = float(np.finfo(np.float64 if A.val.dtype == torch.float64 else np.float32).eps)
+        if inner_tol is None:
+            inner_tol = max(INNER_TOL_FACTOR * tol, INNER_TOL_FLOOR_EPS * eps)
+        inner_tol = float(inner_tol)
+        if not inner_tol > 0.0:
+            raise LanczosError("eigsh: inner_tol > 0")
+        lo, hi = gershgorin(A)
+        scale = max(abs(lo), abs(hi))
+        info = InverseInfo()
+        work = torch.empty(MINRES_WORK_BLOCKS * n * b, dtype=A.val.dtype, device=A.val.device)
+        d = _Restart(self, A, n, b, m, r, lc, passes, A.val, inverse=(sigma, inner, inner_tol, inner_max_iter, info),
+                     work=work)
+        V, vstride, kw = d.V, d.vstride, d.kw
+        U, X = work[:n * b].view(n, b), work[n * b:2 * n * b].view(n, b)  # (the solver's workspace is free between solves)
+        C = torch.empty(r, b, b, **kw)
+        dots = torch.empty(r, 2, b, dtype=torch.float64, device=A.val.device)
+        rb = r * b
+
+        def ran():
+            if inner != "minres" and info.breakdown:
+                raise LanczosError(f'eigsh: A - sigma I is not positive definite at sigma = {sigma} (inner="{inner}", '
+                                   f'{info.breakdown} columns): use inner="minres"')
+
+        def check():
+            """Rayleigh-Ritz on A over the r kept blocks: (lambda ascending, true residual norms,
+            the rb x rb rotation).  W and the panel are not touched."""
+            H = np.empty((rb, rb))
+            for i in range(r):
+                self.spmm(A, V[i * vstride:i * vstride + n * b].view(n, b), U)
+                self.panel_gram(V, vstride, r, U, C)  # C_j = Y_j^T A Y_i: block column i of H
+                H[:, i * b:(i + 1) * b] = _f64(C).reshape(rb, b)
+            lam, Cm = np.linalg.eigh(0.5 * (H + H.T))
+            Sd = torch.from_numpy(_pack_chunks(Cm, r, b)).to(**kw)
+            th = torch.from_numpy(lam).to(device=A.val.device)
+            for c in range(r):
+                self.panel_apply(0.0, 1.0, V, vstride, r, Sd[c], X)
+                self.spmm_resid(A, X, th[c * b:(c + 1) * b], U, dots[c])
+            res = np.sqrt(np.maximum(dots.cpu().numpy()[:, 0, :].reshape(rb), 0.0))
+            return lam, res, Cm
+
+        d.first(d.start_block(B))
+        ran()
+        history = []
+        while True:
+            d.compress("magnitude")
+            lam, res, Cm = check()
+            sel = np.argsort(np.abs(lam - sigma), kind="stable")[:nev]
+            history.append(float(res[sel].max()))
+            converged = bool((res[sel] <= tol * scale).all())
+            if converged or d.cycles >= max_cycles:
+                break
+            d.resume()
+            ran()
+        Zx = _pack_chunks(Cm[:, sel], r, b)
+        self.panel_compress(V, vstride, r, len(Zx), d._dev(Zx), n=n)
+        return dict(theta=lam[sel], resid=res[sel], V=V, vstride=vstride, cycles=d.cycles, n_steps=d.steps,
+                    n_spmm=int(info.n_spmm) + 2 * r * d.cycles, converged=converged, history=history, scale=scale,
+                    sigma=sigma, inner=inner, inner_tol=inner_tol, inner_solves=int(info.solves),
+                    inner_passes=int(info.passes), inner_not_met=int(info.not_met), inner_worst=float(info.worst),
+                    inner_breakdown=int(info.breakdown))
 
     def svds(self, A: CsrDevice, k: int, b: int = 16, m: Optional[int] = None, keep: Optional[int] = None,
              tol: float = 1e-10, max_cycles: int = 100, B=None, lc: int = 0, passes: int = 2):

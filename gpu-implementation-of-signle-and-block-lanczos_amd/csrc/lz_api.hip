@@ -381,14 +381,34 @@ static bool pairwise_apart(std::initializer_list<Span> s)
     return true;
 }
 
-// The operator of a kept-basis solve or of an apply entry, whatever the dtype, in one of four forms:
+// cg_solve as krylov_entry and the Inverse operator call it, for lz_cg_solve (dinv NULL) and lz_pcg_solve: dinv goes in
+// behind shift, in the operator's dtype
+static auto cg_solve_with(const void *dinv)
+{
+    return [dinv](lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, auto *val, int b,
+                  double shift, auto... rest) {
+        return cg_solve(h, n, nnz, rp, col, val, b, shift, (decltype(val))dinv, rest...);
+    };
+}
+
+// The Inverse form's parameters (lz_inverse) and where its counts go (lz_inverse_info, host)
+struct InverseSpec {
+    double sigma = 0.0;
+    int method = 0;  // 0 MINRES, 1 column CG, 2 block CG
+    lz_cg_opts opts = {};
+    lz_inverse_info *info = nullptr;
+};
+
+// The operator of a kept-basis solve or of an apply entry, whatever the dtype, in one of five forms:
 //   Plain   A: the n x n CSR (rp, col, val); no work
 //   Filter  p(A): the Chebyshev filter f on it; work 2 n b elements
 //   Series  s(A): the Chebyshev series sr on it; work 2 n b elements
 //   Normal  P^T (P Q): (rp, col, val) is P, p x n, and (t_rp, t_col, t_val) its n x p transpose;
 //           work the p b elements between the two SpMMs
+//   Inverse (A - sigma I)^-1 by an inner Krylov solve per block (inv); work the solver's blocks,
+//           kMinresWorkBlocks n b elements whatever the method (the CG solvers use 4)
 struct OpSpec {
-    enum Form { Plain, Filter, Series, Normal } form;
+    enum Form { Plain, Filter, Series, Normal, Inverse } form;
     int64_t nnz;
     const int64_t *rp;
     const int32_t *col;
@@ -400,6 +420,7 @@ struct OpSpec {
     const int64_t *t_rp;
     const int32_t *t_col;
     const void *t_val;
+    InverseSpec inv;
 
     // f == NULL: the plain operator (the _cheb entry points' way to say so)
     static OpSpec filter(int64_t nnz, const int64_t *rp, const int32_t *col, const void *val, const lz_cheb *f, void *work)
@@ -416,9 +437,19 @@ struct OpSpec {
     {
         return OpSpec{Normal, nnz, rp, col, val, work, {}, {}, p, t_rp, t_col, t_val};
     }
+    // iv == NULL is an argument error the entry reports: the spec then has method -1
+    static OpSpec inverse(int64_t nnz, const int64_t *rp, const int32_t *col, const void *val, const lz_inverse *iv,
+                          void *work, lz_inverse_info *info)
+    {
+        return OpSpec{Inverse, nnz, rp, col, val, work, {}, {}, 0, nullptr, nullptr, nullptr,
+                      iv ? InverseSpec{iv->sigma, iv->method, iv->opts, info} : InverseSpec{0.0, -1, {}, info}};
+    }
     // rows of the CSR (rp, col, val) of an operator on n-row blocks
     int64_t rows(int64_t n) const { return form == Normal ? p : n; }
-    int64_t work_elems(int64_t n, int b) const { return form == Plain ? 0 : form == Normal ? p * b : 2 * n * b; }
+    int64_t work_elems(int64_t n, int b) const
+    {
+        return form == Plain ? 0 : form == Normal ? p * b : form == Inverse ? kMinresWorkBlocks * n * b : 2 * n * b;
+    }
 };
 
 // A spec against the call's other buffers: the form's own parameter rules; then work is there, on 16
@@ -448,10 +479,57 @@ static int op_args(const OpSpec &op, int64_t n, int b, lz_dtype dtype, bool work
         LZ_ARG_CHECK(op.t_rp != nullptr, "normal operator: the transpose's row_ptr is NULL");
         LZ_ARG_CHECK(op.t_col != nullptr && op.t_val != nullptr, "normal operator: the transpose's col/val NULL");
         break;
+    case OpSpec::Inverse: {
+        const InverseSpec &iv = op.inv;
+        LZ_ARG_CHECK(iv.method != -1 && iv.info != nullptr, "inverse operator: inv or info is NULL");
+        LZ_ARG_CHECK(iv.method >= 0 && iv.method <= 2, "inverse operator: method in {0 MINRES, 1 CG, 2 block CG}");
+        LZ_ARG_CHECK(std::isfinite(iv.sigma), "inverse operator: sigma finite");
+        LZ_ARG_CHECK(iv.method != 2 || b <= kMaxSolveB, "inverse operator: the block method needs b <= 32");
+        LZ_ARG_CHECK(iv.opts.tol > 0.0 && std::isfinite(iv.opts.tol), "inverse operator: tol > 0, finite");
+        LZ_ARG_CHECK(iv.opts.max_iter >= 0 && iv.opts.max_restarts >= 0,
+                     "inverse operator: max_iter, max_restarts >= 0");
+        break;
+    }
     }
     LZ_ARG_CHECK(op.work != nullptr, "work is NULL");
     LZ_ARG_CHECK(!work16 || reinterpret_cast<uintptr_t>(op.work) % 16 == 0, "work must be on 16 bytes");
     LZ_ARG_CHECK(apart(span_of(op.work, op.work_elems(n, b), dtype), others), apart_msg);
+    return LZ_OK;
+}
+
+// W = (A - sigma I)^-1 Q by one inner solve of the block from X0 = 0, the solver templates called
+// as krylov_entry calls them (shift = -sigma, B = Q read only, X = W).  Synchronises the stream:
+// the solvers read their live count.  A column that misses the tolerance does not fail the call;
+// the counts go to the spec's lz_inverse_info.  The solvers' workspaces are h->cg_ws / h->bcg_ws
+// (grown and poisoned there), h->dots_ws and, for the block method, h->partials and the sqrtm
+// scratch: the callers hold nothing in any of them across this line (binv and the Gram slabs of
+// a step are consumed, in stream order, by the tsmm / sqrtm / finish before it).
+template <typename T>
+static int inverse_op(lz_handle *h, int64_t n, int b, const OpSpec &op, const T *Q, T *W)
+{
+    const InverseSpec &iv = op.inv;
+    const T *val = (const T *)op.val;
+    T *work = (T *)op.work;
+    int iters[kMaxB], status[kMaxB], info[5] = {};  // (info: 3 ints; 5 from the block solver)
+    double resid[kMaxB], est[kMaxB];
+    LZ_HIP_TRY(hipMemsetAsync(W, 0, sizeof(T) * (size_t)n * b, h->stream));  // X0 = 0
+    const double shift = -iv.sigma;
+    if (iv.method == 0)
+        LZ_TRY(minres_solve(h, n, op.nnz, op.rp, op.col, val, b, shift, Q, W, work, iv.opts, iters, status, resid, est,
+                            info));
+    else if (iv.method == 1)
+        LZ_TRY(cg_solve_with(nullptr)(h, n, op.nnz, op.rp, op.col, val, b, shift, Q, W, work, iv.opts, iters, status,
+                                      resid, est, info));
+    else
+        LZ_TRY(bcg_solve(h, n, op.nnz, op.rp, op.col, val, b, shift, Q, W, work, iv.opts, iters, status, resid, est,
+                         info));
+    lz_inverse_info &o = *iv.info;
+    o.solves += 1, o.passes += info[0], o.n_spmm += info[2];
+    for (int c = 0; c < b; ++c) {
+        o.not_met += status[c] != 0;
+        o.breakdown += status[c] == 2;
+        if (!(resid[c] <= o.worst)) o.worst = resid[c];  // (a NaN residual shows)
+    }
     return LZ_OK;
 }
 
@@ -469,6 +547,8 @@ static int reorth_op(lz_handle *h, int64_t n, int b, const OpSpec &op, const T *
     case OpSpec::Normal:
         LZ_TRY(spmm_rm<T>(h, op.p, op.nnz, op.rp, op.col, val, b, Q, b, n, work, b));
         return spmm_rm<T>(h, n, op.nnz, op.t_rp, op.t_col, (const T *)op.t_val, b, work, b, op.p, W, b);
+    case OpSpec::Inverse:
+        return inverse_op<T>(h, n, b, op, Q, W);
     case OpSpec::Plain:
         break;
     }
@@ -1635,16 +1715,6 @@ static int krylov_entry(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp,
     });
 }
 
-// cg_solve as krylov_entry calls it, for lz_cg_solve (dinv NULL) and lz_pcg_solve: dinv goes in
-// behind shift, in the operator's dtype
-static auto cg_solve_with(const void *dinv)
-{
-    return [dinv](lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, auto *val, int b,
-                  double shift, auto... rest) {
-        return cg_solve(h, n, nnz, rp, col, val, b, shift, (decltype(val))dinv, rest...);
-    };
-}
-
 extern "C" {
 
 const char *lz_last_error(void) { return g_err; }
@@ -2104,7 +2174,7 @@ int lz_normal_apply(lz_handle *h, int64_t n, int64_t p, int64_t nnz, const int64
 // spmm_terms in the dtype
 static int terms_entry(lz_handle *h, int64_t n, bool want_dots, int64_t nnz, const int64_t *rp, const int32_t *col,
                        const void *val, lz_dtype dtype, int b, double a, const void *X, double c, double d, const void *Z,
-                       double e, const void *U, bool four, void *Y, double *dots)
+                       double e, const void *U, bool four, void *Y, double *dots, const double *theta = nullptr)
 {
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(n, nnz, rp, col, val));
@@ -2112,11 +2182,21 @@ static int terms_entry(lz_handle *h, int64_t n, bool want_dots, int64_t nnz, con
     LZ_ARG_CHECK(X && Y && (Z || d == 0.0), "X/Y NULL, or Z NULL with d != 0");
     LZ_ARG_CHECK(U || e == 0.0, "U NULL with e != 0");
     LZ_ARG_CHECK(dots || !want_dots, "dots is NULL");
+    const bool resid = theta != nullptr;  // lz_csr_spmm_resid: Y is its R, and a, c, d, e are not used
     const int64_t nb = n * b;
     const Span z = d == 0.0 ? Span{} : span_of(Z, nb, dtype), u = e == 0.0 ? Span{} : span_of(U, nb, dtype);
     // Z != X is a pointer-equality test, not an overlap rule: a Z that partly overlaps X is accepted
     LZ_ARG_CHECK(apart(span_of(Y, nb, dtype), {span_of(X, nb, dtype), z, u}) && (d == 0.0 || Z != X),
                  "Y must be distinct from X, Z and U, and Z from X (no in-place form)");
+    if (resid) {
+        const Span th{theta, (int64_t)b * 8}, dd{dots, (int64_t)b * 16};
+        LZ_ARG_CHECK(apart(th, {span_of(Y, nb, dtype), dd}) && apart(dd, {span_of(Y, nb, dtype), span_of(X, nb, dtype)}),
+                     "theta must not overlap R or dots, and dots must not overlap R or X");
+        return by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return spmm_resid<T>(h, n, nnz, rp, col, (const T *)val, b, theta, (const T *)X, (T *)Y, dots, ax3_fused());
+        });
+    }
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return spmm_terms<T>(h, n, nnz, rp, col, (const T *)val, b,
@@ -2304,7 +2384,7 @@ int lz_minres_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, con
                         [](auto... a) { return minres_solve(a...); }, kMinresWorkBlocks);
 }
 
-// The eight kept-basis entry points.  r == 0 with B (sigma NULL) is a first cycle, lz_block_lanczos_reorth
+// The ten kept-basis entry points.  r == 0 with B (sigma NULL) is a first cycle, lz_block_lanczos_reorth
 // and its forms; anything else is a resumed one, lz_block_lanczos_reorth_resume and its forms, which
 // needs 1 <= r < m and sigma (its B is NULL).
 static int cycle_entry(lz_handle *h, int64_t n, const OpSpec &op, lz_dtype dtype, int b, int r, int m, int64_t lc,
@@ -2400,6 +2480,45 @@ int lz_block_lanczos_reorth_resume_normal(lz_handle *h, int64_t n, int64_t p, in
 {
     return cycle_entry(h, n, OpSpec::normal(p, nnz, rp, col, val, t_rp, t_col, t_val, work), dtype, b, r, m, lc, nullptr,
                        sigma, q, alpha, beta, V, vstride, W, passes);
+}
+
+int lz_inverse_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                     lz_dtype dtype, int b, const void *X, void *Y, const lz_inverse *inv, void *work,
+                     lz_inverse_info *info)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
+    LZ_ARG_CHECK(X && Y && work, "X/Y/work NULL");
+    return apply_entry(h, n, OpSpec::inverse(nnz, rp, col, val, inv, work, info), dtype, b, X, Y);
+}
+
+int lz_block_lanczos_reorth_inverse(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                                    const void *val, lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q,
+                                    void *alpha, void *beta, void *V, int64_t vstride, void *W, int passes,
+                                    const lz_inverse *inv, void *work, lz_inverse_info *info)
+{
+    return cycle_entry(h, n, OpSpec::inverse(nnz, rp, col, val, inv, work, info), dtype, b, 0, m, lc, B, nullptr, q,
+                       alpha, beta, V, vstride, W, passes);
+}
+
+int lz_block_lanczos_reorth_resume_inverse(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp,
+                                           const int32_t *col, const void *val, lz_dtype dtype, int b, int r, int m,
+                                           int64_t lc, const void *sigma, void *q, void *alpha, void *beta, void *V,
+                                           int64_t vstride, void *W, int passes, const lz_inverse *inv, void *work,
+                                           lz_inverse_info *info)
+{
+    return cycle_entry(h, n, OpSpec::inverse(nnz, rp, col, val, inv, work, info), dtype, b, r, m, lc, nullptr, sigma,
+                       q, alpha, beta, V, vstride, W, passes);
+}
+
+int lz_csr_spmm_resid(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                      lz_dtype dtype, int b, const double *theta, const void *X, void *R, double *dots)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_ARG_CHECK(theta != nullptr, "theta is NULL");
+    return terms_entry(h, n, true, nnz, rp, col, val, dtype, b, 1.0, X, 0.0, 0.0, nullptr, 0.0, nullptr, false, R, dots,
+                       theta);
 }
 
 int lz_csr_spmm_axpby4(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,

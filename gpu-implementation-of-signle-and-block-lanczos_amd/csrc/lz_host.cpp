@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <numeric>
 #include <vector>
 
 namespace {
@@ -569,17 +570,41 @@ int lzh_ritz_pairs(int m, int b, const double *alpha, const double *beta, int ne
     return lzh_ritz_pairs_dense(m, b, T.data(), beta + (size_t)m * b * b, nev, which, theta, S, resid);
 }
 
-int lzh_ritz_pairs_dense(int m, int b, const double *T, const double *bm, int nev, int which, double *theta,
-                         double *S, double *resid)
+// The index maps of the Ritz selections: position i of the selection -> index into the
+// ascending eigenvalues ev[0 .. k).  which 0: ascending, 1: descending.
+static std::vector<int> ritz_order(int k, int which)
+{
+    std::vector<int> o(k);
+    for (int i = 0; i < k; ++i) o[i] = which == 0 ? i : k - 1 - i;
+    return o;
+}
+
+// By |theta| descending, ties by theta ascending (the _mag functions: the wanted Ritz values
+// of a shift-and-invert operator are its largest in magnitude, of both signs)
+static std::vector<int> ritz_order_mag(const std::vector<double> &ev)
+{
+    std::vector<int> o(ev.size());
+    std::iota(o.begin(), o.end(), 0);
+    std::stable_sort(o.begin(), o.end(), [&](int a, int c) {
+        const double fa = std::fabs(ev[a]), fc = std::fabs(ev[c]);
+        return fa != fc ? fa > fc : ev[a] < ev[c];
+    });
+    return o;
+}
+
+// lzh_ritz_pairs_dense and lzh_ritz_pairs_dense_mag: mag picks the index map
+static int ritz_pairs_dense_by(int m, int b, const double *T, const double *bm, int nev, bool mag, int which,
+                               double *theta, double *S, double *resid)
 {
     const int k = m * b;
-    if (m <= 0 || b <= 0 || !T || nev < 1 || nev > k || (which != 0 && which != 1) || !theta || !S ||
+    if (m <= 0 || b <= 0 || !T || nev < 1 || nev > k || (!mag && which != 0 && which != 1) || !theta || !S ||
         (resid && !bm))
         return -1;
     std::vector<double> ev(k), Z((size_t)k * k);
     if (lzh_sym_eig(k, T, ev.data(), Z.data())) return -1;
+    const std::vector<int> order = mag ? ritz_order_mag(ev) : ritz_order(k, which);
     for (int i = 0; i < nev; ++i) {
-        const int src = which == 0 ? i : k - 1 - i;
+        const int src = order[i];
         theta[i] = ev[src];
         for (int r = 0; r < k; ++r) S[(size_t)r * nev + i] = Z[(size_t)r * k + src];
         if (resid) {  // || A x - theta x || = || beta_m s_last || in exact arithmetic
@@ -595,19 +620,32 @@ int lzh_ritz_pairs_dense(int m, int b, const double *T, const double *bm, int ne
     return 0;
 }
 
+int lzh_ritz_pairs_dense(int m, int b, const double *T, const double *bm, int nev, int which, double *theta,
+                         double *S, double *resid)
+{
+    return ritz_pairs_dense_by(m, b, T, bm, nev, false, which, theta, S, resid);
+}
+
+int lzh_ritz_pairs_dense_mag(int m, int b, const double *T, const double *bm, int nev, double *theta, double *S,
+                             double *resid)
+{
+    return ritz_pairs_dense_by(m, b, T, bm, nev, true, 0, theta, S, resid);
+}
+
 // Thick restart (Wu & Simon), block form.  With A P = P T + W E_m^T and
 // T = Z Theta Z^T, keeping the first r b pairs Z_k gives Y = P Z_k with
 // A Y = Y Theta_k + Q_r Sigma, Q_r = W beta_m^-1, Sigma = beta_m Z_k[last b rows, :].
-int lzh_restart_coeffs(int m, int b, int r, const double *T, const double *bm, int which, double *theta_k,
-                       double *Z, double *sigma, double *T_next)
+static int restart_coeffs_by(int m, int b, int r, const double *T, const double *bm, bool mag, int which,
+                             double *theta_k, double *Z, double *sigma, double *T_next)
 {
     const int k = m * b, rb = r * b;
-    if (m <= 0 || b <= 0 || r < 1 || r >= m || !T || !bm || (which != 0 && which != 1) || !theta_k || !Z ||
+    if (m <= 0 || b <= 0 || r < 1 || r >= m || !T || !bm || (!mag && which != 0 && which != 1) || !theta_k || !Z ||
         !sigma || !T_next)
         return -1;
     std::vector<double> ev(k), E((size_t)k * k), Sg((size_t)b * rb);
     if (lzh_sym_eig(k, T, ev.data(), E.data())) return -1;
-    auto src = [&](int i) { return which == 0 ? i : k - 1 - i; };
+    const std::vector<int> order = mag ? ritz_order_mag(ev) : ritz_order(k, which);
+    auto src = [&](int i) { return order[i]; };
     for (int i = 0; i < rb; ++i) theta_k[i] = ev[src(i)];
     // compress layout (r, m, b, b): Z[c][j] takes block j of the panel into output block c
     for (int c = 0; c < r; ++c)
@@ -633,6 +671,18 @@ int lzh_restart_coeffs(int m, int b, int r, const double *T, const double *bm, i
             T_next[(size_t)i * k + rb + p] = Sg[(size_t)p * rb + i];
         }
     return 0;
+}
+
+int lzh_restart_coeffs(int m, int b, int r, const double *T, const double *bm, int which, double *theta_k,
+                       double *Z, double *sigma, double *T_next)
+{
+    return restart_coeffs_by(m, b, r, T, bm, false, which, theta_k, Z, sigma, T_next);
+}
+
+int lzh_restart_coeffs_mag(int m, int b, int r, const double *T, const double *bm, double *theta_k, double *Z,
+                           double *sigma, double *T_next)
+{
+    return restart_coeffs_by(m, b, r, T, bm, true, 0, theta_k, Z, sigma, T_next);
 }
 
 int lzh_gershgorin(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val, double out[2])

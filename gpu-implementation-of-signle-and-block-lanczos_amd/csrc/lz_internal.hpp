@@ -33,6 +33,14 @@ struct SpmmTerms {
 template <typename T>
 int spmm_terms(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
                SpmmTerms<T> t, T *Y, double *dots = nullptr, bool fused = true, bool fused_dot = true);
+// R = A X - X diag(theta) and dots = [R.R | R.X] of the stored R (lz_csr_spmm_resid): theta b
+// device doubles, each rounded to T once.  spmm_terms' shapes leave k_spmm_seg's store
+// (SegStore::ShiftDots, last_kernel | LZ_K_RESID, slabs in h->dots_ws); else, or fused =
+// false: spmm_rm, one row-local kernel, col_dots -- the same bits.  Per element the
+// arithmetic of spmm_terms at a = 1, c = -theta_c, d = 0.
+template <typename T>
+int spmm_resid(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+               const double *theta, const T *X, T *R, double *dots, bool fused = true);
 template <typename T>
 int spmm_cm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
             const T *X, int64_t ldx, int64_t nx, T *Y, int64_t ldy);  // nx: rows of X

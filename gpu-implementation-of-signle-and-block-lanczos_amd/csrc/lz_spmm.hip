@@ -19,6 +19,8 @@
 #include "lz_kernels.hpp"
 #include "lz_internal.hpp"
 
+#include <type_traits>
+
 namespace lz {
 
 template <typename T, int B>
@@ -449,6 +451,19 @@ struct DotAcc {
     }
 };
 
+// The residual store's lane state (ShiftDots, lz_csr_spmm_resid): the running dots and the
+// lane's VEC coefficients -theta_c of its own column piece pc, rounded to T once per store
+// loop (a lane stores the same piece of every row it stores).
+template <typename T, int VEC>
+struct ShiftDotAcc : DotAcc<T, VEC> {
+    T c[VEC];
+    __device__ __forceinline__ void load(const double *__restrict__ cshift, int pc)
+    {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) c[i] = -(T)cshift[pc * VEC + i];
+    }
+};
+
 // The tile's slab of 2 B doubles (yy, then yx) from the 256 lanes' sums: the 8
 // lanes of a wave that hold the same piece by xor shuffles (a fixed tree), the 4
 // waves in order through LDS (red: 8 B doubles).  No atomics: the same bits every
@@ -518,20 +533,26 @@ __device__ __forceinline__ int xcc_id()
 //               differs from run to run, the tiles do not).
 //   Terms4      lz_csr_spmm_axpby4: Terms3 and one more term, e U[row] (U == nullptr when
 //               e == 0; it may be X or Z).
+//   ShiftDots   lz_csr_spmm_resid: Y[row][c] = y[c] - theta_c X[row][c] with theta the b device
+//               doubles at cshift, and Terms3Dots' slabs of the stored rows.  term_piece's
+//               arithmetic at a = 1, c = -theta_c, d = 0: fma(1, y, fma(-theta_c, x, 0)).
 // Only Rows and ColMajor have windowed (WIN) launches; only Rows the diagnostic build's PF.
-enum class SegStore { Rows, ColMajor, Beta2, Terms3, Terms3Dots, Terms4 };
+enum class SegStore { Rows, ColMajor, Beta2, Terms3, Terms3Dots, Terms4, ShiftDots };
 
 constexpr bool seg_terms(SegStore st)
 {
     return st == SegStore::Terms3 || st == SegStore::Terms3Dots || st == SegStore::Terms4;
 }
 
+// the stores that leave a slab of column dots per tile
+constexpr bool seg_dots(SegStore st) { return st == SegStore::Terms3Dots || st == SegStore::ShiftDots; }
+
 // the store's bits of lz_debug_last_kernel's SpMM word
 constexpr int seg_store_bits(SegStore st)
 {
     return (st == SegStore::ColMajor ? LZ_K_YCM : 0) | (st == SegStore::Beta2 ? LZ_K_EPI : 0) |
            (seg_terms(st) ? LZ_K_AX3 : 0) | (st == SegStore::Terms3Dots ? LZ_K_DOT : 0) |
-           (st == SegStore::Terms4 ? LZ_K_AX4 : 0);
+           (st == SegStore::Terms4 ? LZ_K_AX4 : 0) | (st == SegStore::ShiftDots ? LZ_K_RESID : 0);
 }
 
 // What the stores read or write besides Y; a field is dead in the launches of the other stores
@@ -540,8 +561,13 @@ struct SegOperands {
     const T *Wprev = nullptr, *M = nullptr;  // Beta2
     const T *Z = nullptr, *U = nullptr;      // the term stores (U: Terms4)
     T a = T(0), c = T(0), d = T(0), e = T(0);
-    double *dots = nullptr;                  // Terms3Dots: the tiles' slabs
+    double *dots = nullptr;                  // Terms3Dots, ShiftDots: the tiles' slabs
+    const double *cshift = nullptr;          // ShiftDots: theta, B doubles
 };
+
+// a store loop's lane state: the dots (dead without them) and, ShiftDots, the coefficients
+template <SegStore ST, typename T, int VEC>
+using SegAcc = std::conditional_t<ST == SegStore::ShiftDots, ShiftDotAcc<T, VEC>, DotAcc<T, VEC>>;
 
 // A finished 16-B piece (piece pc of row `row`) becomes the piece to store: the one place
 // the store policies differ per piece, for both store loops of k_spmm_seg.  epi, Ms: the
@@ -553,10 +579,15 @@ struct SegOperands {
 template <SegStore ST, typename T, int B, int VEC>
 __device__ __forceinline__ void seg_store_piece(Vec<T, VEC> &y, int64_t row, int pc, const T *X, int64_t ldx,
                                                 const SegOperands<T> &ops, bool epi, const T *Ms,
-                                                DotAcc<T, VEC> &dacc)
+                                                SegAcc<ST, T, VEC> &dacc)
 {
     if constexpr (ST == SegStore::Beta2) {
         if (epi) y = epi_piece<T, B, VEC>(y, ops.Wprev + row * B, Ms, pc);
+    } else if constexpr (ST == SegStore::ShiftDots) {
+        const Vec<T, VEC> x = ldv<T, VEC>(X + row * ldx + pc * VEC);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) y.v[i] = fma(T(1), y.v[i], fma(dacc.c[i], x.v[i], T(0)));
+        dacc.add(y, x);
     } else if constexpr (seg_terms(ST)) {
         [[maybe_unused]] Vec<T, VEC> x;
         y = term_piece<T, VEC, ST == SegStore::Terms4>(y, X + row * ldx + pc * VEC, ops.Z, ops.U, row * B + pc * VEC,
@@ -716,14 +747,15 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
             if constexpr (ST == SegStore::ColMajor) {
                 store_tile_cm<T>(Y, r0, nrows, B, ldy, [&](int r, int c) { return yt[r][c / VEC].v[c % VEC]; });
             } else {
-                [[maybe_unused]] DotAcc<T, VEC> dacc;
-                if constexpr (ST == SegStore::Terms3Dots) dacc.clear();
+                [[maybe_unused]] SegAcc<ST, T, VEC> dacc;
+                if constexpr (seg_dots(ST)) dacc.clear();
+                if constexpr (ST == SegStore::ShiftDots) dacc.load(ops.cshift, tid % LPR);
                 for (int idx = tid; idx < nrows * LPR; idx += 256) {
                     Vec<T, VEC> y = yt[idx / LPR][idx % LPR];
                     seg_store_piece<ST, T, B, VEC>(y, r0 + idx / LPR, idx % LPR, X, ldx, ops, epi, Ms, dacc);
                     stv<T, VEC>(Y + (r0 + idx / LPR) * ldy + (idx % LPR) * VEC, y);
                 }
-                if constexpr (ST == SegStore::Terms3Dots) {  // (red: read here, next written after the next
+                if constexpr (seg_dots(ST)) {  // (red: read here, next written after the next
                                                              // tile's barriers)
                     __shared__ double red[8 * B];
                     dot_slab<T, B, VEC>(dacc, red, ops.dots + (int64_t)longq[2 + qi] * (2 * B));
@@ -938,8 +970,9 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
         store_tile_cm<T>(Y, r0, nrows, B, ldy, [&](int r, int c) { return yt[r][c / VEC].v[c % VEC]; });
         return;
     }
-    [[maybe_unused]] DotAcc<T, VEC> dacc;
-    if constexpr (ST == SegStore::Terms3Dots) dacc.clear();
+    [[maybe_unused]] SegAcc<ST, T, VEC> dacc;
+    if constexpr (seg_dots(ST)) dacc.clear();
+    if constexpr (ST == SegStore::ShiftDots) dacc.load(ops.cshift, tid % LPR);
     for (int idx = tid; idx < nrows * LPR; idx += 256) {
         if (ry + idx / LPR >= n) break;  // (diag only: a Y tile shorter than the tile read)
         T *dst = Y + (ry + idx / LPR) * ldy + (idx % LPR) * VEC;
@@ -954,7 +987,7 @@ __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__re
             stv<T, VEC>(dst, y);
         }
     }
-    if constexpr (ST == SegStore::Terms3Dots) {
+    if constexpr (seg_dots(ST)) {
         __shared__ double red[8 * B];
         dot_slab<T, B, VEC>(dacc, red, ops.dots + (r0 / TR) * (2 * B));
     }
@@ -1958,6 +1991,60 @@ template int spmm_terms<double>(lz_handle *, int64_t, int64_t, const int64_t *, 
                                 SpmmTerms<double>, double *, double *, bool, bool);
 template int spmm_terms<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
                                SpmmTerms<float>, float *, double *, bool, bool);
+
+// The row-local pass of the two-launch residual: R[i][c] = fma(1, R[i][c], fma(-theta_c, X[i][c], 0))
+// over nb = n b contiguous elements (ld = b), the ShiftDots store's arithmetic on the stored
+// SpMM row; the coefficient rounded to T as there.
+template <typename T>
+__global__ __launch_bounds__(256) void k_resid_rows(int64_t nb, int b, const double *__restrict__ theta,
+                                                    const T *__restrict__ X, T *__restrict__ R)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nb; i += (int64_t)gridDim.x * 256) {
+        const T c = -(T)theta[i % b];
+        R[i] = fma(T(1), R[i], fma(c, X[i], T(0)));
+    }
+}
+
+// R = A X - X diag(theta), dots = [R.R | R.X] (lz_csr_spmm_resid).  spmm_terms' conditions for
+// the fused store (ShiftDots, a slab per 48-row tile, folded by dots_fold); else, or fused =
+// false: spmm_rm, k_resid_rows, col_dots -- the same bits.
+template <typename T>
+int spmm_resid(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+               const double *theta, const T *X, T *R, double *dots, bool fused)
+{
+    if (n <= 0) return LZ_OK;
+    const bool rows128 = (int64_t)b * (int64_t)sizeof(T) == 128;
+    const bool buf_ok = n * b * (int64_t)sizeof(T) < (1LL << 31) && n < (1 << 24);
+    const bool al16 = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(R)) & 15) == 0;
+    const char *fz = getenv("LZ_SPMM_FNZ");  // (the fixed-nnz experiment has no fused store)
+    if (fused && rows128 && buf_ok && al16 && !(fz && fz[0] == '1')) {
+        constexpr int B = 128 / (int)sizeof(T);
+        SegOperands<T> ops;
+        ops.cshift = theta;
+        LZ_TRY(dots_reserve(h, n, b));
+        ops.dots = h->dots_ws;
+        const int ev = prof_begin(h, PROF_SPMM);
+        const int rc = by_stage<SegStore::ShiftDots>(seg_stage(n, nnz), false, [&](auto cap, auto win) {
+            return launch_seg<T, B, 48, decltype(cap)::value, decltype(win)::value, SegStore::ShiftDots>(
+                h, n, rp, col, val, X, B, n, R, B, ops, -1, nullptr);
+        });
+        prof_end(h, ev);
+        LZ_TRY(rc);
+        LZ_LAUNCH_CHECK();
+        return dots_fold(h, ceil_div(n, (int64_t)48), b, dots);
+    }
+    LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, X, b, n, R, b));
+    const int64_t nb = n * b;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(nb, (int64_t)256), (int64_t)h->n_cu * 16));
+    hipLaunchKernelGGL((k_resid_rows<T>), dim3(grid), dim3(256), 0, h->stream, nb, b, theta, X, R);
+    LZ_LAUNCH_CHECK();
+    return col_dots<T>(h, n, b, R, X, dots);
+}
+
+template int spmm_resid<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *, int,
+                                const double *, const double *, double *, double *, bool);
+template int spmm_resid<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
+                               const double *, const float *, float *, double *, bool);
 
 // Column-major block (b columns, leading dimension ld) -> row-major (ld = b),
 // kCmRows rows per workgroup through LDS: the column reads and the row writes

@@ -327,6 +327,19 @@ int lz_col_dots(lz_handle *h, int64_t n, int b, lz_dtype dtype, const void *Y, c
 int lz_csr_spmm_axpby_dots(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
                            const void *val, lz_dtype dtype, int b, double a, const void *X, double c, double d,
                            const void *Z, void *Y, double *dots);
+/* The residual block of b Ritz pairs in one pass: R = A X - X diag(theta) and dots[0 .. b) =
+ * sum_i R[i][c]^2, dots[b .. 2b) = sum_i R[i][c] X[i][c] of the stored R.  theta: b doubles
+ * in device memory, each rounded to the dtype once; per element R = fma(1, (A X), fma(-theta_c,
+ * x, 0)), so with every theta_c equal the call is lz_csr_spmm_axpby_dots(a = 1, c = -theta,
+ * d = 0) bit for bit, in R and in dots.  lz_csr_spmm_axpby_dots' shapes, rules and dots;
+ * where that call fuses its store this one does too (lz_debug_last_kernel: the SpMM id |
+ * LZ_K_RESID), every other shape -- and LZ_AX3=0 -- runs lz_csr_spmm, a row-local pass and
+ * lz_col_dots' kernel: the same bits where both apply.  X is read only.  R distinct from X;
+ * theta must not overlap R or dots, nor dots R or X: LZ_E_ARG.  No host synchronisation once
+ * the slab workspace has its size. */
+int lz_csr_spmm_resid(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                      const void *val, lz_dtype dtype, int b, const double *theta, const void *X, void *R,
+                      double *dots);
 /* The raw dots of K Chebyshev steps on Ah = (A - c0) / e, e = (hi - lo) / 2, c0 =
  * (hi + lo) / 2:  t_0 = X0 (read only), t_1 = Ah t_0, t_{k+1} = 2 Ah t_k - t_{k-1},
  * one lz_csr_spmm_axpby_dots each, the coefficients host doubles.
@@ -655,6 +668,47 @@ int lz_block_lanczos_reorth_resume_normal(lz_handle *h, int64_t n, int64_t p, in
                                           int64_t lc, const void *sigma, void *q, void *alpha, void *beta, void *V,
                                           int64_t vstride, void *W, int passes, void *work);
 
+/* ------------------------- shift-and-invert operator (no reference counterpart)
+ * The operator (A - sigma I)^-1 applied through an inner Krylov solve per block.
+ * method: 0 MINRES (any sigma), 1 column CG, 2 block CG (b <= 32) -- the CG methods are the
+ * caller's claim that A - sigma I is positive definite.  opts: the inner solve's
+ * lz_cg_opts (tol > 0). */
+typedef struct {
+    double sigma;
+    int method;
+    lz_cg_opts opts;
+} lz_inverse;
+/* Host memory.  A call accumulates into it; the caller zeroes it.  solves: inner solves
+ * (one per operator application); passes, n_spmm: info[0] and info[2] of the solves;
+ * not_met: columns that ended with status != 0; breakdown: those with status 2; worst: the
+ * largest measured relative residual of any column. */
+typedef struct {
+    int64_t solves, passes, n_spmm, not_met, breakdown;
+    double worst;
+} lz_inverse_info;
+/* Y = (A - sigma I)^-1 X: Y is zeroed on the handle's stream (the start vector), then
+ * lz_minres_solve / lz_cg_solve / lz_bcg_solve's solver runs with shift = -sigma, B = X
+ * (read only).  X, Y: n x b row-major, ld = b; work: 5 n b elements whatever the method;
+ * the three pairwise distinct.  A column that does not meet opts.tol does not fail the
+ * call: info says so.  Synchronises the stream (the inner solve reads its live count). */
+int lz_inverse_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                     const void *val, lz_dtype dtype, int b, const void *X, void *Y, const lz_inverse *inv,
+                     void *work, lz_inverse_info *info);
+/* lz_block_lanczos_reorth / lz_block_lanczos_reorth_resume on (A - sigma I)^-1: every
+ * W = A Q_j of the solve becomes lz_inverse_apply (work as there, on 16 bytes, distinct
+ * from B, W and the panel).  alpha, beta and the projected matrix are those of the inverse:
+ * its eigenvalues are nu = 1 / (lambda - sigma).  Unlike the other kept-basis entry
+ * points, a cycle synchronises the stream once per block step. */
+int lz_block_lanczos_reorth_inverse(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                                    const void *val, lz_dtype dtype, int b, int m, int64_t lc, const void *B, void *q,
+                                    void *alpha, void *beta, void *V, int64_t vstride, void *W, int passes,
+                                    const lz_inverse *inv, void *work, lz_inverse_info *info);
+int lz_block_lanczos_reorth_resume_inverse(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr,
+                                           const int32_t *col, const void *val, lz_dtype dtype, int b, int r, int m,
+                                           int64_t lc, const void *sigma, void *q, void *alpha, void *beta, void *V,
+                                           int64_t vstride, void *W, int passes, const lz_inverse *inv, void *work,
+                                           lz_inverse_info *info);
+
 /* Single-vector Lanczos.  Replaces vector_lanczos<T>(A, b, m, lc, q, alpha,
  * beta, q0, q1, w) (methods/vector_lanczos.hpp:8-67; the correct variant -- the
  * BLAS variant's axpy at :116 is a reference bug not reproduced).  alpha[m],
@@ -723,7 +777,7 @@ int lz_debug_last_wf(lz_handle *h, int out[2]);
  * b = 32 fp32 or generic-b solve), out[1]: its last Gram / tall-skinny-product
  * launch (lz_gram, lz_sym_cross_gram, lz_tsmm and the solves that call them);
  * 0: none yet.  SpMM ids: a kernel in the low byte, or-ed with the LZ_K_WIN /
- * LZ_K_YCM / LZ_K_EPI / LZ_K_AX3 / LZ_K_DOT / LZ_K_AX4 flags; LZ_K_SPMV carries its lanes per row in bits 16+. */
+ * LZ_K_YCM / LZ_K_EPI / LZ_K_AX3 / LZ_K_DOT / LZ_K_AX4 / LZ_K_RESID flags; LZ_K_SPMV carries its lanes per row in bits 16+. */
 enum {
     LZ_K_SEG768 = 1,    /* nnz-split tiles, 768-entry stage (128-B rows, <= 13 nnz/row) */
     LZ_K_SEG1536 = 2,   /* ... 1536-entry stage (> 13 nnz/row) */
@@ -740,6 +794,7 @@ enum {
     LZ_K_AX3 = 0x800,   /* lz_csr_spmm_axpby's fused three-term store a A X + c X + d Z */
     LZ_K_DOT = 0x1000,  /* lz_csr_spmm_axpby_dots: the column dots leave the fused store too */
     LZ_K_AX4 = 0x2000,  /* lz_csr_spmm_axpby4: the fused store's fourth term e U (with LZ_K_AX3) */
+    LZ_K_RESID = 0x4000, /* lz_csr_spmm_resid: the fused residual store A X - X diag(theta) with its dots */
     LZ_K_GRAM16 = 1,    /* dense ids: b = 16 MFMA Gram (fp64 and fp32) */
     LZ_K_GRAM32F = 2,   /* b = 32 fp32 MFMA Gram */
     LZ_K_GRAM_GEN = 3,  /* any b, any pitch */

@@ -121,6 +121,16 @@ int lzh_ritz_pairs_dense(int m, int b, const double *T, const double *beta_m, in
 int lzh_restart_coeffs(int m, int b, int r, const double *T, const double *beta_m, int which,
                        double *theta_k, double *Z, double *sigma, double *T_next);
 int lzh_restart_fill(int r, int m, int b, const double *alpha, const double *beta, double *T_next);
+/* lzh_ritz_pairs_dense and lzh_restart_coeffs with the largest-magnitude selection, for a
+ * solve on a shift-and-invert operator (A - sigma I)^-1, whose wanted Ritz values
+ * nu = 1 / (lambda - sigma) are the largest in magnitude, of both signs when sigma lies
+ * inside the spectrum.  Order: |theta| descending, ties by theta ascending (so -t comes
+ * before +t).  No `which`; every other argument, output and formula as above.  (The two
+ * functions above keep rejecting which = 2 and 3.) */
+int lzh_ritz_pairs_dense_mag(int m, int b, const double *T, const double *beta_m, int nev, double *theta,
+                             double *S, double *resid);
+int lzh_restart_coeffs_mag(int m, int b, int r, const double *T, const double *beta_m, double *theta_k,
+                           double *Z, double *sigma, double *T_next);
 /* The Gershgorin enclosure of a square CSR operator's spectrum (symmetric: real):
  * out[0] = min_i (a_ii - R_i), out[1] = max_i (a_ii + R_i), R_i the sum of
  * |a_ij| over the row's off-diagonal entries; an empty row's disc is [0, 0].

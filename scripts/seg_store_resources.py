@@ -7,13 +7,16 @@
 
 Prints one table per file, keyed by (T, CAP, WIN, MODE, store), and compares them: the same
 instantiations; equal LDS and occupancy; no scratch, no spills; VGPRs no higher.  Exit 1 otherwise.
+Instantiations of a store in ADDED that only the new file has are a new store's: listed, and held
+to no scratch and no spills.
 Both spellings of the store are read: the six booleans (YCM, EPI, PF, AX3, DOT, AX4) and the
 SegStore enumerator.
 """
 import re
 import sys
 
-STORES = ["Rows", "ColMajor", "Beta2", "Terms3", "Terms3Dots", "Terms4"]
+STORES = ["Rows", "ColMajor", "Beta2", "Terms3", "Terms3Dots", "Terms4", "ShiftDots"]
+ADDED = {"ShiftDots"}  # stores younger than the six: a parent file need not have them
 BOOLS = {(0, 0, 0, 0, 0): "Rows", (1, 0, 0, 0, 0): "ColMajor", (0, 1, 0, 0, 0): "Beta2", (0, 0, 1, 0, 0): "Terms3",
          (0, 0, 1, 1, 0): "Terms3Dots", (0, 0, 1, 0, 1): "Terms4"}
 HEAD = r"k_spmm_segI([fd])Li\d+ELi\d+ELi(\d+)ELb([01])ELi([01])E"
@@ -73,6 +76,12 @@ def main():
     table("parent", old)
     table("new", new)
     bad = []
+    added = {k for k in set(new) - set(old) if k[4] in ADDED}
+    for k in sorted(added):
+        n = new.pop(k)
+        print(f"# added {k}: VGPR {n['vgpr']}, SGPR {n['sgpr']}, LDS {n['lds']}, occupancy {n['occ']}")
+        if n["scratch"] or n["sspill"] or n["vspill"]:
+            bad.append(f"{k}: scratch or spills {n}")
     if set(old) != set(new):
         bad.append(f"instantiations differ: only parent {sorted(set(old) - set(new))}, only new {sorted(set(new) - set(old))}")
     for k in sorted(set(old) & set(new)):
