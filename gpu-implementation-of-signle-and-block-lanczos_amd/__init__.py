@@ -75,6 +75,14 @@ LZ_K_BCG16, LZ_K_BCG32F, LZ_K_BCG_GEN = 13, 14, 15  # lz_debug_last_kernel's den
 BCG_NONE, BCG_CONVERGED, BCG_SPENT, BCG_RANK, BCG_NOT_PD = 0, 1, 2, 3, 4
 
 
+# the thick-restart drivers' rank test: a fresh beta block whose rank ratio (rank_ratios)
+# is below delta -- or not finite -- is refused as rank deficient.  Per precision of the solve, for the
+# start block's beta_0 (sigma_min / sigma_max) and for the blocks of the steps (sigma_min / max|theta|):
+# the geometric means of the smallest healthy and the largest deficient ratio measured on the device
+RANK_DELTA_START_F64, RANK_DELTA_START_F32 = 1.4e-5, 1.0e-5
+RANK_DELTA_STEP_F64, RANK_DELTA_STEP_F32 = 2.4e-11, 2.5e-7
+
+
 def bcg_guard(b: int, eps: float) -> float:
     """The block solver's rank guard: lambda_min > bcg_guard * lambda_max (lzh_bcg_guard)."""
     return max(1e-10, 64.0 * b * eps)
@@ -874,9 +882,35 @@ def _pack_chunks(S: np.ndarray, m: int, b: int) -> np.ndarray:
     return Sp
 
 
-def _restart_sizes(who: str, count: str, nev: int, b: int, m: Optional[int], keep: Optional[int]):
+def rank_ratios(beta: np.ndarray, j0: int, T: np.ndarray) -> np.ndarray:
+    """The rank ratio of the fresh blocks beta[j0:] ((m + 1, b, b), host fp64) of a cycle:
+    sigma_min(beta_j) / max|theta(T)|, T the cycle's projected matrix; for the start block's
+    beta_0, which T does not hold, sigma_min / sigma_max.  NaN where beta_j (or, past beta_0,
+    T) is not finite or the denominator is zero.  A block W = Q_j beta_j of full rank whose
+    columns are as long as the operator is wide has a ratio of order 1 / b; a singular W^T W
+    gives one near sqrt(eps) or below (its computed zero eigenvalue over the largest)."""
+    out = np.full(len(beta) - j0, np.nan)
+    scale = None
+    for i, bj in enumerate(beta[j0:]):
+        if not np.isfinite(bj).all():
+            continue
+        sv = np.linalg.svd(bj, compute_uv=False)
+        if j0 + i == 0:
+            den = sv[0]
+        else:
+            if scale is None:
+                scale = float(np.abs(np.linalg.eigvalsh(0.5 * (T + T.T))).max()) if np.isfinite(T).all() else np.nan
+            den = scale
+        if den > 0:  # (False for NaN)
+            out[i] = sv[-1] / den
+    return out
+
+
+def _restart_sizes(who: str, count: str, nev: int, b: int, m: Optional[int], keep: Optional[int],
+                   n: Optional[int] = None):
     """(m, keep) of a thick-restart solve for nev pairs, with the defaults and limits of
-    eigsh's docstring; who and count name the caller and its nev in the errors."""
+    eigsh's docstring; who and count name the caller and its nev in the errors.  n: the
+    Lanczos dimension; a panel of m * b orthonormal columns needs m * b <= n."""
     want = -(-(nev + b) // b)  # the smallest keep with keep * b >= nev + b
     if m is None:
         m = min(PANEL_MAX_BLOCKS, max(4, 2 * want))
@@ -887,6 +921,9 @@ def _restart_sizes(who: str, count: str, nev: int, b: int, m: Optional[int], kee
         raise LanczosError(f"{who}: keep = {r} >= m = {m}")
     if r > PANEL_MAX_KEEP or m > PANEL_MAX_BLOCKS or r < 1:
         raise LanczosError(f"{who}: 1 <= keep <= {PANEL_MAX_KEEP} and m <= {PANEL_MAX_BLOCKS}")
+    if n is not None and m * b > n:
+        raise LanczosError(f"{who}: m * b = {m * b} > n = {n}: the panel cannot hold more orthonormal columns "
+                           f"than the operator has rows")
     return m, r
 
 
@@ -898,14 +935,16 @@ class _Restart:
     caller set are passed on) and the counters.  which: "smallest", "largest" or, on an
     inverse, "magnitude".
 
-        first(B)         block_lanczos_reorth from B, copy back, Assemble_T
+        first(B)         block_lanczos_reorth from B, copy back, Assemble_T, check_rank
         ritz(which)      all m*b Ritz pairs of T: theta, S, resid, max|theta|
         compress(which)  restart_coeffs, then panel_compress onto the keep*b kept pairs
         resume()         row lc of the kept blocks into q, block_lanczos_reorth_resume,
-                         copy back, restart_fill
+                         copy back, restart_fill, check_rank
         pack(S, nev)     panel_compress onto the Ritz vectors of S[:, :nev]; returns their blocks
 
-    One copy-back each of q, al and be per cycle; the callers keep the stop test."""
+    One copy-back each of q, al and be per cycle; the callers keep the stop test.  check_rank
+    refuses a cycle with a rank-deficient fresh block (LanczosError); ran, when set, is called
+    after the cycle's device call and before that test."""
 
     def __init__(self, h: "Handle", A, n: int, b: int, m: int, r: int, lc: int, passes: int, like, **op):
         torch = _torch()
@@ -913,6 +952,9 @@ class _Restart:
         self.lc, self.passes, self.op = lc, passes, op
         self.kw = kw = dict(dtype=like.dtype, device=like.device)
         self.npdt = np.float64 if like.dtype == torch.float64 else np.float32
+        self.delta = (RANK_DELTA_START_F64, RANK_DELTA_STEP_F64) if like.dtype == torch.float64 \
+            else (RANK_DELTA_START_F32, RANK_DELTA_STEP_F32)  # (beta_0, every later block)
+        self.ran = None  # called after every cycle's device call, before its rank test
         self.vstride = _panel_stride(n, b, like)
         self.V = torch.zeros(m * self.vstride, **kw)
         self.W = torch.empty(n, b, **kw)
@@ -936,6 +978,22 @@ class _Restart:
         self.cycles = 1
         self.alpha, self.beta = _f64(self.al), _f64(self.be)
         self.T = Assemble_T(self.m, self.b, self.alpha, self.beta[:self.m])
+        if self.ran:
+            self.ran()
+        self.check_rank(0)
+
+    def check_rank(self, j0: int):
+        """Refuse a cycle whose fresh blocks beta[j0:] are rank deficient (rank_ratios below
+        delta, or not finite): beta^-1 = 1 / sqrt|lambda| then left the panel unnormalised and
+        not orthogonal, and neither T nor the residual estimate beta_m S[-b:] means anything.
+        Host work on the copies first() and resume() already made."""
+        for i, x in enumerate(rank_ratios(self.beta, j0, self.T)):
+            j = j0 + i
+            delta = self.delta[min(j, 1)]
+            if not x >= delta:  # (NaN fails)
+                where = "the start block" if j == 0 else f"the block of cycle {self.cycles}, step {j}"
+                raise LanczosError(f"{where} is rank deficient (rank ratio {x:.1e} < {delta:.1e}): its columns "
+                                   f"are dependent to working precision, or the Krylov space is exhausted")
 
     def ritz(self, which: str):
         theta, S, resid = ritz_pairs_dense(self.m, self.b, self.T, self.beta[self.m], self.m * self.b, which)
@@ -956,6 +1014,9 @@ class _Restart:
         restart_fill(r, m, b, self.alpha, self.beta, self.T)
         self.steps += m - r
         self.cycles += 1
+        if self.ran:
+            self.ran()
+        self.check_rank(r)
 
     def pack(self, S: np.ndarray, nev: int) -> int:
         Zx = _pack_chunks(S[:, :nev], self.m, self.b)
@@ -1717,6 +1778,15 @@ class Handle:
         cycles, n_spmm, converged, history (the largest wanted residual of each cycle), scale
         (the last cycle's max|theta|).
 
+        Limits, in every form: m * b <= n (refused with the other arguments).  A rank-deficient
+        block -- a start block with a zero or (nearly) duplicated column, an operator of rank
+        below m * b - b, a start block inside an invariant subspace, an exhausted Krylov space --
+        raises LanczosError("... is rank deficient ...") naming the start block or the cycle and
+        step (rank_ratios against RANK_DELTA_*; host work on the beta blocks already copied back):
+        beta^-1 = 1 / sqrt|lambda| would leave the panel neither normalised nor orthogonal.
+        Only LanczosError leaves the solve.  Repeated eigenvalues up to multiplicity b come out
+        complete; one of multiplicity above b is not guaranteed to.
+
         filter_degree = d (1 .. 256): the same restart on p(A), a degree-d scaled Chebyshev
         filter, for ends that converge slowly (the smallest eigenvalues of Laplacian-like
         operators).  One unfiltered solve of m blocks gives the Ritz values theta of A (and
@@ -1764,7 +1834,7 @@ class Handle:
         _which(which)
         if filter_degree is not None and not 1 <= int(filter_degree) <= 256:
             raise LanczosError("eigsh: 1 <= filter_degree <= 256")
-        m, r = _restart_sizes("eigsh", "nev", nev, b, m, keep)
+        m, r = _restart_sizes("eigsh", "nev", nev, b, m, keep, A.n)
         d = _Restart(self, A, A.n, b, m, r, lc, passes, A.val)
         B = d.start_block(B)
         if filter_degree is not None:
@@ -1792,7 +1862,7 @@ class Handle:
             raise LanczosError('eigsh: inner is "minres", "columns" or "block"')
         if not np.isfinite(sigma):
             raise LanczosError("eigsh: sigma must be finite")
-        m, r = _restart_sizes("eigsh", "nev", nev, b, m, keep)
+        m, r = _restart_sizes("eigsh", "nev", nev, b, m, keep, A.n)
         n = A.n
         eps = float(np.finfo(np.float64 if A.val.dtype == torch.float64 else np.float32).eps)
         if inner_tol is None:
@@ -1834,8 +1904,8 @@ class Handle:
             res = np.sqrt(np.maximum(dots.cpu().numpy()[:, 0, :].reshape(rb), 0.0))
             return lam, res, Cm
 
+        d.ran = ran  # (a broken-down inner solve leaves NaN blocks: name it before the rank test does)
         d.first(d.start_block(B))
-        ran()
         history = []
         while True:
             d.compress("magnitude")
@@ -1846,7 +1916,6 @@ class Handle:
             if converged or d.cycles >= max_cycles:
                 break
             d.resume()
-            ran()
         Zx = _pack_chunks(Cm[:, sel], r, b)
         self.panel_compress(V, vstride, r, len(Zx), d._dev(Zx), n=n)
         return dict(theta=lam[sel], resid=res[sel], V=V, vstride=vstride, cycles=d.cycles, n_steps=d.steps,
@@ -1879,9 +1948,13 @@ class Handle:
         (the left / right singular vectors as block-major panels of ceil(k / b) blocks of R / C
         rows, the last zero-padded); resid[k] measured; est[k]; cycles; n_spmm (every SpMM: two
         per Lanczos step, two per block of the finish); converged; history (the largest wanted
-        est_i / (sigma_max * max(sigma_i, sqrt(eps) sigma_max)) of each cycle); At."""
+        est_i / (sigma_max * max(sigma_i, sqrt(eps) sigma_max)) of each cycle); At.
+
+        Limits as eigsh's, on G: m * b <= n = min(R, C); a rank-deficient block (a deficient start
+        block, an A of rank below m * b - b) raises LanczosError("... is rank deficient ...");
+        a singular value of multiplicity above b is not guaranteed to come out complete."""
         torch = _torch()
-        m, r = _restart_sizes("svds", "k", k, b, m, keep)
+        m, r = _restart_sizes("svds", "k", k, b, m, keep, min(A.n, A.n_cols))
         At = A.transpose(self)
         P, Pt = (A, At) if A.n_cols <= A.n else (At, A)
         n, p = P.n_cols, P.n
@@ -2048,7 +2121,8 @@ class Handle:
         n_steps + 2 * keep * cycles (every SpMM: degree per step, 2 keep per cycle's check),
         converged, full, history (per cycle, the largest residual among the pairs that meet
         the window; 0 when none does), scale, filter = (degree, lo, hi).  Device memory that
-        scales with n: the panel, W, B and 2 n block elements of workspace."""
+        scales with n: the panel, W, B and 2 n block elements of workspace.  m * block <= n, and a
+        rank-deficient block raises LanczosError, as in eigsh."""
         torch = _torch()
         a, b = float(a), float(b)
         if not a < b:
@@ -2066,7 +2140,8 @@ class Handle:
         degree = int(degree)
         if keep is None:
             keep = 4 if m is None else max(1, min(4, m - 1))
-        m, r = _restart_sizes("eigsh_interval", "(keep - 1) * block", max((keep - 1) * block, 1), block, m, keep)
+        m, r = _restart_sizes("eigsh_interval", "(keep - 1) * block", max((keep - 1) * block, 1), block, m, keep,
+                               A.n)
         n, bs = A.n, block
         scale = max(abs(lo), abs(hi))
         gamma = cheb_window(degree, lo, hi, a, b)

@@ -274,6 +274,56 @@ def test_sqrtm_known_answer(lz, handle, torch_cuda, golden):
     assert np.allclose(binv.cpu().numpy(), golden["ka4_inv_sqrtm"], rtol=0, atol=1e-12)
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("b", [4, 5, 16, 32])
+def test_sqrtm_singular_gram(lz, orc, handle, torch_cuda, monkeypatch, b, dtype):
+    """G = B^T B of a block with a zero column, a duplicated column and of rank 1 (integer
+    entries: the three Grams are exactly singular in both precisions), on both routes
+    (LZ_SQRTM_NS unset and 0).  beta is finite, beta beta is G: with E = beta - s, s the oracle's
+    eigendecomposition square root, |E| <= floor max|s| is the existing sqrtm tests' bound (floor
+    1e-12 / 2e-6) and beta beta - s s = s E + E s + E E gives 2 b floor |G|_2 to first order --
+    stated on the squares because sqrt|lambda| of a zero eigenvalue computed as eps lambda_max is
+    sqrt(eps lambda_max), not small.  That is also the singular value the drivers' rank test
+    (rank_ratios) rests on: sigma_min(beta) <= sqrt(64 b eps) sigma_max(beta), 64 b eps the
+    relative size a zero eigenvalue of G is computed to.  beta^-1 = 1 / sqrt|lambda| is the
+    reference's definition and is not asserted."""
+    torch = torch_cuda
+    eps = EPS[dtype]
+    rng = np.random.default_rng(40 + b)
+    n = 4 * b + 3
+    B0 = rng.integers(-2, 3, (n, b)).astype(np.float64)
+    zero, dup = B0.copy(), B0.copy()
+    zero[:, 2] = 0
+    dup[:, 1] = B0[:, 3]
+    rank1 = np.outer(B0[:, 0] + (B0[:, 0] == 0), np.arange(1, b + 1))
+    tdt = torch.float64 if dtype == np.float64 else torch.float32
+    floor = 1e-12 if dtype == np.float64 else 2e-6
+    for name, Bh in [("zero column", zero), ("duplicated column", dup), ("rank 1", rank1)]:
+        G64 = Bh.T @ Bh
+        G = G64.astype(dtype)
+        assert np.array_equal(G.astype(np.float64), G64) and np.linalg.matrix_rank(G64) < b
+        with np.errstate(all="ignore"):
+            s, _ = orc.sqrtm_pair(G64)
+        norm2 = np.linalg.norm(G64, 2)
+        for ns in (None, "0"):
+            if ns is None:
+                monkeypatch.delenv("LZ_SQRTM_NS", raising=False)
+            else:
+                monkeypatch.setenv("LZ_SQRTM_NS", ns)
+            beta = torch.empty(b, b, dtype=tdt, device="cuda")
+            binv = torch.empty_like(beta)
+            handle.sqrtm(torch.from_numpy(G).cuda(), beta, binv)
+            bh = beta.cpu().numpy().astype(np.float64)
+            assert np.isfinite(bh).all(), (name, ns)
+            err = np.abs(bh @ bh - s @ s).max()
+            sv = np.linalg.svd(bh, compute_uv=False)
+            print(f"sqrtm {name} b={b} {np.dtype(dtype).name} NS={ns}: |beta beta - G| {err:.3e} (bound "
+                  f"{2 * b * floor * norm2:.3e}), sigma_min / sigma_max {sv[-1] / sv[0]:.3e} (bound "
+                  f"{np.sqrt(64 * b * eps):.3e})")
+            assert err <= 2 * b * floor * norm2, (name, ns)
+            assert sv[-1] <= np.sqrt(64 * b * eps) * sv[0], (name, ns)
+
+
 def test_copy_row_exact(lz, handle, torch_cuda):
     torch = torch_cuda
     Q = torch.arange(1000 * 16, dtype=torch.float64, device="cuda").reshape(1000, 16)

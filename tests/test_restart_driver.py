@@ -42,8 +42,14 @@ def make_standin(lz):
             return DenseCsr.from_dense(np.ascontiguousarray(self.dense.T))
 
     def sqrtm_pair(G):
+        """As the device: beta = U sqrt|w| U^T, beta^-1 = U / sqrt|w| U^T (1 / 0 = inf, no
+        exception), and a Gram that is not finite gives NaN blocks."""
+        if not np.isfinite(G).all():
+            return np.full_like(G, np.nan), np.full_like(G, np.nan)
         w, U = np.linalg.eigh(0.5 * (G + G.T))
-        return (U * np.sqrt(w)) @ U.T, (U / np.sqrt(w)) @ U.T
+        w = np.abs(w)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (U * np.sqrt(w)) @ U.T, (U / np.sqrt(w)) @ U.T
 
     def operator(A, filt, normal):
         """Q -> A Q, p(A) Q (the three-term recurrence of cheb_apply) or Pt (P Q)."""
