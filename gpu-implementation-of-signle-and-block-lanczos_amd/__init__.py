@@ -62,6 +62,9 @@ CG_MET, CG_SPENT, CG_NOT_PD = 0, 1, 2  # Handle.solve's status per column
 # lz_pcg_solve's work is PCG_WORK_BLOCKS blocks of n b elements; lz_csr_jacobi (csrc/lz_internal.hpp
 # kJacobi*) gives a row JACOBI_LANES lanes, a workgroup pass JACOBI_ROWS rows
 PCG_WORK_BLOCKS, JACOBI_LANES, JACOBI_ROWS = 5, 8, 32
+# lz_pcg_cheb_solve's work is CHEB_PCG_WORK_BLOCKS blocks of n b elements, [R | W | P | S | Z | T0 | T1];
+# CHEB_PRECOND_MAX_DEGREE: the Chebyshev preconditioner's highest degree (csrc/lz_internal.hpp kCheb*)
+CHEB_PCG_WORK_BLOCKS, CHEB_PRECOND_MAX_DEGREE = 7, 64
 # lz_minres_solve's work is MINRES_WORK_BLOCKS blocks of n b elements (csrc/lz_internal.hpp kMinresWorkBlocks);
 # lz_minres_update's coef has MINRES_COEFS rows of b; MINRES_BREAKDOWN: its status 2 (LZ_MINRES_BREAKDOWN)
 MINRES_WORK_BLOCKS, MINRES_COEFS, MINRES_BREAKDOWN = 5, 7, 2
@@ -157,6 +160,13 @@ HIP_SYMBOLS = [
     ("lz_csr_jacobi", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_dbl, _c_vp, _c_vp]),
     ("lz_pcg_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp,
                               _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lz_csr_spmm_axpby4_dots", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp,
+                                         _c_dbl, _c_dbl, _c_vp, _c_dbl, _c_vp, _c_vp, _c_vp]),
+    ("lz_cgz_update", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lz_cheb_precond_apply", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp,
+                                       _c_vp, _c_vp, _c_vp]),
+    ("lz_pcg_cheb_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp,
+                                   _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_bcg_update", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_bcg_direction", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_bcg_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp,
@@ -257,6 +267,8 @@ HOST_SYMBOLS = [
                                 _c_vp, _c_vp]),
     ("lzh_pcg_scalars", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                  _c_vp, _c_vp, _c_vp]),
+    ("lzh_cheb_precond_coeffs", _c_int, [_c_int, _c_dbl, _c_dbl, _c_vp]),
+    ("lzh_cheb_precond_lo", _c_dbl, [_c_int, _c_dbl]),
     ("lzh_minres_start", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_minres_scalars", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lzh_bcg_start", _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -433,6 +445,21 @@ def gershgorin(A: CsrHost):
     return float(out[0]), float(out[1])
 
 
+def cheb_precond_lo(degree: int, hi: float) -> float:
+    """The Chebyshev preconditioner's default lower end, hi / (4 (degree + 1)^2) (lzh_cheb_precond_lo)."""
+    return float(host_lib().lzh_cheb_precond_lo(int(degree), float(hi)))
+
+
+def cheb_precond_coeffs(degree: int, lo: float, hi: float) -> np.ndarray:
+    """(degree, 4) fp64: row j - 1 = the (a, c, d, e) of step j of the Chebyshev polynomial
+    preconditioner on [lo, hi] as lz_cheb_precond_apply applies it (lzh_cheb_precond_coeffs): step 1
+    is a three-term step on r, step 2 has d = 0 (its z_1 = r / theta travels in e)."""
+    out = np.empty((max(int(degree), 1), 4))
+    if host_lib().lzh_cheb_precond_coeffs(int(degree), float(lo), float(hi), _p(out)):
+        raise LanczosError("cheb_precond_coeffs: 1 <= degree <= 64 and 0 < lo < hi, finite")
+    return out
+
+
 def kpm_moments(dots: np.ndarray) -> np.ndarray:
     """(K+1, 2, b) raw dots of Handle.cheb_moments -> (2K+1, b) Chebyshev moments, column c those
     of probe c (lzh_kpm_moments: mu_2k = 2 <t_k,t_k> - mu_0, mu_2k+1 = 2 <t_k+1,t_k> - mu_1)."""
@@ -536,6 +563,33 @@ class ChebFilter(ctypes.Structure):
 class CgOpts(ctypes.Structure):
     """lz_cg_opts (include/lz_hip.h): check_every 0 = the library's default."""
     _fields_ = [("tol", _c_dbl), ("max_iter", _c_int), ("check_every", _c_int), ("max_restarts", _c_int)]
+
+
+class ChebPrecondSpec(ctypes.Structure):
+    """lz_cheb_precond (include/lz_hip.h): the Chebyshev polynomial preconditioner of `degree` on [lo, hi]."""
+    _fields_ = [("degree", _c_int), ("lo", _c_dbl), ("hi", _c_dbl)]
+
+
+@dataclass
+class ChebPrecond:
+    """Handle.solve(precond=ChebPrecond(...)): z = q(A + shift I) r, the Chebyshev semi-iteration's
+    polynomial of `degree` SpMMs on [lo, hi].  hi None: the Gershgorin upper bound of A + shift I;
+    lo None: hi / (4 (degree + 1)^2)."""
+    degree: int = 8
+    lo: Optional[float] = None
+    hi: Optional[float] = None
+
+
+def _cheb_precond(pc) -> ChebPrecondSpec:
+    """A ChebPrecondSpec from a ChebPrecond with both ends given or a (degree, lo, hi) tuple, checked."""
+    degree, lo, hi = (pc.degree, pc.lo, pc.hi) if isinstance(pc, (ChebPrecond, ChebPrecondSpec)) else pc
+    if lo is None or hi is None:
+        raise LanczosError("Chebyshev preconditioner: lo and hi are needed here")
+    if int(degree) != degree or not 1 <= degree <= CHEB_PRECOND_MAX_DEGREE:
+        raise LanczosError(f"Chebyshev preconditioner: 1 <= degree <= {CHEB_PRECOND_MAX_DEGREE}")
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo < hi):
+        raise LanczosError(f"Chebyshev preconditioner: 0 < lo < hi, finite (got {lo}, {hi})")
+    return ChebPrecondSpec(int(degree), float(lo), float(hi))
 
 
 class Inverse(ctypes.Structure):
@@ -1095,6 +1149,16 @@ class Handle:
                                          a, _ptr(X), c, d, _ptr(Z), e, _ptr(U), _ptr(Y)), "lz_csr_spmm_axpby4")
         return Y
 
+    def spmm_axpby4_dots(self, A: CsrDevice, a: float, X, c: float, d: float, Z, e: float, U, Y, dots=None):
+        """spmm_axpby4 with U required (e != 0), and the column dots of the stored Y with itself and
+        with U as col_dots(Y, U) returns them (lz_csr_spmm_axpby4_dots); returns (Y, dots)."""
+        n, b = self._blocks("spmm_axpby4_dots", A, X, Y, Z, U)
+        dots = self._dots("spmm_axpby4_dots", dots, 1, b, Y)
+        _check(self.L.lz_csr_spmm_axpby4_dots(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                              a, _ptr(X), c, d, _ptr(Z), e, _ptr(U), _ptr(Y), _ptr(dots)),
+               "lz_csr_spmm_axpby4_dots")
+        return Y, dots.view(2, b)
+
     def _dots(self, what: str, dots, rows: int, b: int, like):
         """The (rows, 2, b) fp64 device tensor the dots land in (allocated when None)."""
         torch = _torch()
@@ -1202,6 +1266,34 @@ class Handle:
         _check(self.L.lz_pcg_update(self.ptr, n, b, _dt(R), _ptr(coef), _ptr(dinv), _ptr(R), _ptr(W), _ptr(P),
                                     _ptr(S), _ptr(X), _ptr(Z), _ptr(dots)), "lz_pcg_update")
         return dots
+
+    def cgz_update(self, coef, R, W, P, S, X, Z, rr=None):
+        """cg_update with z0 read from the block Z (lz_cgz_update): P = Z + beta P, S = W + beta S, X +=
+        alpha P, R -= alpha S under cg_update's zero-coefficient rules, and rr[c] = the column sums of
+        the new R * R.  Z and W are read only and nothing is written to Z; R, W, P, S, X, Z: (n, b)
+        contiguous, of one dtype, all six pairwise distinct.  Returns rr (b fp64 on the device)."""
+        n, b = R.shape
+        rr = self._cg_update_args("cgz_update", "R, W, P, S, X, Z", (R, W, P, S, X, Z), coef, "rr", rr, 1)
+        _check(self.L.lz_cgz_update(self.ptr, n, b, _dt(R), _ptr(coef), _ptr(R), _ptr(W), _ptr(P), _ptr(S), _ptr(X),
+                                    _ptr(Z), _ptr(rr)), "lz_cgz_update")
+        return rr
+
+    def cheb_precond_apply(self, A: CsrDevice, precond, R, Z, work=None, shift: float = 0.0, dots=None):
+        """Z = q(A + shift I) R, q the Chebyshev polynomial preconditioner `precond` (a ChebPrecond
+        with lo and hi given, or (degree, lo, hi)), in exactly degree SpMMs (lz_cheb_precond_apply).
+        work: flat, 2*n*b elements (allocated when None); R is only read.  Returns (Z, dots): dots[0] =
+        the column sums of Z * Z, dots[1] = those of Z * R, of the stored Z."""
+        torch = _torch()
+        n, b = self._blocks("cheb_precond_apply", A, R, Z)
+        pc = _cheb_precond(precond)
+        if work is None:
+            work = torch.empty(2 * n * b, dtype=R.dtype, device=R.device)
+        self._work("cheb_precond_apply", work, n, b, R)
+        dots = self._dots("cheb_precond_apply", dots, 1, b, Z)
+        _check(self.L.lz_cheb_precond_apply(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                            float(shift), ctypes.addressof(pc), _ptr(R), _ptr(Z), _ptr(work),
+                                            _ptr(dots)), "lz_cheb_precond_apply")
+        return Z, dots.view(2, b)
 
     def jacobi(self, A: CsrDevice, shift: float = 0.0):
         """The Jacobi preconditioner of A + shift I (lz_csr_jacobi): dinv[i] = 1 / (a_ii + shift) in
@@ -1315,6 +1407,18 @@ class Handle:
         with a near-constant diagonal -- Jacobi gains nothing: the same iterations, each a little
         slower.  work is then 5 n b elements (PCG_WORK_BLOCKS), and the device holds 7 blocks and dinv.
 
+        precond=ChebPrecond(degree=8, lo=None, hi=None), or "chebyshev" for ChebPrecond()
+        (lz_pcg_cheb_solve; method="columns" only): the Chebyshev polynomial preconditioner z = q(M) r
+        of that degree on [lo, hi], degree SpMMs per application.  hi=None: gershgorin(A)[1] + shift (one
+        copy of the CSR arrays to the host), a guaranteed upper bound, with which q(M) is positive
+        definite whatever lo is; lo=None: hi / (4 (degree + 1)^2) (cheb_precond_lo).  It pays where
+        Jacobi cannot -- a constant diagonal, the grid Laplacians and banded operators: about degree +
+        1 times fewer iterations for about the same SpMMs, each iteration one update pass, one scalar
+        launch and one live-count read.  A caller who knows lambda_min passes it as lo; an hi below
+        lambda_max makes q indefinite and ends columns with status 2.  work is then 7 n b elements
+        (CHEB_PCG_WORK_BLOCKS); n_spmm = (degree + 1) iterations + starts + degree (starts with a live
+        column).  The dict carries precond="chebyshev", precond_degree and precond_bounds=(lo, hi).
+
         method="minres" (lz_minres_solve, b <= 64): MINRES, for a symmetric A + shift I that may be
         indefinite (a Helmholtz-type operator, a saddle-point block, A - sigma I at a sigma inside the
         spectrum); the columns in lock step, each by its own scalars, as method="columns".  Same
@@ -1331,7 +1435,7 @@ class Handle:
         Returns a dict: X; iters, status (0 met tol on the measured residual, 1 iterations or
         restarts spent, 2 not positive definite), converged (status == 0), resid (measured), est
         (the recurrence's last value) -- NumPy arrays of b entries; restarts, n_spmm, iterations;
-        with a preconditioner also precond ("jacobi" or "diagonal"; without one the dict is the one
+        with a preconditioner also precond ("jacobi", "diagonal" or "chebyshev"; without one the dict is the one
         it always was, so out.get("precond") is None); with method="block" also fallback (0 / 1)
         and stop (BCG_* reason of the last stop)."""
         torch = _torch()
@@ -1340,10 +1444,16 @@ class Handle:
         if precond is not None and method != "columns":
             raise LanczosError(f'solve: method="{method}" takes no preconditioner')
         n, b = self._blocks("solve", A, B)
-        dinv, kind = None, None
-        if isinstance(precond, str):
+        dinv, kind, cheb = None, None, None
+        if isinstance(precond, ChebPrecond) or (isinstance(precond, str) and precond == "chebyshev"):
+            cp = ChebPrecond() if isinstance(precond, str) else precond
+            hi = gershgorin(A)[1] + float(shift) if cp.hi is None else float(cp.hi)
+            lo = cheb_precond_lo(cp.degree, hi) if cp.lo is None else float(cp.lo)
+            cheb, kind = _cheb_precond((cp.degree, lo, hi)), "chebyshev"
+        elif isinstance(precond, str):
             if precond != "jacobi":
-                raise LanczosError('solve: precond is None, "jacobi" or a 1-D tensor of n elements')
+                raise LanczosError('solve: precond is None, "jacobi", "chebyshev", a ChebPrecond or a 1-D tensor of n '
+                                   'elements')
             dinv, kind = self.jacobi(A, shift), "jacobi"
         elif precond is not None:
             dinv, kind = precond, "diagonal"
@@ -1360,7 +1470,8 @@ class Handle:
         else:
             self._blocks("solve", A, B, X0)
             X = X0.clone()
-        blocks = MINRES_WORK_BLOCKS if method == "minres" else 4 if dinv is None else PCG_WORK_BLOCKS
+        blocks = MINRES_WORK_BLOCKS if method == "minres" else CHEB_PCG_WORK_BLOCKS if cheb is not None \
+            else 4 if dinv is None else PCG_WORK_BLOCKS
         work = self._work4("solve", work, n, b, B, blocks)
         if check_every is not None and check_every < 1:
             raise LanczosError("solve: check_every >= 1")
@@ -1376,6 +1487,8 @@ class Handle:
             _check(self.L.lz_minres_solve(*args, *tail, _p(info)), "lz_minres_solve")
         elif dinv is not None:
             _check(self.L.lz_pcg_solve(*args, _ptr(dinv), *tail, _p(info)), "lz_pcg_solve")
+        elif cheb is not None:
+            _check(self.L.lz_pcg_cheb_solve(*args, ctypes.addressof(cheb), *tail, _p(info)), "lz_pcg_cheb_solve")
         else:
             _check(self.L.lz_cg_solve(*args, *tail, _p(info)), "lz_cg_solve")
         out = {"X": X, "iters": iters, "status": status, "converged": status == 0, "resid": resid, "est": est,
@@ -1386,6 +1499,8 @@ class Handle:
             out["method"] = "minres"
         elif dinv is not None:
             out["precond"] = kind
+        elif cheb is not None:
+            out.update(precond=kind, precond_degree=cheb.degree, precond_bounds=(cheb.lo, cheb.hi))
         return out
 
     @staticmethod

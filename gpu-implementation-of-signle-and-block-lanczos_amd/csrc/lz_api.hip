@@ -381,13 +381,13 @@ static bool pairwise_apart(std::initializer_list<Span> s)
     return true;
 }
 
-// cg_solve as krylov_entry and the Inverse operator call it, for lz_cg_solve (dinv NULL) and lz_pcg_solve: dinv goes in
-// behind shift, in the operator's dtype
-static auto cg_solve_with(const void *dinv)
+// cg_solve as krylov_entry and the Inverse operator call it, for lz_cg_solve (dinv NULL), lz_pcg_solve and
+// lz_pcg_cheb_solve (pc): dinv goes in behind shift, in the operator's dtype, then the Chebyshev preconditioner
+static auto cg_solve_with(const void *dinv, const lz_cheb_precond *pc = nullptr)
 {
-    return [dinv](lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, auto *val, int b,
-                  double shift, auto... rest) {
-        return cg_solve(h, n, nnz, rp, col, val, b, shift, (decltype(val))dinv, rest...);
+    return [dinv, pc](lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, auto *val, int b,
+                      double shift, auto... rest) {
+        return cg_solve(h, n, nnz, rp, col, val, b, shift, (decltype(val))dinv, pc, rest...);
     };
 }
 
@@ -2169,18 +2169,20 @@ int lz_normal_apply(lz_handle *h, int64_t n, int64_t p, int64_t nnz, const int64
     return apply_entry(h, n, OpSpec::normal(p, nnz, rp, col, val, t_rp, t_col, t_val, work), dtype, b, X, Y);
 }
 
-// The term steps' entry points (lz_csr_spmm_axpby, _axpby_dots, _axpby4): their shared checks
-// (want_dots: the call returns dots and needs n >= 1; the three-term ones pass e = 0), then
-// spmm_terms in the dtype
+// The term steps' entry points (lz_csr_spmm_axpby, _axpby_dots, _axpby4, _axpby4_dots): their shared
+// checks (want_dots: the call returns dots and needs n >= 1; the three-term ones pass e = 0; the
+// four-term one with dots pairs them with U, which it requires), then spmm_terms in the dtype
 static int terms_entry(lz_handle *h, int64_t n, bool want_dots, int64_t nnz, const int64_t *rp, const int32_t *col,
                        const void *val, lz_dtype dtype, int b, double a, const void *X, double c, double d, const void *Z,
                        double e, const void *U, bool four, void *Y, double *dots, const double *theta = nullptr)
 {
+    const bool dot_u = four && want_dots;
     LZ_HANDLE_CHECK(h);
     LZ_TRY(check_csr(n, nnz, rp, col, val));
     LZ_TRY(shape_args(dtype, n, want_dots ? 1 : 0, b, kMaxB, "b in [1,64] (and n >= 1 with dots)"));
     LZ_ARG_CHECK(X && Y && (Z || d == 0.0), "X/Y NULL, or Z NULL with d != 0");
     LZ_ARG_CHECK(U || e == 0.0, "U NULL with e != 0");
+    LZ_ARG_CHECK(!dot_u || (U && e != 0.0), "the dots pair Y with U: U given and e != 0");
     LZ_ARG_CHECK(dots || !want_dots, "dots is NULL");
     const bool resid = theta != nullptr;  // lz_csr_spmm_resid: Y is its R, and a, c, d, e are not used
     const int64_t nb = n * b;
@@ -2200,8 +2202,8 @@ static int terms_entry(lz_handle *h, int64_t n, bool want_dots, int64_t nnz, con
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return spmm_terms<T>(h, n, nnz, rp, col, (const T *)val, b,
-                             {(T)a, (const T *)X, (T)c, (T)d, (const T *)Z, (T)e, (const T *)U, four}, (T *)Y, dots,
-                             ax3_fused(), ax3dot_fused());
+                             {(T)a, (const T *)X, (T)c, (T)d, (const T *)Z, (T)e, (const T *)U, four, dot_u}, (T *)Y,
+                             dots, ax3_fused(), ax3dot_fused());
     });
 }
 
@@ -2526,6 +2528,69 @@ int lz_csr_spmm_axpby4(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, 
                        const void *U, void *Y)
 {
     return terms_entry(h, n, false, nnz, rp, col, val, dtype, b, a, X, c, d, Z, e, U, true, Y, nullptr);
+}
+
+int lz_csr_spmm_axpby4_dots(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                            const void *val, lz_dtype dtype, int b, double a, const void *X, double c, double d,
+                            const void *Z, double e, const void *U, void *Y, double *dots)
+{
+    return terms_entry(h, n, true, nnz, rp, col, val, dtype, b, a, X, c, d, Z, e, U, true, Y, dots);
+}
+
+int lz_cgz_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *coef, void *R, const void *W, void *P,
+                  void *S, void *X, const void *Z, double *rr)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
+    LZ_ARG_CHECK(coef && R && W && P && S && X && Z && rr, "coef/R/W/P/S/X/Z/rr NULL");
+    const int64_t nb = n * b;
+    LZ_ARG_CHECK(pairwise_apart({span_of(R, nb, dtype), span_of(W, nb, dtype), span_of(P, nb, dtype),
+                                 span_of(S, nb, dtype), span_of(X, nb, dtype), span_of(Z, nb, dtype)}),
+                 "R, W, P, S, X and Z must be pairwise distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);  // (Z is only read: cg_update's block form, dinv NULL)
+        return cg_update<T>(h, n, b, coef, (T *)R, (const T *)W, (T *)P, (T *)S, (T *)X, nullptr, (T *)const_cast<void *>(Z),
+                            rr);
+    });
+}
+
+// lz_cheb_precond's rules
+static int cheb_precond_args(const lz_cheb_precond *pc)
+{
+    LZ_ARG_CHECK(pc != nullptr, "the Chebyshev preconditioner is NULL");
+    LZ_ARG_CHECK(pc->degree >= 1 && pc->degree <= kChebPrecondMaxDegree, "Chebyshev preconditioner: 1 <= degree <= 64");
+    LZ_ARG_CHECK(std::isfinite(pc->lo) && std::isfinite(pc->hi) && 0.0 < pc->lo && pc->lo < pc->hi,
+                 "Chebyshev preconditioner: 0 < lo < hi, finite");
+    return LZ_OK;
+}
+
+int lz_cheb_precond_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                          lz_dtype dtype, int b, double shift, const lz_cheb_precond *pc, const void *R, void *Z,
+                          void *work, double *dots)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
+    LZ_TRY(cheb_precond_args(pc));
+    LZ_ARG_CHECK(R && Z && work && std::isfinite(shift), "R/Z/work NULL, or shift not finite");
+    const int64_t nb = n * b;
+    LZ_ARG_CHECK(pairwise_apart({span_of(R, nb, dtype), span_of(Z, nb, dtype), span_of(work, 2 * nb, dtype)}),
+                 "R, Z and work must be pairwise distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return cheb_precond_apply<T>(h, n, nnz, rp, col, (const T *)val, b, shift, *pc, (const T *)R, (T *)Z, (T *)work,
+                                     dots, ax3_fused(), ax3dot_fused());
+    });
+}
+
+int lz_pcg_cheb_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                      lz_dtype dtype, int b, double shift, const lz_cheb_precond *pc, const void *B, void *X, void *work,
+                      const lz_cg_opts *opts, int *iters, int *status, double *resid, double *est, int *info)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(cheb_precond_args(pc));
+    return krylov_entry(h, n, nnz, rp, col, val, dtype, b, kMaxB, shift, B, X, work, opts, iters, status, resid, est, info,
+                        cg_solve_with(nullptr, pc), kChebPcgWorkBlocks);
 }
 
 int lz_cheb_series_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,

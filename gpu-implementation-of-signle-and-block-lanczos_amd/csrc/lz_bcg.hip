@@ -680,7 +680,8 @@ int bcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int
         lz_cg_opts oc = o;
         oc.max_iter = std::max(0, o.max_iter - done);
         int ci[3] = {0, 0, 0};
-        LZ_TRY(cg_solve<T>(h, n, nnz, rp, col, val, b, shift, nullptr, B, X, work, oc, iters, status, resid, est, ci));
+        LZ_TRY(cg_solve<T>(h, n, nnz, rp, col, val, b, shift, nullptr, nullptr, B, X, work, oc, iters, status, resid, est,
+                           ci));
         for (int c = 0; c < b; ++c) iters[c] += done;
         iterations += ci[0];
         restarts += ci[1];

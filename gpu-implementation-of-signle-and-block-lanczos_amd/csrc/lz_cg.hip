@@ -1,11 +1,13 @@
 // lz_cg.hip -- batched conjugate gradients on M = A + shift I for b right-hand
-// sides in lock step, with or without a diagonal preconditioner (DESIGN.md 23,
-// 25): lz_cg_update, lz_cg_solve, lz_pcg_update, lz_pcg_solve, lz_csr_jacobi.
+// sides in lock step, without a preconditioner, with a diagonal one or with a Chebyshev
+// polynomial of M: lz_cg_update, lz_cg_solve, lz_pcg_update,
+// lz_pcg_solve, lz_csr_jacobi, lz_cgz_update, lz_cheb_precond_apply, lz_pcg_cheb_solve.
 // One kernel family with a preconditioner switch:
 //   * k_cg_update: the row-local half of a Chronopoulos-Gear step with per-column
 //     device coefficients -- five blocks read, four written, slabs of the new
 //     residual's column dots; a 128-byte-row form and a generic one.  With a
-//     preconditioner also dinv read, Z = D^-1 r written and r.z beside r.r;
+//     preconditioner also dinv read, Z = D^-1 r written and r.z beside r.r; with a block
+//     one (lz_cgz_update) Z = q(M) r is a sixth block, read only;
 //   * k_cg_start / k_cg_scalars / k_cg_live: one workgroup, the per-column rules
 //     of lz_cg.hpp on device memory only;
 //   * cg_solve: the host loop -- one fused SpMM with dots (gathering R, or Z), the
@@ -13,6 +15,7 @@
 //     count per check_every iterations is its only synchronisation.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 
 #include "lz_cg.hpp"
@@ -26,14 +29,16 @@ namespace lz {
 // Y.X], 2 b used: a start's first b are the measured r.r, an iteration's second b
 // are delta); bn2: col_dots(B, B); coef: [alpha(b) | beta(b)]; rec: the
 // recurrence's dots, the update's output -- r.r (b), with a preconditioner [r.z
-// (b) | r.r (b)].
+// (b) | r.r (b)].  zz: directly in front of rec, so that the Chebyshev preconditioner's fused
+// dots [z.z | r.z] (2 b), written at rec - b, leave r.z in rec[0 .. b) where the rule reads it.
 struct CgState {
     double sd[2 * kMaxB], bn2[2 * kMaxB], coef[2 * kMaxB];
-    double rec[2 * kMaxB], meas[kMaxB];
+    double zz[kMaxB], rec[2 * kMaxB], meas[kMaxB];
     CgCol col[kMaxB];
     int nlive, pad;
     unsigned long long nbad;  // lz_csr_jacobi's count
 };
+static_assert(offsetof(CgState, rec) == offsetof(CgState, zz) + kMaxB * sizeof(double), "zz ends where rec starts");
 
 template <typename T>
 struct Vec16;
@@ -46,13 +51,21 @@ struct Vec16<float> {
     typedef float type __attribute__((ext_vector_type(4)));
 };
 
+// The update pass's preconditioner: none (z0 = r), diagonal (z0 = dinv r, Z written), or a
+// block Z = q(M) r some other kernel made (z0 = Z, read only).
+enum class CgPre { None, Diag, Block };
+
 // The preconditioner's streams, the update kernels' last argument: nothing without one.
-template <typename T, bool PRE>
+template <typename T, CgPre PRE>
 struct Pre {};
 template <typename T>
-struct Pre<T, true> {
+struct Pre<T, CgPre::Diag> {
     const T *__restrict__ dinv;
     T *__restrict__ Z;
+};
+template <typename T>
+struct Pre<T, CgPre::Block> {
+    const T *__restrict__ Z;
 };
 
 // Both forms finish every element in this order, alpha and beta being the
@@ -68,6 +81,7 @@ struct Pre<T, true> {
 // the very bits the last pass stored in Z, so Z is written and never read; a
 // frozen column's Z is rewritten with the bits it held.  Without PRE no dinv or Z
 // exists: nothing of them is read, multiplied or passed.
+// Block: z0 = Z[row], a sixth block that is only read; no dinv, nothing written to Z, r.r alone.
 //
 // The 128-byte-row form (b = 16 fp64, b = 32 fp32; every block on 16 bytes):
 // lane t moves 16 bytes, columns VEC (t % 8) .. + VEC of row lane t / 8, so its
@@ -76,15 +90,16 @@ struct Pre<T, true> {
 // lanes of a column are summed in order through LDS into slab q: b doubles, PRE
 // [r.z (b) | r.r (b)].  NT: P, S, X and W move with non-temporal loads and stores
 // (nothing reads them again before a whole iteration has passed); R, which the
-// next SpMM gathers, always with plain ones.  ZNT: Z's store non-temporal as well.
-template <typename T, bool NT, bool PRE, bool ZNT>
+// next SpMM gathers, always with plain ones.  ZNT: Z's store (Block: Z's load) non-temporal as well.
+template <typename T, bool NT, CgPre PRE, bool ZNT>
 __global__ __launch_bounds__(kCgThreads) void k_cg_update128(int64_t n, const double *__restrict__ coef,
                                                              T *__restrict__ R, const T *__restrict__ W,
                                                              T *__restrict__ P, T *__restrict__ S, T *__restrict__ X,
                                                              double *__restrict__ slabs, Pre<T, PRE> pre)
 {
     using V = typename Vec16<T>::type;
-    constexpr int VEC = 16 / (int)sizeof(T), B = 8 * VEC, K = PRE ? 2 : 1;  // K partials; the last is r.r
+    constexpr bool DIAG = PRE == CgPre::Diag;
+    constexpr int VEC = 16 / (int)sizeof(T), B = 8 * VEC, K = DIAG ? 2 : 1;  // K partials; the last is r.r
     __shared__ double red[K][kCgThreads][VEC];
     const int tid = threadIdx.x, l = tid & 7, rl = tid >> 3;
     T al[VEC], be[VEC];
@@ -98,23 +113,25 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update128(int64_t n, const do
     const int64_t step = (int64_t)gridDim.x * kCgRows128;
     for (int64_t row = (int64_t)blockIdx.x * kCgRows128 + rl; row < n; row += step) {
         const int64_t i = row * 8 + l;  // in 16-byte units
-        T dv = T(0);  // (PRE only)
-        if constexpr (PRE) dv = pre.dinv[row];
+        T dv = T(0);  // (Diag only)
+        if constexpr (DIAG) dv = pre.dinv[row];
         V r = reinterpret_cast<const V *>(R)[i];
         const V w = ldnt<NT>(reinterpret_cast<const V *>(W) + i);
         V p = ldnt<NT>(reinterpret_cast<const V *>(P) + i);
         V s = ldnt<NT>(reinterpret_cast<const V *>(S) + i);
         V x = ldnt<NT>(reinterpret_cast<const V *>(X) + i);
         V z;
+        if constexpr (PRE == CgPre::Block) z = ldnt<ZNT>(reinterpret_cast<const V *>(pre.Z) + i);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
             T z0 = r[v];
-            if constexpr (PRE) z0 = dv * r[v];
+            if constexpr (DIAG) z0 = dv * r[v];
+            if constexpr (PRE == CgPre::Block) z0 = z[v];
             p[v] = be[v] == T(0) ? z0 : fma(be[v], p[v], z0);
             s[v] = be[v] == T(0) ? w[v] : fma(be[v], s[v], w[v]);
             x[v] = al[v] == T(0) ? x[v] : fma(al[v], p[v], x[v]);
             r[v] = al[v] == T(0) ? r[v] : fma(-al[v], s[v], r[v]);
-            if constexpr (PRE) {
+            if constexpr (DIAG) {
                 z[v] = dv * r[v];
                 acc[0][v] = fma((double)r[v], (double)z[v], acc[0][v]);
             }
@@ -124,14 +141,14 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update128(int64_t n, const do
         stnt<NT>(reinterpret_cast<V *>(S) + i, s);
         stnt<NT>(reinterpret_cast<V *>(X) + i, x);
         reinterpret_cast<V *>(R)[i] = r;
-        if constexpr (PRE) stnt<ZNT>(reinterpret_cast<V *>(pre.Z) + i, z);
+        if constexpr (DIAG) stnt<ZNT>(reinterpret_cast<V *>(pre.Z) + i, z);
     }
 #pragma unroll
     for (int v = 0; v < VEC; ++v)
         for (int k = 0; k < K; ++k) red[k][tid][v] = acc[k][v];
     __syncthreads();
     if (tid < K * B) {
-        const int kind = PRE ? tid / B : 0, c = tid - kind * B, cl = c / VEC, cv = c - cl * VEC;
+        const int kind = DIAG ? tid / B : 0, c = tid - kind * B, cl = c / VEC, cv = c - cl * VEC;
         double sum = 0.0;
         for (int j = 0; j < kCgRows128; ++j) sum += red[kind][j * 8 + cl][cv];
         slabs[(int64_t)blockIdx.x * K * B + tid] = sum;
@@ -141,13 +158,14 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update128(int64_t n, const do
 // The generic form, 1 <= b <= 64, either dtype: k_col_dots's mapping -- thread t <
 // rpb b (rpb = kCgThreads / b) holds column t % b of row lane t / b; block q takes
 // rows q rpb + t / b + k G rpb.
-template <typename T, bool PRE>
+template <typename T, CgPre PRE>
 __global__ __launch_bounds__(kCgThreads) void k_cg_update_gen(int64_t n, const double *__restrict__ coef,
                                                               T *__restrict__ R, const T *__restrict__ W,
                                                               T *__restrict__ P, T *__restrict__ S, T *__restrict__ X,
                                                               double *__restrict__ slabs, Pre<T, PRE> pre, int b)
 {
-    constexpr int K = PRE ? 2 : 1;
+    constexpr bool DIAG = PRE == CgPre::Diag;
+    constexpr int K = DIAG ? 2 : 1;
     __shared__ double red[K][kCgThreads];
     const int tid = threadIdx.x, rpb = kCgThreads / b, rl = tid / b, c = tid - rl * b;
     double acc[K] = {};
@@ -156,10 +174,11 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update_gen(int64_t n, const d
         const int64_t step = (int64_t)gridDim.x * rpb;
         for (int64_t row = (int64_t)blockIdx.x * rpb + rl; row < n; row += step) {
             const int64_t i = row * b + c;
-            T dv = T(0);  // (PRE only)
-            if constexpr (PRE) dv = pre.dinv[row];
+            T dv = T(0);  // (Diag only)
+            if constexpr (DIAG) dv = pre.dinv[row];
             T z0 = R[i];
-            if constexpr (PRE) z0 = dv * R[i];
+            if constexpr (DIAG) z0 = dv * R[i];
+            if constexpr (PRE == CgPre::Block) z0 = pre.Z[i];
             const T p = be == T(0) ? z0 : fma(be, P[i], z0);
             const T s = be == T(0) ? W[i] : fma(be, S[i], W[i]);
             const T x = al == T(0) ? X[i] : fma(al, p, X[i]);
@@ -168,7 +187,7 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update_gen(int64_t n, const d
             S[i] = s;
             X[i] = x;
             R[i] = r;
-            if constexpr (PRE) {
+            if constexpr (DIAG) {
                 const T z = dv * r;
                 pre.Z[i] = z;
                 acc[0] = fma((double)r, (double)z, acc[0]);
@@ -179,7 +198,7 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update_gen(int64_t n, const d
     for (int k = 0; k < K; ++k) red[k][tid] = acc[k];
     __syncthreads();
     if (tid < K * b) {
-        const int kind = PRE ? tid / b : 0, cc = tid - kind * b;
+        const int kind = DIAG ? tid / b : 0, cc = tid - kind * b;
         double sum = 0.0;
         for (int j = 0; j < rpb; ++j) sum += red[kind][j * b + cc];
         slabs[(int64_t)blockIdx.x * K * b + tid] = sum;
@@ -237,9 +256,19 @@ static bool pcg_z_nt()
     return !(e && e[0] == '0');
 }
 
+// LZ_CGZ_Z_NT=0 (read per call, measurement): lz_cgz_update's Z load plain.  Shipped
+// non-temporal: nothing reads Z again before the next preconditioner application
+// overwrites it.
+static bool cgz_z_nt()
+{
+    const char *e = getenv("LZ_CGZ_Z_NT");
+    return !(e && e[0] == '0');
+}
+
 // One update: the kernel, then the fold of its G slabs into dots -- b doubles each
-// into r.r, or with a preconditioner (dinv and Z given; else both NULL) 2 b each
-// into [r.z | r.r].  h->dots_ws must hold them (dots_reserve(h, n, b, kCgGridCap)).
+// into r.r, or with a diagonal preconditioner (dinv and Z given) 2 b each into [r.z |
+// r.r]; Z without dinv: the block form, Z only read, b doubles into r.r; without a
+// preconditioner both are NULL.  h->dots_ws must hold them (dots_reserve(h, n, b, kCgGridCap)).
 template <typename T>
 static int cg_update_launch(lz_handle *h, int64_t n, int b, const double *coef, T *R, const T *W, T *P, T *S, T *X,
                             const T *dinv, T *Z, double *dots)
@@ -254,19 +283,25 @@ static int cg_update_launch(lz_handle *h, int64_t n, int b, const double *coef, 
     auto run = [&](auto kernel, auto... tail) {
         hipLaunchKernelGGL(kernel, grid, block, 0, h->stream, n, coef, R, W, P, S, X, h->dots_ws, tail...);
     };
-    const Pre<T, false> none;
-    const Pre<T, true> pre{dinv, Z};
+    const Pre<T, CgPre::None> none;
+    const Pre<T, CgPre::Diag> pre{dinv, Z};
+    const Pre<T, CgPre::Block> blk{Z};
     const bool nt = cg_nt();
     const int ev = prof_begin(h, PROF_UPDATE_PASS);
-    if (!dinv) {
-        if (!rows128) run(k_cg_update_gen<T, false>, none, b);
-        else if (nt) run(k_cg_update128<T, true, false, false>, none);
-        else run(k_cg_update128<T, false, false, false>, none);
+    if (!dinv && !Z) {
+        if (!rows128) run(k_cg_update_gen<T, CgPre::None>, none, b);
+        else if (nt) run(k_cg_update128<T, true, CgPre::None, false>, none);
+        else run(k_cg_update128<T, false, CgPre::None, false>, none);
+    } else if (!dinv) {
+        if (!rows128) run(k_cg_update_gen<T, CgPre::Block>, blk, b);
+        else if (!nt) run(k_cg_update128<T, false, CgPre::Block, false>, blk);
+        else if (cgz_z_nt()) run(k_cg_update128<T, true, CgPre::Block, true>, blk);
+        else run(k_cg_update128<T, true, CgPre::Block, false>, blk);
     } else {
-        if (!rows128) run(k_cg_update_gen<T, true>, pre, b);
-        else if (!nt) run(k_cg_update128<T, false, true, false>, pre);
-        else if (pcg_z_nt()) run(k_cg_update128<T, true, true, true>, pre);
-        else run(k_cg_update128<T, true, true, false>, pre);
+        if (!rows128) run(k_cg_update_gen<T, CgPre::Diag>, pre, b);
+        else if (!nt) run(k_cg_update128<T, false, CgPre::Diag, false>, pre);
+        else if (pcg_z_nt()) run(k_cg_update128<T, true, CgPre::Diag, true>, pre);
+        else run(k_cg_update128<T, true, CgPre::Diag, false>, pre);
     }
     prof_end(h, ev);
     LZ_LAUNCH_CHECK();
@@ -417,20 +452,62 @@ __global__ __launch_bounds__(kMaxB) void k_cg_live(CgState *st, int b, double to
     cg_count_live(st, b, live);
 }
 
-// The solve; dinv: the preconditioner, or NULL.  work = [R | W | P | S], then Z with
-// a preconditioner.  A verification (the start step) follows every phase of
-// iterations, so resid is always a measured residual.
+// Z = q(M) R, M = A + shift I, q the Chebyshev polynomial preconditioner pc (lz_cg.hpp):
+// pc.degree SpMMs, the first a three-term step on R, the others four-term steps with U = R,
+// the shift in the c coefficient (sg: the shift rounded to T, as the solve's).  Step i
+// writes buffer (i + 2 - degree) mod 3 of {work_0, work_1, Z}, as lz_cheb_apply: the last
+// step lands in Z and a step's output is none of its inputs.  dots != NULL: [Z.Z | Z.R] of
+// the stored Z, out of the last step's store where it fuses.  No host synchronisation.
+template <typename T>
+int cheb_precond_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                       double shift, const lz_cheb_precond &pc, const T *R, T *Z, T *work, double *dots, bool fused,
+                       bool fused_dot)
+{
+    double cf[4 * kChebPrecondMaxDegree];
+    cheb_precond_coeffs(pc.degree, pc.lo, pc.hi, cf);
+    const double sg = (double)(T)shift;
+    const int D = pc.degree;
+    T *buf[3] = {work, work + n * b, Z};
+    auto out = [&](int i) { return buf[((i + 2 - D) % 3 + 3) % 3]; };
+    LZ_TRY(spmm_terms<T>(h, n, nnz, rp, col, val, b, {T(cf[0]), R, T(cf[1] + cf[0] * sg), T(0), nullptr}, out(1),
+                         D == 1 ? dots : nullptr, fused, fused_dot));
+    for (int i = 2; i <= D; ++i) {
+        const double *c = cf + 4 * (i - 1);
+        LZ_TRY(spmm_terms<T>(h, n, nnz, rp, col, val, b,
+                             {T(c[0]), out(i - 1), T(c[1] + c[0] * sg), T(c[2]), i == 2 ? nullptr : out(i - 2), T(c[3]), R,
+                              true, true},
+                             out(i), i == D ? dots : nullptr, fused, fused_dot));
+    }
+    return LZ_OK;
+}
+template int cheb_precond_apply<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *,
+                                        int, double, const lz_cheb_precond &, const double *, double *, double *,
+                                        double *, bool, bool);
+template int cheb_precond_apply<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
+                                       double, const lz_cheb_precond &, const float *, float *, float *, double *, bool,
+                                       bool);
+
+// The solve; dinv: the diagonal preconditioner, pc: the Chebyshev one, at most one of them
+// given.  work = [R | W | P | S], then Z with a preconditioner, then the Chebyshev one's two
+// blocks.  A verification (the start step) follows every phase of iterations, so resid is
+// always a measured residual.
 template <typename T>
 int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
-             double shift, const T *dinv, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status,
-             double *resid, double *est, int *info)
+             double shift, const T *dinv, const lz_cheb_precond *pc, const T *B, T *X, T *work, const lz_cg_opts &o,
+             int *iters, int *status, double *resid, double *est, int *info)
 {
     LZ_TRY(grow_ws_poisoned(h, &h->cg_ws, &h->cg_cap, sizeof(CgState)));
     LZ_TRY(dots_reserve(h, n, b, kCgGridCap));
     CgState *st = static_cast<CgState *>(h->cg_ws);
-    const int pre = dinv != nullptr;
+    const int pre = dinv != nullptr || pc != nullptr;
     const int64_t nb = n * b;
     T *R = work, *W = work + nb, *P = work + 2 * nb, *S = work + 3 * nb, *Z = pre ? work + 4 * nb : nullptr;
+    // the Chebyshev application: its dots [z.z | r.z] at rec - b, so r.z lands in rec[0 .. b)
+    int live_starts = 0;
+    auto precondition = [&]() -> int {
+        double *zd = reinterpret_cast<double *>(reinterpret_cast<char *>(st) + offsetof(CgState, rec)) - b;
+        return cheb_precond_apply<T>(h, n, nnz, rp, col, val, b, shift, *pc, R, Z, work + 5 * nb, zd, true, true);
+    };
     const T *D = pre ? Z : R;  // the search direction's source, what the SpMM gathers
     const T sg = (T)shift;     // rounded once: it travels as the store's c coefficient
     const double tol2 = o.tol * o.tol;
@@ -442,11 +519,12 @@ int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int3
         LZ_HIP_TRY(hipStreamSynchronize(h->stream));
         return LZ_OK;
     };
-    // R = B - M X with its dots (r.r measured); Z = D^-1 R with r.z; the start rule
+    // R = B - M X with its dots (r.r measured); Z = D^-1 R with r.z; the start rule; then, for a live
+    // column, Z = q(M) R with r.z
     auto start = [&](bool initial) -> int {
         LZ_TRY(spmm_terms<T>(h, n, nnz, rp, col, val, b, {T(-1), X, -sg, T(1), B}, R, st->sd));
         ++n_spmm;
-        if (pre) {
+        if (dinv) {
             const int64_t rpb = kCgThreads / b;
             const int G = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, rpb), kCgGridCap));
             const int ev = prof_begin(h, PROF_UPDATE_PASS);
@@ -458,7 +536,14 @@ int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int3
         hipLaunchKernelGGL(k_cg_start, dim3(1), dim3(kMaxB), 0, h->stream, st, b, tol2, o.max_iter, initial ? 1 : 0,
                            pre);
         LZ_LAUNCH_CHECK();
-        return read_live();
+        LZ_TRY(read_live());
+        // (the start rule reads no r.z: the polynomial is applied only for a column that goes on,
+        // so the verification that ends a solve pays none)
+        if (pc && nlive > 0) {
+            ++live_starts;
+            LZ_TRY(precondition());
+        }
+        return LZ_OK;
     };
 
     LZ_TRY(col_dots<T>(h, n, b, B, B, st->bn2, true));
@@ -471,7 +556,8 @@ int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int3
                 hipLaunchKernelGGL(k_cg_scalars, dim3(1), dim3(kMaxB), 0, h->stream, st, b, tol2, o.max_iter,
                                    first ? 1 : 0, pre);
                 LZ_LAUNCH_CHECK();
-                LZ_TRY(cg_update_launch<T>(h, n, b, st->coef, R, W, P, S, X, dinv, Z, st->rec));
+                LZ_TRY(cg_update_launch<T>(h, n, b, st->coef, R, W, P, S, X, dinv, Z, pc ? st->rec + b : st->rec));
+                if (pc) LZ_TRY(precondition());
                 first = false;
             }
             iterations += chunk;
@@ -501,14 +587,14 @@ int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int3
     }
     info[0] = iterations;
     info[1] = restarts;
-    info[2] = n_spmm;
+    info[2] = n_spmm + (pc ? pc->degree * (iterations + live_starts) : 0);
     return LZ_OK;
 }
 template int cg_solve<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *, int,
-                              double, const double *, const double *, double *, double *, const lz_cg_opts &, int *,
-                              int *, double *, double *, int *);
+                              double, const double *, const lz_cheb_precond *, const double *, double *, double *,
+                              const lz_cg_opts &, int *, int *, double *, double *, int *);
 template int cg_solve<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int, double,
-                             const float *, const float *, float *, float *, const lz_cg_opts &, int *, int *, double *,
-                             double *, int *);
+                             const float *, const lz_cheb_precond *, const float *, float *, float *, const lz_cg_opts &,
+                             int *, int *, double *, double *, int *);
 
 }  // namespace lz

@@ -93,4 +93,37 @@ LZ_CG_HD inline void cg_step_rule(bool pre, double rz, double rr, double delta, 
     s.iters += 1;
 }
 
+// The Chebyshev polynomial preconditioner z = q(M) r: the Chebyshev
+// semi-iteration on M z = r from z_0 = 0 over [lo, hi], `degree` SpMMs.  With theta =
+// (hi + lo) / 2, delta = (hi - lo) / 2, sigma_1 = theta / delta, rho_0 = 1 / sigma_1, z_1 =
+// r / theta and rho_j = 1 / (2 sigma_1 - rho_{j-1}):
+//   z_{j+1} = a_j M z_j + c_j z_j + d_j z_{j-1} + e_j r,
+//   a_j = -2 rho_j / delta, c_j = 1 + rho_j rho_{j-1}, d_j = -rho_j rho_{j-1}, e_j = 2 rho_j / delta.
+// out: rows (a, c, d, e) of steps j = 1 .. degree, as the device applies them.  z_1 is never
+// stored: step 1 carries it folded in and is a three-term step on r, (a_1 / theta, c_1 /
+// theta + e_1, 0, 0); step 2, whose z_{j-1} is that z_1, takes it through r as well:
+// (a_2, c_2, 0, d_2 / theta + e_2).  The result is z_{degree+1}, and 1 - lambda q(lambda) =
+// T_k((theta - lambda) / delta) / T_k(sigma_1) with k = degree + 1.
+// The default lower end: hi / (4 (degree + 1)^2).
+inline double cheb_precond_lo(int degree, double hi) { return hi / (4.0 * (degree + 1.0) * (degree + 1.0)); }
+
+inline void cheb_precond_coeffs(int degree, double lo, double hi, double *out)
+{
+    const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), s1 = theta / delta;
+    double rp = 1.0 / s1;
+    for (int j = 1; j <= degree; ++j) {
+        const double rho = 1.0 / (2.0 * s1 - rp);
+        const double a = -2.0 * rho / delta, c = 1.0 + rho * rp, d = -(rho * rp), e = 2.0 * rho / delta;
+        double *o = out + 4 * (j - 1);
+        if (j == 1) {
+            o[0] = a / theta, o[1] = c / theta + e, o[2] = 0.0, o[3] = 0.0;
+        } else if (j == 2) {
+            o[0] = a, o[1] = c, o[2] = 0.0, o[3] = d / theta + e;
+        } else {
+            o[0] = a, o[1] = c, o[2] = d, o[3] = e;
+        }
+        rp = rho;
+    }
+}
+
 }  // namespace lz

@@ -759,6 +759,17 @@ int lzh_pcg_scalars(int b, int first, int max_iter, const double *rz, const doub
     return 0;
 }
 
+// ---- the Chebyshev polynomial preconditioner's coefficients (lz_cg.hpp), as lz_cheb_precond_apply uses them
+int lzh_cheb_precond_coeffs(int degree, double lo, double hi, double *out)
+{
+    if (degree < 1 || degree > 64 || !out || !std::isfinite(lo) || !std::isfinite(hi) || !(0.0 < lo) || !(lo < hi))
+        return -1;
+    lz::cheb_precond_coeffs(degree, lo, hi, out);
+    return 0;
+}
+
+double lzh_cheb_precond_lo(int degree, double hi) { return lz::cheb_precond_lo(degree, hi); }
+
 // ---- batched MINRES: the per-column rules of lz_minres.hpp, as k_minres_start and
 // k_minres_scalars apply them, on host arrays: state = 8 rows of b doubles [beta_prev |
 // alpha_prev | c1 | s1 | c2 | s2 | phibar | est2], ctl = 4 rows of b ints [live | iters |

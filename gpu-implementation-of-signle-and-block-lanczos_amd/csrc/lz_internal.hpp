@@ -22,6 +22,7 @@ struct SpmmTerms {
     T e = T(0);
     const T *U = nullptr;
     bool four = false;
+    bool dot_u = false;  // the cross dots pair Y with U (lz_csr_spmm_axpby4_dots), not with X
 };
 // Y = those terms on a square operator.  128-B rows under 2 GiB, every block read on 16
 // bytes: they leave k_spmm_seg's store (SegStore::Terms3, last_kernel | LZ_K_AX3; four:
@@ -29,7 +30,8 @@ struct SpmmTerms {
 // dots != nullptr: also dots[0 .. b) = sum_i Y[i][c]^2, dots[b .. 2b) = sum_i Y[i][c] X[i][c]
 // of the stored Y (device, fp64, fixed summation order; n >= 1).  A three-term step at the
 // fused shapes with fused_dot: the dots leave the store too (Terms3Dots, | LZ_K_DOT), a
-// slab per tile in h->dots_ws; else col_dots afterwards.
+// slab per tile in h->dots_ws; else col_dots afterwards.  dot_u (four, U given): dots[b .. 2b) =
+// sum_i Y[i][c] U[i][c] instead, from the four-term store (Terms4Dots, | LZ_K_AX4 | LZ_K_DOT).
 template <typename T>
 int spmm_terms(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
                SpmmTerms<T> t, T *Y, double *dots = nullptr, bool fused = true, bool fused_dot = true);
@@ -68,7 +70,11 @@ int slabs_fold(lz_handle *h, int64_t P, int bb, double *out, int zero_from = -1)
 // The solve's work: 4 blocks, [R | W | P | S]; kPcgWorkBlocks with a preconditioner, Z behind them.
 constexpr int kCgThreads = 256, kCgRows128 = 32, kCgGridCap = 2048, kCgCheckEvery = 8;
 constexpr int kJacobiLanes = 8, kJacobiRows = kCgThreads / kJacobiLanes, kPcgWorkBlocks = 5;
-// lz_cg_update (dinv = Z = NULL, dots: b) and lz_pcg_update (dots: 2 b) (include/lz_hip.h)
+// The Chebyshev polynomial preconditioner: its highest degree, and the solve's
+// work with it, [R | W | P | S | Z | T0 | T1].
+constexpr int kChebPrecondMaxDegree = 64, kChebPcgWorkBlocks = 7;
+// lz_cg_update (dinv = Z = NULL, dots: b), lz_pcg_update (dots: 2 b) and lz_cgz_update (dinv = NULL,
+// Z given and only read, dots: b) (include/lz_hip.h)
 template <typename T>
 int cg_update(lz_handle *h, int64_t n, int b, const double *coef, T *R, const T *W, T *P, T *S, T *X, const T *dinv,
               T *Z, double *dots);
@@ -76,11 +82,16 @@ int cg_update(lz_handle *h, int64_t n, int b, const double *coef, T *R, const T 
 template <typename T>
 int csr_jacobi(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, const T *val, double shift, T *dinv,
                int64_t *n_bad);
-// lz_cg_solve (dinv = NULL) and lz_pcg_solve (include/lz_hip.h)
+// lz_cheb_precond_apply (include/lz_hip.h); fused, fused_dot: spmm_terms'
+template <typename T>
+int cheb_precond_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                       double shift, const lz_cheb_precond &pc, const T *R, T *Z, T *work, double *dots, bool fused,
+                       bool fused_dot);
+// lz_cg_solve (dinv = pc = NULL), lz_pcg_solve (dinv) and lz_pcg_cheb_solve (pc) (include/lz_hip.h)
 template <typename T>
 int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
-             double shift, const T *dinv, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *status,
-             double *resid, double *est, int *info);
+             double shift, const T *dinv, const lz_cheb_precond *pc, const T *B, T *X, T *work, const lz_cg_opts &o,
+             int *iters, int *status, double *resid, double *est, int *info);
 // ---- batched MINRES (lz_minres.hip): k_minres_update runs k_cg_update's
 // shapes (kCgThreads, kCgRows128, kCgGridCap; one slab of b doubles per block).
 // The solve's work: kMinresWorkBlocks blocks, [U0 | U1 | W | D0 | D1].

@@ -399,11 +399,11 @@ __device__ __forceinline__ Vec<T, VEC> epi_piece(Vec<T, VEC> y, const T *__restr
 // nullptr exactly when e == 0); a term whose test fails is never read.  (A test on U itself
 // keeps one more flag live across the MODE 1 gather: 100 VGPRs for 94 and a wave per SIMD
 // less at fp64.)  HAS_U = false (the three-term stores): no U load and no branch for it.
-// xo (Terms3Dots): the x piece, for the column dots.
+// xo (Terms3Dots): the x piece, for the column dots; uo (Terms4Dots, whose e is never 0): the u piece.
 template <typename T, int VEC, bool HAS_U>
 __device__ __forceinline__ Vec<T, VEC> term_piece(Vec<T, VEC> s, const T *__restrict__ xrow, const T *__restrict__ Z,
                                                   const T *__restrict__ U, int64_t o, T a, T c, T d, T e,
-                                                  Vec<T, VEC> *xo = nullptr)
+                                                  Vec<T, VEC> *xo = nullptr, Vec<T, VEC> *uo = nullptr)
 {
     static_assert(sizeof(T) * VEC == 16, "128-B rows: 16-B pieces");
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -419,6 +419,7 @@ __device__ __forceinline__ Vec<T, VEC> term_piece(Vec<T, VEC> s, const T *__rest
         const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(U + o));
         __builtin_memcpy(&u, &r, 16);
     }
+    if (uo) *uo = u;
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
         T t = hu ? e * u.v[i] : T(0);
@@ -536,32 +537,41 @@ __device__ __forceinline__ int xcc_id()
 //   ShiftDots   lz_csr_spmm_resid: Y[row][c] = y[c] - theta_c X[row][c] with theta the b device
 //               doubles at cshift, and Terms3Dots' slabs of the stored rows.  term_piece's
 //               arithmetic at a = 1, c = -theta_c, d = 0: fma(1, y, fma(-theta_c, x, 0)).
+//   Terms4Dots  lz_csr_spmm_axpby4_dots: Terms4's stored row, and Terms3Dots' slabs with U's rows
+//               in X's place: the column dots of the stored rows with themselves and with U's
+//               (U is required: e != 0).
 // Only Rows and ColMajor have windowed (WIN) launches; only Rows the diagnostic build's PF.
-enum class SegStore { Rows, ColMajor, Beta2, Terms3, Terms3Dots, Terms4, ShiftDots };
+enum class SegStore { Rows, ColMajor, Beta2, Terms3, Terms3Dots, Terms4, ShiftDots, Terms4Dots };
 
 constexpr bool seg_terms(SegStore st)
 {
-    return st == SegStore::Terms3 || st == SegStore::Terms3Dots || st == SegStore::Terms4;
+    return st == SegStore::Terms3 || st == SegStore::Terms3Dots || st == SegStore::Terms4 || st == SegStore::Terms4Dots;
 }
 
+// the term stores with the fourth term e U
+constexpr bool seg_four(SegStore st) { return st == SegStore::Terms4 || st == SegStore::Terms4Dots; }
+
 // the stores that leave a slab of column dots per tile
-constexpr bool seg_dots(SegStore st) { return st == SegStore::Terms3Dots || st == SegStore::ShiftDots; }
+constexpr bool seg_dots(SegStore st)
+{
+    return st == SegStore::Terms3Dots || st == SegStore::Terms4Dots || st == SegStore::ShiftDots;
+}
 
 // the store's bits of lz_debug_last_kernel's SpMM word
 constexpr int seg_store_bits(SegStore st)
 {
     return (st == SegStore::ColMajor ? LZ_K_YCM : 0) | (st == SegStore::Beta2 ? LZ_K_EPI : 0) |
-           (seg_terms(st) ? LZ_K_AX3 : 0) | (st == SegStore::Terms3Dots ? LZ_K_DOT : 0) |
-           (st == SegStore::Terms4 ? LZ_K_AX4 : 0) | (st == SegStore::ShiftDots ? LZ_K_RESID : 0);
+           (seg_terms(st) ? LZ_K_AX3 : 0) | (seg_terms(st) && seg_dots(st) ? LZ_K_DOT : 0) |
+           (seg_four(st) ? LZ_K_AX4 : 0) | (st == SegStore::ShiftDots ? LZ_K_RESID : 0);
 }
 
 // What the stores read or write besides Y; a field is dead in the launches of the other stores
 template <typename T>
 struct SegOperands {
     const T *Wprev = nullptr, *M = nullptr;  // Beta2
-    const T *Z = nullptr, *U = nullptr;      // the term stores (U: Terms4)
+    const T *Z = nullptr, *U = nullptr;      // the term stores (U: Terms4, Terms4Dots)
     T a = T(0), c = T(0), d = T(0), e = T(0);
-    double *dots = nullptr;                  // Terms3Dots, ShiftDots: the tiles' slabs
+    double *dots = nullptr;                  // Terms3Dots, Terms4Dots, ShiftDots: the tiles' slabs
     const double *cshift = nullptr;          // ShiftDots: theta, B doubles
 };
 
@@ -589,11 +599,11 @@ __device__ __forceinline__ void seg_store_piece(Vec<T, VEC> &y, int64_t row, int
         for (int i = 0; i < VEC; ++i) y.v[i] = fma(T(1), y.v[i], fma(dacc.c[i], x.v[i], T(0)));
         dacc.add(y, x);
     } else if constexpr (seg_terms(ST)) {
-        [[maybe_unused]] Vec<T, VEC> x;
-        y = term_piece<T, VEC, ST == SegStore::Terms4>(y, X + row * ldx + pc * VEC, ops.Z, ops.U, row * B + pc * VEC,
-                                                       ops.a, ops.c, ops.d, ops.e,
-                                                       ST == SegStore::Terms3Dots ? &x : nullptr);
-        if constexpr (ST == SegStore::Terms3Dots) dacc.add(y, x);
+        [[maybe_unused]] Vec<T, VEC> x;  // the piece the dots pair with: X's (Terms3Dots) or U's (Terms4Dots)
+        y = term_piece<T, VEC, seg_four(ST)>(y, X + row * ldx + pc * VEC, ops.Z, ops.U, row * B + pc * VEC, ops.a,
+                                             ops.c, ops.d, ops.e, ST == SegStore::Terms3Dots ? &x : nullptr,
+                                             ST == SegStore::Terms4Dots ? &x : nullptr);
+        if constexpr (seg_dots(ST)) dacc.add(y, x);
     }
 }
 
@@ -1933,13 +1943,16 @@ __global__ __launch_bounds__(256) void k_term_rows(int64_t nb, T a, T c, T d, T 
 // X under 2 GiB / 2^24 rows, 16-B aligned blocks (Z, U: those that are read).  fused =
 // false (measurement, the benchmarks' two-launch side) or any other shape: spmm_rm, then
 // k_term_rows -- the same bits.  dots: the stored Y's column dots; from the store too
-// (a slab per 48-row tile, folded by dots_fold) unless fused_dot = false (measurement) or
-// the step has four terms, else the streaming col_dots.
+// (a slab per 48-row tile, folded by dots_fold: Terms3Dots, or with t.dot_u -- the cross
+// dots with U -- Terms4Dots) unless fused_dot = false (measurement) or the step's terms
+// and its cross block do not match a store (four terms with X, three with U), else the
+// streaming col_dots.
 template <typename T>
 int spmm_terms(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
                SpmmTerms<T> t, T *Y, double *dots, bool fused, bool fused_dot)
 {
     if (n <= 0) return LZ_OK;
+    const T *cross = t.dot_u ? t.U : t.X;  // the block of the cross dots
     if (t.d == T(0)) t.Z = nullptr;
     if (t.e == T(0) || !t.four) t.U = nullptr;
     const bool rows128 = (int64_t)b * (int64_t)sizeof(T) == 128;
@@ -1949,7 +1962,7 @@ int spmm_terms(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const in
     const char *fz = getenv("LZ_SPMM_FNZ");  // (the fixed-nnz experiment has no fused store)
     if (fused && rows128 && buf_ok && al16 && !(fz && fz[0] == '1')) {
         constexpr int B = 128 / (int)sizeof(T);
-        const bool store_dots = dots && fused_dot && !t.four;
+        const bool store_dots = dots && fused_dot && (t.four ? t.dot_u && t.U : !t.dot_u);
         SegOperands<T> ops;
         ops.Z = t.Z, ops.U = t.U;
         ops.a = t.a, ops.c = t.c, ops.d = t.d, ops.e = t.e;
@@ -1965,7 +1978,8 @@ int spmm_terms(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const in
             });
         };
         const int ev = prof_begin(h, PROF_SPMM);
-        const int rc = store_dots ? seg(std::integral_constant<SegStore, SegStore::Terms3Dots>{})
+        const int rc = store_dots && t.four ? seg(std::integral_constant<SegStore, SegStore::Terms4Dots>{})
+                       : store_dots ? seg(std::integral_constant<SegStore, SegStore::Terms3Dots>{})
                        : t.four   ? seg(std::integral_constant<SegStore, SegStore::Terms4>{})
                                   : seg(std::integral_constant<SegStore, SegStore::Terms3>{});
         prof_end(h, ev);
@@ -1984,7 +1998,7 @@ int spmm_terms(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const in
                                t.Z, t.U, Y);
         LZ_LAUNCH_CHECK();
     }
-    return dots ? col_dots<T>(h, n, b, Y, t.X, dots) : LZ_OK;
+    return dots ? col_dots<T>(h, n, b, Y, cross, dots) : LZ_OK;
 }
 
 template int spmm_terms<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *, int,

@@ -502,6 +502,63 @@ int lz_pcg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, c
                  lz_dtype dtype, int b, double shift, const void *dinv, const void *B, void *X, void *work,
                  const lz_cg_opts *opts, int *iters, int *status, double *resid, double *est, int *info);
 
+/* ------------- Chebyshev polynomial preconditioner for lz_cg_solve's method (no reference counterpart)
+ * z = q(M) r, M = A + shift I, q the polynomial of the Chebyshev semi-iteration on M z = r
+ * from z_0 = 0 over [lo, hi] (lzh_cheb_precond_coeffs in lz_host.h gives the steps): 1 -
+ * lambda q(lambda) = T_k((theta - lambda) / delta) / T_k(theta / delta), k = degree + 1, so
+ * q > 0 on (0, hi] for any 0 < lo < hi: with hi >= lambda_max (Gershgorin's bound is one) q(M)
+ * is symmetric positive definite whatever lo is.  It trades update passes, reductions and
+ * launches for SpMMs, and pays where Jacobi cannot: on a constant diagonal.
+ *
+ * lz_csr_spmm_axpby4_dots: lz_csr_spmm_axpby4 (same arguments, same rules, the same bits in
+ * Y) with U required (U NULL or e == 0 is LZ_E_ARG), and dots[0 .. b) = sum_i Y[i][c]^2,
+ * dots[b .. 2b) = sum_i Y[i][c] U[i][c] of the stored Y, as lz_col_dots(Y, U) returns them.
+ * Where lz_csr_spmm_axpby4 fuses its store the dots leave it too (lz_debug_last_kernel: the
+ * SpMM id | LZ_K_AX3 | LZ_K_AX4 | LZ_K_DOT), a slab per 48-row tile folded in
+ * lz_csr_spmm_axpby_dots' fixed order; every other shape -- and LZ_AX3DOT=0 -- runs
+ * lz_csr_spmm_axpby4 and then the streaming kernel of lz_col_dots. */
+int lz_csr_spmm_axpby4_dots(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                            const void *val, lz_dtype dtype, int b, double a, const void *X, double c, double d,
+                            const void *Z, double e, const void *U, void *Y, double *dots);
+/* lz_cg_update's pass with z0 read from a block Z, which is only read (no dinv, nothing
+ * written to Z):
+ *   P = fma(beta, P, Z),  S = fma(beta, S, W),  X = fma(alpha, P, X),  R = fma(-alpha, S, R)
+ * and rr[c] = sum_i R[i][c]^2 of the stored R, under lz_cg_update's zero-coefficient rules
+ * (beta == 0 stores P = Z and S = W; alpha == 0 leaves X and R bit for bit).  Six blocks
+ * read, four written.  The same two forms and the LZ_CG_GENERIC and LZ_CG_NT switches; Z is
+ * loaded with non-temporal loads (LZ_CGZ_Z_NT=0, measurement: plain).  With Z a copy of R
+ * it stores lz_cg_update's bits.  The six blocks must not overlap: LZ_E_ARG. */
+int lz_cgz_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *coef, void *R, const void *W, void *P,
+                  void *S, void *X, const void *Z, double *rr);
+/* 1 <= degree <= 64 and 0 < lo < hi finite; anything else is LZ_E_ARG. */
+typedef struct {
+    int degree;
+    double lo, hi;
+} lz_cheb_precond;
+/* Z = q(A + shift I) R in exactly `degree` SpMMs: the first an lz_csr_spmm_axpby on R, the
+ * others lz_csr_spmm_axpby4 with U = R; the shift, rounded once to the dtype, travels in the
+ * c coefficient (c_j + a_j shift).  dots (2 b doubles, device; may be NULL) receives [Z.Z |
+ * Z.R] of the stored Z out of the last step (lz_csr_spmm_axpby_dots when degree = 1, else
+ * lz_csr_spmm_axpby4_dots).  R (read only), Z: n x b row-major, ld = b; work: 2 n b
+ * elements (not read on entry); R, Z and work pairwise distinct.  {work_0, work_1, Z}
+ * rotate as in lz_cheb_apply.  No host synchronisation. */
+int lz_cheb_precond_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                          const void *val, lz_dtype dtype, int b, double shift, const lz_cheb_precond *pc,
+                          const void *R, void *Z, void *work, double *dots);
+/* lz_cg_solve with that preconditioner: the same arguments, options, results and status
+ * codes, but work is 7 n b elements ([R | W | P | S | Z | T0 | T1]).  lz_pcg_solve's
+ * contract holds (a column stops on r.r <= tol^2 |B_c|^2; resid is measured; status 2 also
+ * when r.z <= 0 or is not finite: hi below lambda_max makes q indefinite).  A start is R =
+ * B - M X with its dots, the start rule and the live-count read; only when a column is live
+ * does Z = q(M) R follow, so the verification that ends a solve applies no polynomial.  Per
+ * iteration: W = M Z with dots, one one-workgroup launch, one lz_cgz_update, one
+ * lz_cheb_precond_apply whose last store carries r.z.  info[2] (SpMMs) = (degree + 1)
+ * iterations + starts + degree (starts after which a column was live). */
+int lz_pcg_cheb_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                      const void *val, lz_dtype dtype, int b, double shift, const lz_cheb_precond *pc, const void *B,
+                      void *X, void *work, const lz_cg_opts *opts, int *iters, int *status, double *resid, double *est,
+                      int *info);
+
 /* ----------------------------- block conjugate gradients (no reference counterpart)
  * The b columns share one Krylov space: Dubrulle's BCGrQ with the symmetric
  * orthonormalisation of lz_sqrtm_pair in place of the QR.  M = A + shift I; the
@@ -792,7 +849,7 @@ enum {
     LZ_K_YCM = 0x200,   /* column-major Y store */
     LZ_K_EPI = 0x400,   /* the beta^2 step's epilogue U = A X - Wp M */
     LZ_K_AX3 = 0x800,   /* lz_csr_spmm_axpby's fused three-term store a A X + c X + d Z */
-    LZ_K_DOT = 0x1000,  /* lz_csr_spmm_axpby_dots: the column dots leave the fused store too */
+    LZ_K_DOT = 0x1000,  /* lz_csr_spmm_axpby_dots, _axpby4_dots (with LZ_K_AX4): the column dots leave the fused store too */
     LZ_K_AX4 = 0x2000,  /* lz_csr_spmm_axpby4: the fused store's fourth term e U (with LZ_K_AX3) */
     LZ_K_RESID = 0x4000, /* lz_csr_spmm_resid: the fused residual store A X - X diag(theta) with its dots */
     LZ_K_GRAM16 = 1,    /* dense ids: b = 16 MFMA Gram (fp64 and fp32) */

@@ -172,6 +172,19 @@ int lzh_cg_scalars(int b, int first, int max_iter, const double *gamma, const do
 int lzh_pcg_scalars(int b, int first, int max_iter, const double *rz, const double *rr, const double *delta,
                     const double *thr, double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters,
                     int *status, double *coef, int *nlive);
+/* The steps of the Chebyshev polynomial preconditioner z = q(M) r (lz_cheb_precond in
+ * lz_hip.h), the numbers lz_cheb_precond_apply uses: with theta = (hi + lo) / 2, delta =
+ * (hi - lo) / 2, sigma_1 = theta / delta, rho_0 = 1 / sigma_1, rho_j = 1 / (2 sigma_1 -
+ * rho_{j-1}), z_0 = 0 and z_1 = r / theta,
+ *   z_{j+1} = a_j M z_j + c_j z_j + d_j z_{j-1} + e_j r,
+ *   a_j = -2 rho_j / delta, c_j = 1 + rho_j rho_{j-1}, d_j = -rho_j rho_{j-1}, e_j = 2 rho_j / delta.
+ * out: 4 degree doubles, row j - 1 = the (a, c, d, e) of step j as it is applied.  z_1 is
+ * never stored: step 1 is the three-term step on r (a_1 / theta, c_1 / theta + e_1, 0, 0),
+ * and step 2 takes its z_1 through r as well, (a_2, c_2, 0, d_2 / theta + e_2).  The result
+ * of `degree` steps is z_{degree+1}.  1 <= degree <= 64, 0 < lo < hi finite: returns 0, else -1.
+ * lzh_cheb_precond_lo: the default lower end, hi / (4 (degree + 1)^2). */
+int lzh_cheb_precond_coeffs(int degree, double lo, double hi, double *out);
+double lzh_cheb_precond_lo(int degree, double hi);
 /* ------------------------------------------- batched MINRES
  * The per-column scalar rules of lz_minres_solve (lz_hip.h), the very code its
  * one-workgroup kernels run (csrc/lz_minres.hpp), on host arrays.  state: 8 rows of b
