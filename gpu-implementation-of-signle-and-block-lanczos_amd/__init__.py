@@ -42,6 +42,7 @@ LZ_ROW_MAJOR, LZ_COL_MAJOR = 0, 1
 LZ_K_WIN, LZ_K_YCM, LZ_K_EPI, LZ_K_AX3, LZ_K_DOT = 0x100, 0x200, 0x400, 0x800, 0x1000
 LZ_K_AX4 = 0x2000
 LZ_K_RESID = 0x4000  # lz_csr_spmm_resid's fused residual store
+LZ_K_RSC = 0x8000  # lz_csr_spmm_rowscale's fused row-scaled store
 LZ_K_GRAM16, LZ_K_GRAM32F, LZ_K_GRAM_GEN, LZ_K_TSMM16, LZ_K_TSMM32F, LZ_K_TSMM_GEN = range(1, 7)
 LZ_K_PGRAM16, LZ_K_PGRAM_GEN, LZ_K_PAPPLY16, LZ_K_PAPPLY_GEN = range(7, 11)
 # blocks per group of the panel Gram kernels (W is re-read once per group): b = 16 fp64 MFMA, generic
@@ -65,6 +66,8 @@ PCG_WORK_BLOCKS, JACOBI_LANES, JACOBI_ROWS = 5, 8, 32
 # lz_pcg_cheb_solve's work is CHEB_PCG_WORK_BLOCKS blocks of n b elements, [R | W | P | S | Z | T0 | T1];
 # CHEB_PRECOND_MAX_DEGREE: the Chebyshev preconditioner's highest degree (csrc/lz_internal.hpp kCheb*)
 CHEB_PCG_WORK_BLOCKS, CHEB_PRECOND_MAX_DEGREE = 7, 64
+# lz_pcg_cheb_jacobi_solve's work: [R | W | P | S | Z | T0 | T1 | Rs] (csrc/lz_internal.hpp kChebJacobiPcgWorkBlocks)
+CHEB_JACOBI_PCG_WORK_BLOCKS = 8
 # lz_minres_solve's work is MINRES_WORK_BLOCKS blocks of n b elements (csrc/lz_internal.hpp kMinresWorkBlocks);
 # lz_minres_update's coef has MINRES_COEFS rows of b; MINRES_BREAKDOWN: its status 2 (LZ_MINRES_BREAKDOWN)
 MINRES_WORK_BLOCKS, MINRES_COEFS, MINRES_BREAKDOWN = 5, 7, 2
@@ -167,6 +170,14 @@ HIP_SYMBOLS = [
                                        _c_vp, _c_vp, _c_vp]),
     ("lz_pcg_cheb_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp,
                                    _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lz_csr_spmm_rowscale", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_dbl, _c_dbl,
+                                      _c_vp, _c_dbl, _c_vp, _c_dbl, _c_dbl, _c_vp, _c_vp, _c_vp]),
+    ("lz_cgzs_update", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                _c_vp, _c_vp]),
+    ("lz_cheb_jacobi_apply", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp,
+                                      _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lz_pcg_cheb_jacobi_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp,
+                                          _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_bcg_update", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_bcg_direction", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_bcg_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp,
@@ -267,6 +278,7 @@ HOST_SYMBOLS = [
                                 _c_vp, _c_vp]),
     ("lzh_pcg_scalars", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                  _c_vp, _c_vp, _c_vp]),
+    ("lzh_gershgorin_jacobi", _c_int, [_c_i64, _c_vp, _c_vp, _c_vp, _c_dbl, _c_vp]),
     ("lzh_cheb_precond_coeffs", _c_int, [_c_int, _c_dbl, _c_dbl, _c_vp]),
     ("lzh_cheb_precond_lo", _c_dbl, [_c_int, _c_dbl]),
     ("lzh_minres_start", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -445,6 +457,24 @@ def gershgorin(A: CsrHost):
     return float(out[0]), float(out[1])
 
 
+def gershgorin_jacobi(A: CsrHost, shift: float = 0.0):
+    """(lo, hi): the Gershgorin enclosure of N = D^-1/2 (A + shift I) D^-1/2, D the diagonal of A +
+    shift I (lzh_gershgorin_jacobi; fp64 whatever A's precision): N has a unit diagonal, so (1 - rad,
+    1 + rad) with rad = max_i sum_{j != i} |a_ij| / sqrt(d_i d_j).  What ChebPrecond(jacobi=True)
+    takes for hi.  Raises LanczosError when a d_i is not positive and finite."""
+    out = np.empty(2)
+    host = lambda t: t if isinstance(t, np.ndarray) else t.cpu().numpy()  # (a CsrDevice: copied back once)
+    val = np.ascontiguousarray(host(A.val), np.float64)
+    rc = host_lib().lzh_gershgorin_jacobi(A.n, _p(np.ascontiguousarray(host(A.row_ptr), np.int64)),
+                                          _p(np.ascontiguousarray(host(A.col), np.int32)), _p(val), float(shift),
+                                          _p(out))
+    if rc == -2:
+        raise LanczosError("gershgorin_jacobi: a row of A + shift I has a diagonal that is not positive and finite")
+    if rc:
+        raise LanczosError("lzh_gershgorin_jacobi failed (n >= 1, shift finite)")
+    return float(out[0]), float(out[1])
+
+
 def cheb_precond_lo(degree: int, hi: float) -> float:
     """The Chebyshev preconditioner's default lower end, hi / (4 (degree + 1)^2) (lzh_cheb_precond_lo)."""
     return float(host_lib().lzh_cheb_precond_lo(int(degree), float(hi)))
@@ -574,10 +604,13 @@ class ChebPrecondSpec(ctypes.Structure):
 class ChebPrecond:
     """Handle.solve(precond=ChebPrecond(...)): z = q(A + shift I) r, the Chebyshev semi-iteration's
     polynomial of `degree` SpMMs on [lo, hi].  hi None: the Gershgorin upper bound of A + shift I;
-    lo None: hi / (4 (degree + 1)^2)."""
+    lo None: hi / (4 (degree + 1)^2).  jacobi=True: the Jacobi-scaled form z = q(D^-1 M) D^-1 r, D the
+    diagonal of M = A + shift I, for a diagonal that varies; [lo, hi] then encloses D^-1/2 M D^-1/2
+    and hi None takes gershgorin_jacobi(A, shift)[1]."""
     degree: int = 8
     lo: Optional[float] = None
     hi: Optional[float] = None
+    jacobi: bool = False
 
 
 def _cheb_precond(pc) -> ChebPrecondSpec:
@@ -1149,6 +1182,27 @@ class Handle:
                                          a, _ptr(X), c, d, _ptr(Z), e, _ptr(U), _ptr(Y)), "lz_csr_spmm_axpby4")
         return Y
 
+    def spmm_rowscale(self, A: CsrDevice, s, a: float, g: float, X, e: float, U, c: float, d: float, Z, Y,
+                      dots=None, want_dots: bool = True):
+        """Y[i] = s_i (a (A X)[i] + g X[i] + e U[i]) + c X[i] + d Z[i] (lz_csr_spmm_rowscale), the step
+        of the Jacobi-scaled Chebyshev preconditioner.  s: n elements of A's dtype; X, U, Z, Y (n, b)
+        contiguous, Y distinct from the others; U is required, d == 0 never reads Z, which may then
+        be None.  Returns (Y, dots): the column dots of the stored Y with itself and with U as
+        col_dots(Y, U) returns them; want_dots=False: no dots are formed and dots is None."""
+        torch = _torch()
+        if U is None:
+            raise LanczosError("spmm_rowscale: U is required (LZ_E_ARG)")
+        n, b = self._blocks("spmm_rowscale", A, X, Y, Z, U)
+        if not torch.is_tensor(s) or s.dim() != 1 or s.numel() != n or s.dtype != A.val.dtype or not s.is_contiguous() \
+                or s.device != X.device:
+            raise LanczosError("spmm_rowscale: s is a contiguous 1-D device tensor of n elements of A's dtype (LZ_E_ARG)")
+        if want_dots:
+            dots = self._dots("spmm_rowscale", dots, 1, b, Y)
+        _check(self.L.lz_csr_spmm_rowscale(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
+                                           _ptr(s), a, g, _ptr(X), e, _ptr(U), c, d, _ptr(Z), _ptr(Y),
+                                           _ptr(dots) if want_dots else None), "lz_csr_spmm_rowscale")
+        return Y, (dots.view(2, b) if want_dots else None)
+
     def spmm_axpby4_dots(self, A: CsrDevice, a: float, X, c: float, d: float, Z, e: float, U, Y, dots=None):
         """spmm_axpby4 with U required (e != 0), and the column dots of the stored Y with itself and
         with U as col_dots(Y, U) returns them (lz_csr_spmm_axpby4_dots); returns (Y, dots)."""
@@ -1278,11 +1332,27 @@ class Handle:
                                     _ptr(Z), _ptr(rr)), "lz_cgz_update")
         return rr
 
-    def cheb_precond_apply(self, A: CsrDevice, precond, R, Z, work=None, shift: float = 0.0, dots=None):
+    def cgzs_update(self, coef, dinv, R, W, P, S, X, Z, Rs, rr=None):
+        """cgz_update that also writes Rs = dinv[:, None] * R of the stored R (lz_cgzs_update), the
+        update pass of the Jacobi-scaled Chebyshev preconditioner: the same bits in R, P, S, X and rr;
+        one rounded product per element of Rs, a frozen column's rewritten with the bits it held.
+        dinv: n elements of the blocks' dtype, read only; R, W, P, S, X, Z, Rs: (n, b) contiguous, of
+        one dtype, all seven pairwise distinct.  Returns rr (b fp64 on the device)."""
+        n, b = R.shape
+        rr = self._cg_update_args("cgzs_update", "R, W, P, S, X, Z, Rs", (R, W, P, S, X, Z, Rs), coef, "rr", rr, 1,
+                                  dinv)
+        _check(self.L.lz_cgzs_update(self.ptr, n, b, _dt(R), _ptr(coef), _ptr(dinv), _ptr(R), _ptr(W), _ptr(P),
+                                     _ptr(S), _ptr(X), _ptr(Z), _ptr(Rs), _ptr(rr)), "lz_cgzs_update")
+        return rr
+
+    def cheb_precond_apply(self, A: CsrDevice, precond, R, Z, work=None, shift: float = 0.0, dots=None, dinv=None):
         """Z = q(A + shift I) R, q the Chebyshev polynomial preconditioner `precond` (a ChebPrecond
         with lo and hi given, or (degree, lo, hi)), in exactly degree SpMMs (lz_cheb_precond_apply).
         work: flat, 2*n*b elements (allocated when None); R is only read.  Returns (Z, dots): dots[0] =
-        the column sums of Z * Z, dots[1] = those of Z * R, of the stored Z."""
+        the column sums of Z * Z, dots[1] = those of Z * R, of the stored Z.
+        dinv (n elements of A's dtype): the Jacobi-scaled form Z = q(D^-1 M) D^-1 R with D^-1 = dinv
+        (lz_cheb_jacobi_apply), [lo, hi] enclosing D^-1/2 M D^-1/2; Rs = dinv[:, None] * R is formed
+        here, one rounded product per element."""
         torch = _torch()
         n, b = self._blocks("cheb_precond_apply", A, R, Z)
         pc = _cheb_precond(precond)
@@ -1290,6 +1360,15 @@ class Handle:
             work = torch.empty(2 * n * b, dtype=R.dtype, device=R.device)
         self._work("cheb_precond_apply", work, n, b, R)
         dots = self._dots("cheb_precond_apply", dots, 1, b, Z)
+        if dinv is not None:
+            if not torch.is_tensor(dinv) or dinv.dim() != 1 or dinv.numel() != n or dinv.dtype != R.dtype \
+                    or not dinv.is_contiguous() or dinv.device != R.device:
+                raise LanczosError("cheb_precond_apply: dinv is a contiguous 1-D device tensor of n elements of A's dtype")
+            Rs = dinv[:, None] * R
+            _check(self.L.lz_cheb_jacobi_apply(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype,
+                                               b, float(shift), ctypes.addressof(pc), _ptr(dinv), _ptr(R), _ptr(Rs),
+                                               _ptr(Z), _ptr(work), _ptr(dots)), "lz_cheb_jacobi_apply")
+            return Z, dots.view(2, b)
         _check(self.L.lz_cheb_precond_apply(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b,
                                             float(shift), ctypes.addressof(pc), _ptr(R), _ptr(Z), _ptr(work),
                                             _ptr(dots)), "lz_cheb_precond_apply")
@@ -1419,6 +1498,20 @@ class Handle:
         (CHEB_PCG_WORK_BLOCKS); n_spmm = (degree + 1) iterations + starts + degree (starts with a live
         column).  The dict carries precond="chebyshev", precond_degree and precond_bounds=(lo, hi).
 
+        precond=ChebPrecond(..., jacobi=True), or "jacobi-chebyshev" for ChebPrecond(jacobi=True)
+        (lz_pcg_cheb_jacobi_solve; method="columns" only): the two combined, z = q(D^-1 M) D^-1 r = D^-1/2
+        q(N) D^-1/2 r with D the diagonal of M (Handle.jacobi, which raises on a diagonal that is not
+        positive) and N = D^-1/2 M D^-1/2; [lo, hi] encloses N's spectrum.  hi=None:
+        gershgorin_jacobi(A, shift)[1], the bound of the symmetric form (2 on a five-point stencil
+        whatever the coefficient; the Gershgorin bound of D^-1 M is useless on a varying diagonal);
+        lo=None: cheb_precond_lo(degree, hi).  For an operator whose diagonal varies AND whose stencil
+        is ill conditioned -- variable-coefficient diffusion, a heat step with a varying mass, a graph
+        Laplacian plus a shift -- where Jacobi still pays the grid's condition number and the plain
+        polynomial is harmful: about Jacobi's SpMMs in degree + 1 times fewer iterations.  Where
+        Jacobi alone already leaves a small condition number it gains nothing.  work is then 8 n b
+        elements (CHEB_JACOBI_PCG_WORK_BLOCKS); n_spmm as above.  The dict carries
+        precond="jacobi-chebyshev", precond_degree and precond_bounds=(lo, hi).
+
         method="minres" (lz_minres_solve, b <= 64): MINRES, for a symmetric A + shift I that may be
         indefinite (a Helmholtz-type operator, a saddle-point block, A - sigma I at a sigma inside the
         spectrum); the columns in lock step, each by its own scalars, as method="columns".  Same
@@ -1435,7 +1528,7 @@ class Handle:
         Returns a dict: X; iters, status (0 met tol on the measured residual, 1 iterations or
         restarts spent, 2 not positive definite), converged (status == 0), resid (measured), est
         (the recurrence's last value) -- NumPy arrays of b entries; restarts, n_spmm, iterations;
-        with a preconditioner also precond ("jacobi", "diagonal" or "chebyshev"; without one the dict is the one
+        with a preconditioner also precond ("jacobi", "diagonal", "chebyshev" or "jacobi-chebyshev"; without one the dict is the one
         it always was, so out.get("precond") is None); with method="block" also fallback (0 / 1)
         and stop (BCG_* reason of the last stop)."""
         torch = _torch()
@@ -1445,15 +1538,20 @@ class Handle:
             raise LanczosError(f'solve: method="{method}" takes no preconditioner')
         n, b = self._blocks("solve", A, B)
         dinv, kind, cheb = None, None, None
-        if isinstance(precond, ChebPrecond) or (isinstance(precond, str) and precond == "chebyshev"):
-            cp = ChebPrecond() if isinstance(precond, str) else precond
-            hi = gershgorin(A)[1] + float(shift) if cp.hi is None else float(cp.hi)
+        if isinstance(precond, ChebPrecond) or (isinstance(precond, str) and precond in ("chebyshev",
+                                                                                         "jacobi-chebyshev")):
+            cp = ChebPrecond(jacobi=precond == "jacobi-chebyshev") if isinstance(precond, str) else precond
+            if cp.jacobi:
+                dinv = self.jacobi(A, shift)
+                hi = gershgorin_jacobi(A, shift)[1] if cp.hi is None else float(cp.hi)
+            else:
+                hi = gershgorin(A)[1] + float(shift) if cp.hi is None else float(cp.hi)
             lo = cheb_precond_lo(cp.degree, hi) if cp.lo is None else float(cp.lo)
-            cheb, kind = _cheb_precond((cp.degree, lo, hi)), "chebyshev"
+            cheb, kind = _cheb_precond((cp.degree, lo, hi)), "jacobi-chebyshev" if cp.jacobi else "chebyshev"
         elif isinstance(precond, str):
             if precond != "jacobi":
-                raise LanczosError('solve: precond is None, "jacobi", "chebyshev", a ChebPrecond or a 1-D tensor of n '
-                                   'elements')
+                raise LanczosError('solve: precond is None, "jacobi", "chebyshev", "jacobi-chebyshev", a ChebPrecond or '
+                                   'a 1-D tensor of n elements')
             dinv, kind = self.jacobi(A, shift), "jacobi"
         elif precond is not None:
             dinv, kind = precond, "diagonal"
@@ -1470,8 +1568,9 @@ class Handle:
         else:
             self._blocks("solve", A, B, X0)
             X = X0.clone()
-        blocks = MINRES_WORK_BLOCKS if method == "minres" else CHEB_PCG_WORK_BLOCKS if cheb is not None \
-            else 4 if dinv is None else PCG_WORK_BLOCKS
+        blocks = MINRES_WORK_BLOCKS if method == "minres" \
+            else CHEB_JACOBI_PCG_WORK_BLOCKS if cheb is not None and dinv is not None \
+            else CHEB_PCG_WORK_BLOCKS if cheb is not None else 4 if dinv is None else PCG_WORK_BLOCKS
         work = self._work4("solve", work, n, b, B, blocks)
         if check_every is not None and check_every < 1:
             raise LanczosError("solve: check_every >= 1")
@@ -1485,6 +1584,9 @@ class Handle:
             _check(self.L.lz_bcg_solve(*args, *tail, _p(info)), "lz_bcg_solve")
         elif method == "minres":
             _check(self.L.lz_minres_solve(*args, *tail, _p(info)), "lz_minres_solve")
+        elif cheb is not None and dinv is not None:
+            _check(self.L.lz_pcg_cheb_jacobi_solve(*args, ctypes.addressof(cheb), _ptr(dinv), *tail, _p(info)),
+                   "lz_pcg_cheb_jacobi_solve")
         elif dinv is not None:
             _check(self.L.lz_pcg_solve(*args, _ptr(dinv), *tail, _p(info)), "lz_pcg_solve")
         elif cheb is not None:
@@ -1497,7 +1599,7 @@ class Handle:
             out.update(fallback=int(info[3]), stop=int(info[4]))
         elif method == "minres":
             out["method"] = "minres"
-        elif dinv is not None:
+        elif dinv is not None and cheb is None:
             out["precond"] = kind
         elif cheb is not None:
             out.update(precond=kind, precond_degree=cheb.degree, precond_bounds=(cheb.lo, cheb.hi))

@@ -381,8 +381,9 @@ static bool pairwise_apart(std::initializer_list<Span> s)
     return true;
 }
 
-// cg_solve as krylov_entry and the Inverse operator call it, for lz_cg_solve (dinv NULL), lz_pcg_solve and
-// lz_pcg_cheb_solve (pc): dinv goes in behind shift, in the operator's dtype, then the Chebyshev preconditioner
+// cg_solve as krylov_entry and the Inverse operator call it, for lz_cg_solve (dinv NULL), lz_pcg_solve,
+// lz_pcg_cheb_solve (pc) and lz_pcg_cheb_jacobi_solve (both): dinv goes in behind shift, in the operator's
+// dtype, then the Chebyshev preconditioner
 static auto cg_solve_with(const void *dinv, const lz_cheb_precond *pc = nullptr)
 {
     return [dinv, pc](lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, auto *val, int b,
@@ -2591,6 +2592,79 @@ int lz_pcg_cheb_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, c
     LZ_TRY(cheb_precond_args(pc));
     return krylov_entry(h, n, nnz, rp, col, val, dtype, b, kMaxB, shift, B, X, work, opts, iters, status, resid, est, info,
                         cg_solve_with(nullptr, pc), kChebPcgWorkBlocks);
+}
+
+int lz_csr_spmm_rowscale(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                         lz_dtype dtype, int b, const void *s, double a, double g, const void *X, double e,
+                         const void *U, double c, double d, const void *Z, void *Y, double *dots)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_TRY(shape_args(dtype, n, dots ? 1 : 0, b, kMaxB, "b in [1,64] (and n >= 1 with dots)"));
+    LZ_ARG_CHECK(s && X && U && Y && (Z || d == 0.0), "s/X/U/Y NULL, or Z NULL with d != 0");
+    const int64_t nb = n * b;
+    LZ_ARG_CHECK(apart(span_of(Y, nb, dtype),
+                       {span_of(X, nb, dtype), span_of(U, nb, dtype), d != 0.0 ? span_of(Z, nb, dtype) : Span{},
+                        span_of(s, n, dtype)}),
+                 "Y must not overlap X, U, Z or s");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return spmm_rowscale<T>(h, n, nnz, rp, col, (const T *)val, b,
+                                {(const T *)s, (T)a, (T)g, (const T *)X, (T)e, (const T *)U, (T)c, (T)d, (const T *)Z},
+                                (T *)Y, dots, ax3_fused(), ax3dot_fused());
+    });
+}
+
+int lz_cgzs_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *coef, const void *dinv, void *R,
+                   const void *W, void *P, void *S, void *X, const void *Z, void *Rs, double *rr)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
+    LZ_ARG_CHECK(coef && dinv && R && W && P && S && X && Z && Rs && rr, "coef/dinv/R/W/P/S/X/Z/Rs/rr NULL");
+    const int64_t nb = n * b;
+    LZ_ARG_CHECK(pairwise_apart({span_of(R, nb, dtype), span_of(W, nb, dtype), span_of(P, nb, dtype),
+                                 span_of(S, nb, dtype), span_of(X, nb, dtype), span_of(Z, nb, dtype),
+                                 span_of(Rs, nb, dtype), span_of(dinv, n, dtype)}),
+                 "R, W, P, S, X, Z, Rs and dinv must be pairwise distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);  // (Z is only read)
+        return cg_update<T>(h, n, b, coef, (T *)R, (const T *)W, (T *)P, (T *)S, (T *)X, (const T *)dinv,
+                            (T *)const_cast<void *>(Z), rr, (T *)Rs);
+    });
+}
+
+int lz_cheb_jacobi_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                         lz_dtype dtype, int b, double shift, const lz_cheb_precond *pc, const void *dinv, const void *R,
+                         const void *Rs, void *Z, void *work, double *dots)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
+    LZ_TRY(cheb_precond_args(pc));
+    LZ_ARG_CHECK(dinv && R && Rs && Z && work && std::isfinite(shift), "dinv/R/Rs/Z/work NULL, or shift not finite");
+    const int64_t nb = n * b;
+    LZ_ARG_CHECK(pairwise_apart({span_of(R, nb, dtype), span_of(Rs, nb, dtype), span_of(Z, nb, dtype),
+                                 span_of(work, 2 * nb, dtype), span_of(dinv, n, dtype)}),
+                 "dinv, R, Rs, Z and work must be pairwise distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return cheb_jacobi_apply<T>(h, n, nnz, rp, col, (const T *)val, b, shift, *pc, (const T *)dinv, (const T *)R,
+                                    (const T *)Rs, (T *)Z, (T *)work, dots, ax3_fused(), ax3dot_fused());
+    });
+}
+
+int lz_pcg_cheb_jacobi_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col,
+                             const void *val, lz_dtype dtype, int b, double shift, const lz_cheb_precond *pc,
+                             const void *dinv, const void *B, void *X, void *work, const lz_cg_opts *opts, int *iters,
+                             int *status, double *resid, double *est, int *info)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(cheb_precond_args(pc));
+    LZ_ARG_CHECK(dinv != nullptr, "dinv is NULL (lz_pcg_cheb_solve is the solve without the row scale)");
+    LZ_ARG_CHECK(dtype == LZ_F64 || dtype == LZ_F32, "dtype");
+    return krylov_entry(h, n, nnz, rp, col, val, dtype, b, kMaxB, shift, B, X, work, opts, iters, status, resid, est, info,
+                        cg_solve_with(dinv, pc), kChebJacobiPcgWorkBlocks,
+                        span_of(dinv, std::max<int64_t>(n, 0), dtype));
 }
 
 int lz_cheb_series_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,

@@ -1,13 +1,15 @@
 // lz_cg.hip -- batched conjugate gradients on M = A + shift I for b right-hand
 // sides in lock step, without a preconditioner, with a diagonal one or with a Chebyshev
-// polynomial of M: lz_cg_update, lz_cg_solve, lz_pcg_update,
-// lz_pcg_solve, lz_csr_jacobi, lz_cgz_update, lz_cheb_precond_apply, lz_pcg_cheb_solve.
+// polynomial of M, plain or Jacobi-scaled: lz_cg_update, lz_cg_solve,
+// lz_pcg_update, lz_pcg_solve, lz_csr_jacobi, lz_cgz_update, lz_cheb_precond_apply,
+// lz_pcg_cheb_solve, lz_cgzs_update, lz_cheb_jacobi_apply, lz_pcg_cheb_jacobi_solve.
 // One kernel family with a preconditioner switch:
 //   * k_cg_update: the row-local half of a Chronopoulos-Gear step with per-column
 //     device coefficients -- five blocks read, four written, slabs of the new
 //     residual's column dots; a 128-byte-row form and a generic one.  With a
 //     preconditioner also dinv read, Z = D^-1 r written and r.z beside r.r; with a block
-//     one (lz_cgz_update) Z = q(M) r is a sixth block, read only;
+//     one (lz_cgz_update) Z = q(M) r is a sixth block, read only; with the
+//     Jacobi-scaled one (lz_cgzs_update) also dinv read and Rs = D^-1 r written;
 //   * k_cg_start / k_cg_scalars / k_cg_live: one workgroup, the per-column rules
 //     of lz_cg.hpp on device memory only;
 //   * cg_solve: the host loop -- one fused SpMM with dots (gathering R, or Z), the
@@ -52,8 +54,9 @@ struct Vec16<float> {
 };
 
 // The update pass's preconditioner: none (z0 = r), diagonal (z0 = dinv r, Z written), or a
-// block Z = q(M) r some other kernel made (z0 = Z, read only).
-enum class CgPre { None, Diag, Block };
+// block Z = q(M) r some other kernel made (z0 = Z, read only), or that block and the row
+// scale (BlockDiag: Block, and Rs = dinv r written for the next application's first gather).
+enum class CgPre { None, Diag, Block, BlockDiag };
 
 // The preconditioner's streams, the update kernels' last argument: nothing without one.
 template <typename T, CgPre PRE>
@@ -66,6 +69,12 @@ struct Pre<T, CgPre::Diag> {
 template <typename T>
 struct Pre<T, CgPre::Block> {
     const T *__restrict__ Z;
+};
+template <typename T>
+struct Pre<T, CgPre::BlockDiag> {
+    const T *__restrict__ Z;
+    const T *__restrict__ dinv;
+    T *__restrict__ Rs;
 };
 
 // Both forms finish every element in this order, alpha and beta being the
@@ -82,6 +91,9 @@ struct Pre<T, CgPre::Block> {
 // frozen column's Z is rewritten with the bits it held.  Without PRE no dinv or Z
 // exists: nothing of them is read, multiplied or passed.
 // Block: z0 = Z[row], a sixth block that is only read; no dinv, nothing written to Z, r.r alone.
+// BlockDiag: Block, and with dv = dinv[row] also Rs = dv * r', one rounded product of the
+// stored r', a fifth block written (six read and the n-vector); a frozen column's Rs is
+// rewritten with the bits it held.  r.r alone.
 //
 // The 128-byte-row form (b = 16 fp64, b = 32 fp32; every block on 16 bytes):
 // lane t moves 16 bytes, columns VEC (t % 8) .. + VEC of row lane t / 8, so its
@@ -90,15 +102,17 @@ struct Pre<T, CgPre::Block> {
 // lanes of a column are summed in order through LDS into slab q: b doubles, PRE
 // [r.z (b) | r.r (b)].  NT: P, S, X and W move with non-temporal loads and stores
 // (nothing reads them again before a whole iteration has passed); R, which the
-// next SpMM gathers, always with plain ones.  ZNT: Z's store (Block: Z's load) non-temporal as well.
-template <typename T, bool NT, CgPre PRE, bool ZNT>
+// next SpMM gathers, always with plain ones.  ZNT: Z's store (Block, BlockDiag: Z's load)
+// non-temporal as well; RNT (BlockDiag): Rs's store too.
+template <typename T, bool NT, CgPre PRE, bool ZNT, bool RNT = false>
 __global__ __launch_bounds__(kCgThreads) void k_cg_update128(int64_t n, const double *__restrict__ coef,
                                                              T *__restrict__ R, const T *__restrict__ W,
                                                              T *__restrict__ P, T *__restrict__ S, T *__restrict__ X,
                                                              double *__restrict__ slabs, Pre<T, PRE> pre)
 {
     using V = typename Vec16<T>::type;
-    constexpr bool DIAG = PRE == CgPre::Diag;
+    constexpr bool DIAG = PRE == CgPre::Diag, BLOCK = PRE == CgPre::Block || PRE == CgPre::BlockDiag;
+    constexpr bool BDIAG = PRE == CgPre::BlockDiag;
     constexpr int VEC = 16 / (int)sizeof(T), B = 8 * VEC, K = DIAG ? 2 : 1;  // K partials; the last is r.r
     __shared__ double red[K][kCgThreads][VEC];
     const int tid = threadIdx.x, l = tid & 7, rl = tid >> 3;
@@ -113,20 +127,20 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update128(int64_t n, const do
     const int64_t step = (int64_t)gridDim.x * kCgRows128;
     for (int64_t row = (int64_t)blockIdx.x * kCgRows128 + rl; row < n; row += step) {
         const int64_t i = row * 8 + l;  // in 16-byte units
-        T dv = T(0);  // (Diag only)
-        if constexpr (DIAG) dv = pre.dinv[row];
+        T dv = T(0);  // (Diag, BlockDiag only)
+        if constexpr (DIAG || BDIAG) dv = pre.dinv[row];
         V r = reinterpret_cast<const V *>(R)[i];
         const V w = ldnt<NT>(reinterpret_cast<const V *>(W) + i);
         V p = ldnt<NT>(reinterpret_cast<const V *>(P) + i);
         V s = ldnt<NT>(reinterpret_cast<const V *>(S) + i);
         V x = ldnt<NT>(reinterpret_cast<const V *>(X) + i);
         V z;
-        if constexpr (PRE == CgPre::Block) z = ldnt<ZNT>(reinterpret_cast<const V *>(pre.Z) + i);
+        if constexpr (BLOCK) z = ldnt<ZNT>(reinterpret_cast<const V *>(pre.Z) + i);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
             T z0 = r[v];
             if constexpr (DIAG) z0 = dv * r[v];
-            if constexpr (PRE == CgPre::Block) z0 = z[v];
+            if constexpr (BLOCK) z0 = z[v];
             p[v] = be[v] == T(0) ? z0 : fma(be[v], p[v], z0);
             s[v] = be[v] == T(0) ? w[v] : fma(be[v], s[v], w[v]);
             x[v] = al[v] == T(0) ? x[v] : fma(al[v], p[v], x[v]);
@@ -136,12 +150,14 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update128(int64_t n, const do
                 acc[0][v] = fma((double)r[v], (double)z[v], acc[0][v]);
             }
             acc[K - 1][v] = fma((double)r[v], (double)r[v], acc[K - 1][v]);
+            if constexpr (BDIAG) z[v] = dv * r[v];  // (z0 is consumed: the register now holds Rs)
         }
         stnt<NT>(reinterpret_cast<V *>(P) + i, p);
         stnt<NT>(reinterpret_cast<V *>(S) + i, s);
         stnt<NT>(reinterpret_cast<V *>(X) + i, x);
         reinterpret_cast<V *>(R)[i] = r;
         if constexpr (DIAG) stnt<ZNT>(reinterpret_cast<V *>(pre.Z) + i, z);
+        if constexpr (BDIAG) stnt<RNT>(reinterpret_cast<V *>(pre.Rs) + i, z);
     }
 #pragma unroll
     for (int v = 0; v < VEC; ++v)
@@ -164,7 +180,7 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update_gen(int64_t n, const d
                                                               T *__restrict__ P, T *__restrict__ S, T *__restrict__ X,
                                                               double *__restrict__ slabs, Pre<T, PRE> pre, int b)
 {
-    constexpr bool DIAG = PRE == CgPre::Diag;
+    constexpr bool DIAG = PRE == CgPre::Diag, BDIAG = PRE == CgPre::BlockDiag;
     constexpr int K = DIAG ? 2 : 1;
     __shared__ double red[K][kCgThreads];
     const int tid = threadIdx.x, rpb = kCgThreads / b, rl = tid / b, c = tid - rl * b;
@@ -174,11 +190,11 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update_gen(int64_t n, const d
         const int64_t step = (int64_t)gridDim.x * rpb;
         for (int64_t row = (int64_t)blockIdx.x * rpb + rl; row < n; row += step) {
             const int64_t i = row * b + c;
-            T dv = T(0);  // (Diag only)
-            if constexpr (DIAG) dv = pre.dinv[row];
+            T dv = T(0);  // (Diag, BlockDiag only)
+            if constexpr (DIAG || BDIAG) dv = pre.dinv[row];
             T z0 = R[i];
             if constexpr (DIAG) z0 = dv * R[i];
-            if constexpr (PRE == CgPre::Block) z0 = pre.Z[i];
+            if constexpr (PRE == CgPre::Block || BDIAG) z0 = pre.Z[i];
             const T p = be == T(0) ? z0 : fma(be, P[i], z0);
             const T s = be == T(0) ? W[i] : fma(be, S[i], W[i]);
             const T x = al == T(0) ? X[i] : fma(al, p, X[i]);
@@ -192,6 +208,7 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_update_gen(int64_t n, const d
                 pre.Z[i] = z;
                 acc[0] = fma((double)r, (double)z, acc[0]);
             }
+            if constexpr (BDIAG) pre.Rs[i] = dv * r;
             acc[K - 1] = fma((double)r, (double)r, acc[K - 1]);
         }
     }
@@ -265,17 +282,29 @@ static bool cgz_z_nt()
     return !(e && e[0] == '0');
 }
 
+// LZ_CGZS_RS_NT=0 (read per call, measurement): lz_cgzs_update's Rs store plain, like R's.
+// Shipped non-temporal, as the diagonal form's Z store, which the next SpMM gathers as well
+// (DESIGN.md 25, 30).
+static bool cgzs_rs_nt()
+{
+    const char *e = getenv("LZ_CGZS_RS_NT");
+    return !(e && e[0] == '0');
+}
+
 // One update: the kernel, then the fold of its G slabs into dots -- b doubles each
 // into r.r, or with a diagonal preconditioner (dinv and Z given) 2 b each into [r.z |
 // r.r]; Z without dinv: the block form, Z only read, b doubles into r.r; without a
-// preconditioner both are NULL.  h->dots_ws must hold them (dots_reserve(h, n, b, kCgGridCap)).
+// preconditioner both are NULL.  Rs given (with dinv and Z): the block form that also writes Rs =
+// dinv r (lz_cgzs_update), b doubles into r.r.  h->dots_ws must hold them (dots_reserve(h, n, b,
+// kCgGridCap)).
 template <typename T>
 static int cg_update_launch(lz_handle *h, int64_t n, int b, const double *coef, T *R, const T *W, T *P, T *S, T *X,
-                            const T *dinv, T *Z, double *dots)
+                            const T *dinv, T *Z, double *dots, T *Rs = nullptr)
 {
     const bool al16 = ((reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(W) |
                         reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(S) |
-                        reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Z)) & 15) == 0;
+                        reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Z) |
+                        reinterpret_cast<uintptr_t>(Rs)) & 15) == 0;
     const bool rows128 = (int64_t)b * (int64_t)sizeof(T) == 128 && al16 && !cg_force_generic();
     const int64_t rpb = rows128 ? kCgRows128 : kCgThreads / b;
     const int G = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, rpb), kCgGridCap));
@@ -286,9 +315,18 @@ static int cg_update_launch(lz_handle *h, int64_t n, int b, const double *coef, 
     const Pre<T, CgPre::None> none;
     const Pre<T, CgPre::Diag> pre{dinv, Z};
     const Pre<T, CgPre::Block> blk{Z};
+    const Pre<T, CgPre::BlockDiag> bd{Z, dinv, Rs};
     const bool nt = cg_nt();
     const int ev = prof_begin(h, PROF_UPDATE_PASS);
-    if (!dinv && !Z) {
+    if (Rs) {
+        const bool znt = cgz_z_nt(), rnt = cgzs_rs_nt();
+        if (!rows128) run(k_cg_update_gen<T, CgPre::BlockDiag>, bd, b);
+        else if (!nt) run(k_cg_update128<T, false, CgPre::BlockDiag, false, false>, bd);
+        else if (znt && rnt) run(k_cg_update128<T, true, CgPre::BlockDiag, true, true>, bd);
+        else if (znt) run(k_cg_update128<T, true, CgPre::BlockDiag, true, false>, bd);
+        else if (rnt) run(k_cg_update128<T, true, CgPre::BlockDiag, false, true>, bd);
+        else run(k_cg_update128<T, true, CgPre::BlockDiag, false, false>, bd);
+    } else if (!dinv && !Z) {
         if (!rows128) run(k_cg_update_gen<T, CgPre::None>, none, b);
         else if (nt) run(k_cg_update128<T, true, CgPre::None, false>, none);
         else run(k_cg_update128<T, false, CgPre::None, false>, none);
@@ -305,20 +343,20 @@ static int cg_update_launch(lz_handle *h, int64_t n, int b, const double *coef, 
     }
     prof_end(h, ev);
     LZ_LAUNCH_CHECK();
-    return dinv ? dots_fold(h, G, b, dots) : slabs_fold(h, G, b, dots);
+    return dinv && !Rs ? dots_fold(h, G, b, dots) : slabs_fold(h, G, b, dots);
 }
 
 template <typename T>
 int cg_update(lz_handle *h, int64_t n, int b, const double *coef, T *R, const T *W, T *P, T *S, T *X, const T *dinv,
-              T *Z, double *dots)
+              T *Z, double *dots, T *Rs)
 {
     LZ_TRY(dots_reserve(h, n, b, kCgGridCap));
-    return cg_update_launch<T>(h, n, b, coef, R, W, P, S, X, dinv, Z, dots);
+    return cg_update_launch<T>(h, n, b, coef, R, W, P, S, X, dinv, Z, dots, Rs);
 }
 template int cg_update<double>(lz_handle *, int64_t, int, const double *, double *, const double *, double *, double *,
-                               double *, const double *, double *, double *);
+                               double *, const double *, double *, double *, double *);
 template int cg_update<float>(lz_handle *, int64_t, int, const double *, float *, const float *, float *, float *,
-                              float *, const float *, float *, double *);
+                              float *, const float *, float *, double *, float *);
 
 // lz_csr_jacobi.  A group of kJacobiLanes lanes per row, kJacobiRows rows per
 // workgroup.  The group walks its row kJacobiLanes positions at a time; each pass
@@ -487,9 +525,62 @@ template int cheb_precond_apply<float>(lz_handle *, int64_t, int64_t, const int6
                                        double, const lz_cheb_precond &, const float *, float *, float *, double *, bool,
                                        bool);
 
-// The solve; dinv: the diagonal preconditioner, pc: the Chebyshev one, at most one of them
-// given.  work = [R | W | P | S], then Z with a preconditioner, then the Chebyshev one's two
-// blocks.  A verification (the start step) follows every phase of iterations, so resid is
+// Z = q(D^-1 M) D^-1 R, the Jacobi-scaled polynomial: cheb_precond_apply's
+// steps, coefficients and buffer rotation with every M z become dinv (M z) and r become Rs =
+// dinv R (the caller's, read only), so each step is one row-scaled store with U = R:
+//   step 1:  Y = dinv (a_1 A Rs + a_1 sg Rs + c_1 R);
+//   step j:  Y = dinv (a_j A z_j + a_j sg z_j + e_j R) + c_j z_j + d_j z_{j-1}  (Z NULL at j = 2: d = 0).
+// dots != NULL: [Z.Z | Z.R] of the stored Z out of the last step's store.  No host synchronisation.
+template <typename T>
+int cheb_jacobi_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                      double shift, const lz_cheb_precond &pc, const T *dinv, const T *R, const T *Rs, T *Z, T *work,
+                      double *dots, bool fused, bool fused_dot)
+{
+    double cf[4 * kChebPrecondMaxDegree];
+    cheb_precond_coeffs(pc.degree, pc.lo, pc.hi, cf);
+    const double sg = (double)(T)shift;
+    const int D = pc.degree;
+    T *buf[3] = {work, work + n * b, Z};
+    auto out = [&](int i) { return buf[((i + 2 - D) % 3 + 3) % 3]; };
+    LZ_TRY(spmm_rowscale<T>(h, n, nnz, rp, col, val, b,
+                            {dinv, T(cf[0]), T(cf[0] * sg), Rs, T(cf[1]), R, T(0), T(0), nullptr}, out(1),
+                            D == 1 ? dots : nullptr, fused, fused_dot));
+    for (int i = 2; i <= D; ++i) {
+        const double *c = cf + 4 * (i - 1);
+        LZ_TRY(spmm_rowscale<T>(h, n, nnz, rp, col, val, b,
+                                {dinv, T(c[0]), T(c[0] * sg), out(i - 1), T(c[3]), R, T(c[1]), T(c[2]),
+                                 i == 2 ? nullptr : out(i - 2)},
+                                out(i), i == D ? dots : nullptr, fused, fused_dot));
+    }
+    return LZ_OK;
+}
+template int cheb_jacobi_apply<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *,
+                                       int, double, const lz_cheb_precond &, const double *, const double *,
+                                       const double *, double *, double *, double *, bool, bool);
+template int cheb_jacobi_apply<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
+                                      double, const lz_cheb_precond &, const float *, const float *, const float *,
+                                      float *, float *, double *, bool, bool);
+
+// Rs = dinv R on n x b blocks: k_pcg_scale (its r.z slabs, left in h->dots_ws, are not folded)
+template <typename T>
+int row_scale(lz_handle *h, int64_t n, int b, const T *dinv, const T *R, T *Rs)
+{
+    if (n <= 0) return LZ_OK;
+    LZ_TRY(dots_reserve(h, n, b, kCgGridCap));
+    const int64_t rpb = kCgThreads / b;
+    const int G = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, rpb), kCgGridCap));
+    const int ev = prof_begin(h, PROF_UPDATE_PASS);
+    hipLaunchKernelGGL((k_pcg_scale<T>), dim3(G), dim3(kCgThreads), 0, h->stream, n, b, dinv, R, Rs, h->dots_ws);
+    prof_end(h, ev);
+    LZ_LAUNCH_CHECK();
+    return LZ_OK;
+}
+template int row_scale<double>(lz_handle *, int64_t, int, const double *, const double *, double *);
+template int row_scale<float>(lz_handle *, int64_t, int, const float *, const float *, float *);
+
+// The solve; dinv: the diagonal preconditioner, pc: the Chebyshev one; both: the Jacobi-scaled
+// polynomial.  work = [R | W | P | S], then Z with a preconditioner, then the Chebyshev one's two
+// blocks, then the Jacobi-scaled one's Rs.  A verification (the start step) follows every phase of iterations, so resid is
 // always a measured residual.
 template <typename T>
 int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
@@ -502,10 +593,14 @@ int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int3
     const int pre = dinv != nullptr || pc != nullptr;
     const int64_t nb = n * b;
     T *R = work, *W = work + nb, *P = work + 2 * nb, *S = work + 3 * nb, *Z = pre ? work + 4 * nb : nullptr;
+    T *Rs = dinv && pc ? work + 7 * nb : nullptr;
     // the Chebyshev application: its dots [z.z | r.z] at rec - b, so r.z lands in rec[0 .. b)
     int live_starts = 0;
     auto precondition = [&]() -> int {
         double *zd = reinterpret_cast<double *>(reinterpret_cast<char *>(st) + offsetof(CgState, rec)) - b;
+        if (Rs)
+            return cheb_jacobi_apply<T>(h, n, nnz, rp, col, val, b, shift, *pc, dinv, R, Rs, Z, work + 5 * nb, zd, true,
+                                        true);
         return cheb_precond_apply<T>(h, n, nnz, rp, col, val, b, shift, *pc, R, Z, work + 5 * nb, zd, true, true);
     };
     const T *D = pre ? Z : R;  // the search direction's source, what the SpMM gathers
@@ -524,7 +619,7 @@ int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int3
     auto start = [&](bool initial) -> int {
         LZ_TRY(spmm_terms<T>(h, n, nnz, rp, col, val, b, {T(-1), X, -sg, T(1), B}, R, st->sd));
         ++n_spmm;
-        if (dinv) {
+        if (dinv && !pc) {
             const int64_t rpb = kCgThreads / b;
             const int G = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, rpb), kCgGridCap));
             const int ev = prof_begin(h, PROF_UPDATE_PASS);
@@ -541,6 +636,7 @@ int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int3
         // so the verification that ends a solve pays none)
         if (pc && nlive > 0) {
             ++live_starts;
+            if (Rs) LZ_TRY(row_scale<T>(h, n, b, dinv, R, Rs));
             LZ_TRY(precondition());
         }
         return LZ_OK;
@@ -556,7 +652,7 @@ int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int3
                 hipLaunchKernelGGL(k_cg_scalars, dim3(1), dim3(kMaxB), 0, h->stream, st, b, tol2, o.max_iter,
                                    first ? 1 : 0, pre);
                 LZ_LAUNCH_CHECK();
-                LZ_TRY(cg_update_launch<T>(h, n, b, st->coef, R, W, P, S, X, dinv, Z, pc ? st->rec + b : st->rec));
+                LZ_TRY(cg_update_launch<T>(h, n, b, st->coef, R, W, P, S, X, dinv, Z, pc ? st->rec + b : st->rec, Rs));
                 if (pc) LZ_TRY(precondition());
                 first = false;
             }

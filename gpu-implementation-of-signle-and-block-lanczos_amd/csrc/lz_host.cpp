@@ -704,6 +704,39 @@ int lzh_gershgorin(int64_t n, const int64_t *row_ptr, const int32_t *col, const 
     return 0;
 }
 
+// The enclosure of N = D^-1/2 M D^-1/2, M = A + shift I, D = diag(M): with s_i =
+// 1 / d_i and rad_i = sum_{j != i} |a_ij| sqrt(s_i s_j), N's diagonal is 1 and its Gershgorin
+// discs are [1 - rad_i, 1 + rad_i].  d_i: the row's stored diagonal entries summed left to
+// right, then the shift, as lz_csr_jacobi forms it.
+int lzh_gershgorin_jacobi(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val, double shift,
+                          double out[2])
+{
+    if (n < 1 || !row_ptr || !out || !std::isfinite(shift) || (row_ptr[n] > 0 && (!col || !val))) return -1;
+    std::vector<double> s((size_t)n);
+    int64_t bad = 0;
+#pragma omp parallel for reduction(+ : bad) schedule(static)
+    for (int64_t r = 0; r < n; ++r) {
+        double d = 0.0;
+        for (int64_t k = row_ptr[r]; k < row_ptr[r + 1]; ++k)
+            if (col[k] == r) d += val[k];
+        d += shift;
+        if (!(d > 0.0) || !std::isfinite(d)) ++bad;
+        s[(size_t)r] = 1.0 / d;
+    }
+    if (bad) return -2;
+    double rmax = 0.0;
+#pragma omp parallel for reduction(max : rmax) schedule(static)
+    for (int64_t r = 0; r < n; ++r) {
+        double rad = 0.0;
+        for (int64_t k = row_ptr[r]; k < row_ptr[r + 1]; ++k)
+            if (col[k] != r) rad += std::fabs(val[k]) * std::sqrt(s[(size_t)r] * s[(size_t)col[k]]);
+        rmax = std::max(rmax, rad);
+    }
+    out[0] = 1.0 - rmax;
+    out[1] = 1.0 + rmax;
+    return 0;
+}
+
 // ---- batched conjugate gradients: the per-column rules of lz_cg.hpp, as k_cg_start and
 // k_cg_scalars apply them, on host arrays of b entries
 int lzh_cg_start(int b, int max_iter, int initial, const double *gamma, const double *rec, const double *thr,

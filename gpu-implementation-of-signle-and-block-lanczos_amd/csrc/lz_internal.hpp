@@ -35,6 +35,26 @@ struct SpmmTerms {
 template <typename T>
 int spmm_terms(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
                SpmmTerms<T> t, T *Y, double *dots = nullptr, bool fused = true, bool fused_dot = true);
+// The terms of Y = diag(s) (a A X + g X + e U) + c X + d Z (lz_csr_spmm_rowscale): s n
+// elements, X / Z / U / Y n x b row-major with ld = b, Y distinct from the others; U is
+// required, d == 0 never reads Z.
+template <typename T>
+struct RowScaleTerms {
+    const T *s;
+    T a, g;
+    const T *X;
+    T e;
+    const T *U;
+    T c, d;
+    const T *Z;
+};
+// Y = those terms on a square operator.  spmm_terms' shapes leave k_spmm_seg's store
+// (SegStore::RowScale, last_kernel | LZ_K_RSC; with dots and fused_dot RowScaleDots, |
+// LZ_K_DOT); else, or fused = false: spmm_rm, one row-local kernel, col_dots -- the same
+// bits in Y.  dots != nullptr: [Y.Y | Y.U] of the stored Y.
+template <typename T>
+int spmm_rowscale(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                  RowScaleTerms<T> t, T *Y, double *dots = nullptr, bool fused = true, bool fused_dot = true);
 // R = A X - X diag(theta) and dots = [R.R | R.X] of the stored R (lz_csr_spmm_resid): theta b
 // device doubles, each rounded to T once.  spmm_terms' shapes leave k_spmm_seg's store
 // (SegStore::ShiftDots, last_kernel | LZ_K_RESID, slabs in h->dots_ws); else, or fused =
@@ -73,11 +93,14 @@ constexpr int kJacobiLanes = 8, kJacobiRows = kCgThreads / kJacobiLanes, kPcgWor
 // The Chebyshev polynomial preconditioner: its highest degree, and the solve's
 // work with it, [R | W | P | S | Z | T0 | T1].
 constexpr int kChebPrecondMaxDegree = 64, kChebPcgWorkBlocks = 7;
-// lz_cg_update (dinv = Z = NULL, dots: b), lz_pcg_update (dots: 2 b) and lz_cgz_update (dinv = NULL,
-// Z given and only read, dots: b) (include/lz_hip.h)
+// The Jacobi-scaled one: Rs = D^-1 R behind them, [R | W | P | S | Z | T0 | T1 | Rs].
+constexpr int kChebJacobiPcgWorkBlocks = 8;
+// lz_cg_update (dinv = Z = NULL, dots: b), lz_pcg_update (dots: 2 b), lz_cgz_update (dinv = NULL,
+// Z given and only read, dots: b) and lz_cgzs_update (dinv, Z only read, Rs written, dots: b)
+// (include/lz_hip.h)
 template <typename T>
 int cg_update(lz_handle *h, int64_t n, int b, const double *coef, T *R, const T *W, T *P, T *S, T *X, const T *dinv,
-              T *Z, double *dots);
+              T *Z, double *dots, T *Rs = nullptr);
 // lz_csr_jacobi (include/lz_hip.h); synchronises the stream once (the count)
 template <typename T>
 int csr_jacobi(lz_handle *h, int64_t n, const int64_t *rp, const int32_t *col, const T *val, double shift, T *dinv,
@@ -87,7 +110,16 @@ template <typename T>
 int cheb_precond_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
                        double shift, const lz_cheb_precond &pc, const T *R, T *Z, T *work, double *dots, bool fused,
                        bool fused_dot);
-// lz_cg_solve (dinv = pc = NULL), lz_pcg_solve (dinv) and lz_pcg_cheb_solve (pc) (include/lz_hip.h)
+// lz_cheb_jacobi_apply (include/lz_hip.h); Rs: the caller's dinv R
+template <typename T>
+int cheb_jacobi_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                      double shift, const lz_cheb_precond &pc, const T *dinv, const T *R, const T *Rs, T *Z, T *work,
+                      double *dots, bool fused, bool fused_dot);
+// Rs = dinv R (n x b, ld = b), the row-local launch of a start; no host synchronisation
+template <typename T>
+int row_scale(lz_handle *h, int64_t n, int b, const T *dinv, const T *R, T *Rs);
+// lz_cg_solve (dinv = pc = NULL), lz_pcg_solve (dinv), lz_pcg_cheb_solve (pc) and
+// lz_pcg_cheb_jacobi_solve (both) (include/lz_hip.h)
 template <typename T>
 int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
              double shift, const T *dinv, const lz_cheb_precond *pc, const T *B, T *X, T *work, const lz_cg_opts &o,

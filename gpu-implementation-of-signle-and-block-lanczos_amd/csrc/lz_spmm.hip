@@ -429,6 +429,47 @@ __device__ __forceinline__ Vec<T, VEC> term_piece(Vec<T, VEC> s, const T *__rest
     return s;
 }
 
+// Row-scaled term row piece (the RowScale stores, lz_csr_spmm_rowscale): from the
+// finished SpMM piece y of a row, s_i (a y + g x + e u) + c x + d z with x, z, u the lane's own
+// 16-B pieces of X[row], Z[row], U[row] and s_i = S[row], one element per row: a plain load,
+// the same address in the row's eight lanes, so one request serves them.  U is required and,
+// as Z, streamed with non-temporal loads (term_piece's); Z == nullptr exactly when d == 0,
+// a test uniform over the launch, and Z is never read then.  One arithmetic order, which
+// k_rowscale_rows repeats on the stored row:
+//   t = fma(a, y, fma(g, x, e u));  o = Z ? fma(c, x, d z) : c x;  Y = fma(s_i, t, o).
+// s_i and the u piece are loaded here, after the gather, and are dead before the next tile's:
+// nothing of this store is live across the MODE 1 gather but the operands' pointers and
+// coefficients.  uo: the u piece, for the column dots.
+template <typename T, int VEC>
+__device__ __forceinline__ Vec<T, VEC> rowscale_piece(Vec<T, VEC> y, const T *__restrict__ xrow,
+                                                      const T *__restrict__ Z, const T *__restrict__ U,
+                                                      const T *__restrict__ S, int64_t row, int64_t o, T a, T g, T e,
+                                                      T c, T d, Vec<T, VEC> *uo = nullptr)
+{
+    static_assert(sizeof(T) * VEC == 16, "128-B rows: 16-B pieces");
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const bool hz = Z != nullptr;
+    const Vec<T, VEC> x = ldv<T, VEC>(xrow);
+    const T si = S[row];
+    Vec<T, VEC> z, u;
+    {
+        const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(U + o));
+        __builtin_memcpy(&u, &r, 16);
+    }
+    if (hz) {
+        const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(Z + o));
+        __builtin_memcpy(&z, &r, 16);
+    }
+    if (uo) *uo = u;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+        const T t = fma(a, y.v[i], fma(g, x.v[i], e * u.v[i]));
+        const T w = hz ? fma(c, x.v[i], d * z.v[i]) : c * x.v[i];
+        y.v[i] = fma(si, t, w);
+    }
+    return y;
+}
+
 // Column dots at the fused store (Terms3Dots, lz_csr_spmm_axpby_dots): a lane's running
 // y.y and y.x of the pieces it stores -- always the same 16-B column piece, since
 // the store loops step by 256 lanes and a row has 8 -- in fp64 for both dtypes
@@ -540,8 +581,14 @@ __device__ __forceinline__ int xcc_id()
 //   Terms4Dots  lz_csr_spmm_axpby4_dots: Terms4's stored row, and Terms3Dots' slabs with U's rows
 //               in X's place: the column dots of the stored rows with themselves and with U's
 //               (U is required: e != 0).
+//   RowScale    lz_csr_spmm_rowscale: Y[row] = s_row (a y + g X[row] + e U[row]) + c X[row] +
+//               d Z[row], s an n-vector (U is required; Z == nullptr when d == 0), rowscale_piece.
+//   RowScaleDots  RowScale's stored row, and Terms4Dots' slabs: the column dots of the stored
+//               rows with themselves and with U's.
 // Only Rows and ColMajor have windowed (WIN) launches; only Rows the diagnostic build's PF.
-enum class SegStore { Rows, ColMajor, Beta2, Terms3, Terms3Dots, Terms4, ShiftDots, Terms4Dots };
+enum class SegStore {
+    Rows, ColMajor, Beta2, Terms3, Terms3Dots, Terms4, ShiftDots, Terms4Dots, RowScale, RowScaleDots
+};
 
 constexpr bool seg_terms(SegStore st)
 {
@@ -551,10 +598,14 @@ constexpr bool seg_terms(SegStore st)
 // the term stores with the fourth term e U
 constexpr bool seg_four(SegStore st) { return st == SegStore::Terms4 || st == SegStore::Terms4Dots; }
 
+// the row-scaled term stores
+constexpr bool seg_rowscale(SegStore st) { return st == SegStore::RowScale || st == SegStore::RowScaleDots; }
+
 // the stores that leave a slab of column dots per tile
 constexpr bool seg_dots(SegStore st)
 {
-    return st == SegStore::Terms3Dots || st == SegStore::Terms4Dots || st == SegStore::ShiftDots;
+    return st == SegStore::Terms3Dots || st == SegStore::Terms4Dots || st == SegStore::ShiftDots ||
+           st == SegStore::RowScaleDots;
 }
 
 // the store's bits of lz_debug_last_kernel's SpMM word
@@ -562,17 +613,20 @@ constexpr int seg_store_bits(SegStore st)
 {
     return (st == SegStore::ColMajor ? LZ_K_YCM : 0) | (st == SegStore::Beta2 ? LZ_K_EPI : 0) |
            (seg_terms(st) ? LZ_K_AX3 : 0) | (seg_terms(st) && seg_dots(st) ? LZ_K_DOT : 0) |
-           (seg_four(st) ? LZ_K_AX4 : 0) | (st == SegStore::ShiftDots ? LZ_K_RESID : 0);
+           (seg_four(st) ? LZ_K_AX4 : 0) | (st == SegStore::ShiftDots ? LZ_K_RESID : 0) |
+           (seg_rowscale(st) ? LZ_K_RSC : 0) | (st == SegStore::RowScaleDots ? LZ_K_DOT : 0);
 }
 
 // What the stores read or write besides Y; a field is dead in the launches of the other stores
 template <typename T>
 struct SegOperands {
     const T *Wprev = nullptr, *M = nullptr;  // Beta2
-    const T *Z = nullptr, *U = nullptr;      // the term stores (U: Terms4, Terms4Dots)
+    const T *Z = nullptr, *U = nullptr;      // the term stores (U: Terms4, Terms4Dots, RowScale, RowScaleDots)
     T a = T(0), c = T(0), d = T(0), e = T(0);
-    double *dots = nullptr;                  // Terms3Dots, Terms4Dots, ShiftDots: the tiles' slabs
+    double *dots = nullptr;                  // Terms3Dots, Terms4Dots, ShiftDots, RowScaleDots: the tiles' slabs
     const double *cshift = nullptr;          // ShiftDots: theta, B doubles
+    const T *s = nullptr;                    // RowScale, RowScaleDots: the row scale, n elements
+    T g = T(0);                              // ... and the coefficient of X inside the scaled sum
 };
 
 // a store loop's lane state: the dots (dead without them) and, ShiftDots, the coefficients
@@ -604,6 +658,11 @@ __device__ __forceinline__ void seg_store_piece(Vec<T, VEC> &y, int64_t row, int
                                              ops.c, ops.d, ops.e, ST == SegStore::Terms3Dots ? &x : nullptr,
                                              ST == SegStore::Terms4Dots ? &x : nullptr);
         if constexpr (seg_dots(ST)) dacc.add(y, x);
+    } else if constexpr (seg_rowscale(ST)) {
+        [[maybe_unused]] Vec<T, VEC> u;  // the piece the dots pair with: U's
+        y = rowscale_piece<T, VEC>(y, X + row * ldx + pc * VEC, ops.Z, ops.U, ops.s, row, row * B + pc * VEC, ops.a,
+                                   ops.g, ops.e, ops.c, ops.d, ST == SegStore::RowScaleDots ? &u : nullptr);
+        if constexpr (ST == SegStore::RowScaleDots) dacc.add(y, u);
     }
 }
 
@@ -611,11 +670,15 @@ template <typename T, int B, int TR, int CAP, bool WIN, int MODE, SegStore ST = 
 __global__ __launch_bounds__(256) void k_spmm_seg(int64_t n, const int64_t *__restrict__ rp,
                                                   const int32_t *__restrict__ col,
                                                   const T *__restrict__ val,
-                                                  const T *__restrict__ X, int64_t ldx, int64_t nx,
-                                                  T *__restrict__ Y, int64_t ldy, int *__restrict__ longq,
+                                                  const T *__restrict__ X, int64_t ldx_arg, int64_t nx,
+                                                  T *__restrict__ Y, int64_t ldy_arg, int *__restrict__ longq,
                                                   int parity, const SegOperands<T> ops, int diag,
                                                   int *__restrict__ pfc)
 {
+    // (the row-scaled stores' blocks all have ld = B: a constant there, which frees the SGPRs of two
+    // arguments for s and g -- without it the fp32 MODE 1 launches spill 2 to 4 SGPRs; every other
+    // store reads its arguments as before)
+    const int64_t ldx = seg_rowscale(ST) ? (int64_t)B : ldx_arg, ldy = seg_rowscale(ST) ? (int64_t)B : ldy_arg;
     // MODE 0: tiles whose run exceeds the stage (or, WIN, whose columns exceed
     //         the window) are queued (longq[0] = count, longq[1..] = tile ids)
     //         for MODE 1, so their code path costs the main kernel no registers;
@@ -2005,6 +2068,79 @@ template int spmm_terms<double>(lz_handle *, int64_t, int64_t, const int64_t *, 
                                 SpmmTerms<double>, double *, double *, bool, bool);
 template int spmm_terms<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
                                SpmmTerms<float>, float *, double *, bool, bool);
+
+// The row-local pass of the two-launch row-scaled step: rowscale_piece's arithmetic on the
+// stored SpMM row, over n rows of b contiguous elements (ld = b), 64-bit indices; Z ==
+// nullptr: d == 0, and Z is not read.
+template <typename T>
+__global__ __launch_bounds__(256) void k_rowscale_rows(int64_t nb, int b, T a, T g, T e, T c, T d,
+                                                       const T *__restrict__ S, const T *__restrict__ X,
+                                                       const T *__restrict__ Z, const T *__restrict__ U,
+                                                       T *__restrict__ Y)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nb; i += (int64_t)gridDim.x * 256) {
+        const T t = fma(a, Y[i], fma(g, X[i], e * U[i]));
+        const T w = Z ? fma(c, X[i], d * Z[i]) : c * X[i];
+        Y[i] = fma(S[i / b], t, w);
+    }
+}
+
+// Y = diag(s) (a A X + g X + e U) + c X + d Z (lz_csr_spmm_rowscale): square operator, ld = b
+// everywhere, U required.  The row leaves k_spmm_seg's store (RowScale, | LZ_K_RSC) under
+// spmm_terms' conditions; fused = false or any other shape: spmm_rm, then k_rowscale_rows --
+// the same bits.  dots: [Y.Y | Y.U] of the stored Y, from the store too (RowScaleDots, |
+// LZ_K_DOT, a slab per 48-row tile folded by dots_fold) unless fused_dot = false, else the
+// streaming col_dots.
+template <typename T>
+int spmm_rowscale(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
+                  RowScaleTerms<T> t, T *Y, double *dots, bool fused, bool fused_dot)
+{
+    if (n <= 0) return LZ_OK;
+    if (t.d == T(0)) t.Z = nullptr;
+    const bool rows128 = (int64_t)b * (int64_t)sizeof(T) == 128;
+    const bool buf_ok = n * b * (int64_t)sizeof(T) < (1LL << 31) && n < (1 << 24);
+    const bool al16 = ((reinterpret_cast<uintptr_t>(t.X) | reinterpret_cast<uintptr_t>(Y) |
+                        reinterpret_cast<uintptr_t>(t.Z) | reinterpret_cast<uintptr_t>(t.U)) & 15) == 0;
+    const char *fz = getenv("LZ_SPMM_FNZ");  // (the fixed-nnz experiment has no fused store)
+    if (fused && rows128 && buf_ok && al16 && !(fz && fz[0] == '1')) {
+        constexpr int B = 128 / (int)sizeof(T);
+        const bool store_dots = dots && fused_dot;
+        SegOperands<T> ops;
+        ops.Z = t.Z, ops.U = t.U, ops.s = t.s;
+        ops.a = t.a, ops.g = t.g, ops.e = t.e, ops.c = t.c, ops.d = t.d;
+        if (store_dots) {
+            LZ_TRY(dots_reserve(h, n, b));
+            ops.dots = h->dots_ws;
+        }
+        auto seg = [&](auto store) {
+            constexpr SegStore ST = decltype(store)::value;
+            return by_stage<ST>(seg_stage(n, nnz), false, [&](auto cap, auto win) {
+                return launch_seg<T, B, 48, decltype(cap)::value, decltype(win)::value, ST>(
+                    h, n, rp, col, val, t.X, B, n, Y, B, ops, -1, nullptr);
+            });
+        };
+        const int ev = prof_begin(h, PROF_SPMM);
+        const int rc = store_dots ? seg(std::integral_constant<SegStore, SegStore::RowScaleDots>{})
+                                  : seg(std::integral_constant<SegStore, SegStore::RowScale>{});
+        prof_end(h, ev);
+        LZ_TRY(rc);
+        LZ_LAUNCH_CHECK();
+        if (store_dots) return dots_fold(h, ceil_div(n, (int64_t)48), b, dots);
+    } else {
+        LZ_TRY(spmm_rm<T>(h, n, nnz, rp, col, val, b, t.X, b, n, Y, b));
+        const int64_t nb = n * b;
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(nb, (int64_t)256), (int64_t)h->n_cu * 16));
+        hipLaunchKernelGGL((k_rowscale_rows<T>), dim3(grid), dim3(256), 0, h->stream, nb, b, t.a, t.g, t.e, t.c, t.d, t.s,
+                           t.X, t.Z, t.U, Y);
+        LZ_LAUNCH_CHECK();
+    }
+    return dots ? col_dots<T>(h, n, b, Y, t.U, dots) : LZ_OK;
+}
+
+template int spmm_rowscale<double>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const double *, int,
+                                   RowScaleTerms<double>, double *, double *, bool, bool);
+template int spmm_rowscale<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
+                                  RowScaleTerms<float>, float *, double *, bool, bool);
 
 // The row-local pass of the two-launch residual: R[i][c] = fma(1, R[i][c], fma(-theta_c, X[i][c], 0))
 // over nb = n b contiguous elements (ld = b), the ShiftDots store's arithmetic on the stored

@@ -559,6 +559,59 @@ int lz_pcg_cheb_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_p
                       void *X, void *work, const lz_cg_opts *opts, int *iters, int *status, double *resid, double *est,
                       int *info);
 
+/* ------------- Jacobi-scaled Chebyshev preconditioner (no reference counterpart)
+ * M = A + shift I, D = diag(M), s = 1 / d as lz_csr_jacobi returns it, N = D^-1/2 M D^-1/2
+ * (unit diagonal).  z = D^-1/2 q(N) D^-1/2 r = q(D^-1 M) D^-1 r with q the polynomial of
+ * lz_cheb_precond on an enclosure [lo, hi] of N's spectrum (lzh_gershgorin_jacobi in
+ * lz_host.h gives one): symmetric positive definite whenever hi >= lambda_max(N).  For an
+ * operator whose diagonal varies and whose stencil is ill conditioned, where neither
+ * lz_pcg_solve nor lz_pcg_cheb_solve helps.  In unscaled vectors every M z of the recurrence
+ * becomes s (M z) and r becomes Rs = s r, so every step is one store of one shape:
+ *
+ * lz_csr_spmm_rowscale: Y[i] = s_i (a (A X)[i] + g X[i] + e U[i]) + c X[i] + d Z[i].
+ * s: n elements of the dtype; X, U, Z, Y: n x b row-major, ld = b; U is required, d == 0
+ * never reads Z (Z may then be NULL).  Y must not overlap X, U, Z or s: LZ_E_ARG.  Per
+ * element, in the dtype:
+ *   t = fma(a, y, fma(g, x, e u));  o = d != 0 ? fma(c, x, d z) : c x;  Y = fma(s_i, t, o)
+ * with y the finished SpMM element.  dots (2 b doubles, device; may be NULL): [Y.Y | Y.U] of
+ * the stored Y as lz_col_dots(Y, U) returns them.  Where lz_csr_spmm_axpby4_dots fuses its
+ * store this one does (lz_debug_last_kernel: the SpMM id | LZ_K_RSC, and | LZ_K_DOT when the
+ * dots leave the store too); every other shape -- and LZ_AX3=0 -- runs lz_csr_spmm, a
+ * row-local pass and lz_col_dots' kernel, the same bits in Y; LZ_AX3DOT=0: only the dots
+ * fall back. */
+int lz_csr_spmm_rowscale(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                         const void *val, lz_dtype dtype, int b, const void *s, double a, double g, const void *X,
+                         double e, const void *U, double c, double d, const void *Z, void *Y, double *dots);
+/* lz_cgz_update's pass (the same bits in R, P, S, X and rr) that also reads dinv (n
+ * elements) and writes a fifth block Rs[i][c] = dinv_i R[i][c] of the stored R, one rounded
+ * product; a frozen column's Rs is rewritten with the bits it held.  Six blocks and the
+ * n-vector read, five written.  The same two forms and switches (LZ_CG_GENERIC, LZ_CG_NT,
+ * LZ_CGZ_Z_NT); Rs is stored with non-temporal stores (LZ_CGZS_RS_NT=0, measurement: plain).
+ * The seven blocks must not overlap each other or dinv: LZ_E_ARG. */
+int lz_cgzs_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *coef, const void *dinv, void *R,
+                   const void *W, void *P, void *S, void *X, const void *Z, void *Rs, double *rr);
+/* Z = q(D^-1 M) D^-1 R in exactly `degree` SpMMs, each an lz_csr_spmm_rowscale with s = dinv
+ * and U = R: step 1 on X = Rs with (a, g, e, c, d) = (a_1, a_1 shift, c_1, 0, 0), step j >= 2
+ * on X = z_j with (a_j, a_j shift, e_j, c_j, d_j) and Z = z_{j-1} (NULL at j = 2, d_2 = 0);
+ * (a, c, d, e)_j: lzh_cheb_precond_coeffs' rows, the shift rounded once to the dtype.  Rs:
+ * the caller's dinv R, read only.  dots (2 b doubles, device; may be NULL): [Z.Z | Z.R] of the
+ * stored Z out of the last step.  R, Rs (read only), Z: n x b row-major, ld = b; work: 2 n b
+ * elements (not read on entry); dinv, R, Rs, Z and work pairwise distinct.  {work_0, work_1,
+ * Z} rotate as in lz_cheb_precond_apply.  No host synchronisation. */
+int lz_cheb_jacobi_apply(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                         const void *val, lz_dtype dtype, int b, double shift, const lz_cheb_precond *pc,
+                         const void *dinv, const void *R, const void *Rs, void *Z, void *work, double *dots);
+/* lz_pcg_cheb_solve with that preconditioner: the same arguments (dinv behind pc: n elements
+ * of the dtype, positive, as lz_pcg_solve's), options, results, stopping and restart rules
+ * and status codes, but work is 8 n b elements ([R | W | P | S | Z | T0 | T1 | Rs]).  A start
+ * after which a column is live runs one row-local launch for Rs = dinv R and then the
+ * application; each iteration one lz_cgzs_update and one lz_cheb_jacobi_apply.  info[2]
+ * (SpMMs) = (degree + 1) iterations + starts + degree (starts after which a column was live). */
+int lz_pcg_cheb_jacobi_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col,
+                             const void *val, lz_dtype dtype, int b, double shift, const lz_cheb_precond *pc,
+                             const void *dinv, const void *B, void *X, void *work, const lz_cg_opts *opts, int *iters,
+                             int *status, double *resid, double *est, int *info);
+
 /* ----------------------------- block conjugate gradients (no reference counterpart)
  * The b columns share one Krylov space: Dubrulle's BCGrQ with the symmetric
  * orthonormalisation of lz_sqrtm_pair in place of the QR.  M = A + shift I; the
@@ -834,7 +887,7 @@ int lz_debug_last_wf(lz_handle *h, int out[2]);
  * b = 32 fp32 or generic-b solve), out[1]: its last Gram / tall-skinny-product
  * launch (lz_gram, lz_sym_cross_gram, lz_tsmm and the solves that call them);
  * 0: none yet.  SpMM ids: a kernel in the low byte, or-ed with the LZ_K_WIN /
- * LZ_K_YCM / LZ_K_EPI / LZ_K_AX3 / LZ_K_DOT / LZ_K_AX4 / LZ_K_RESID flags; LZ_K_SPMV carries its lanes per row in bits 16+. */
+ * LZ_K_YCM / LZ_K_EPI / LZ_K_AX3 / LZ_K_DOT / LZ_K_AX4 / LZ_K_RESID / LZ_K_RSC flags; LZ_K_SPMV carries its lanes per row in bits 16+. */
 enum {
     LZ_K_SEG768 = 1,    /* nnz-split tiles, 768-entry stage (128-B rows, <= 13 nnz/row) */
     LZ_K_SEG1536 = 2,   /* ... 1536-entry stage (> 13 nnz/row) */
@@ -849,9 +902,10 @@ enum {
     LZ_K_YCM = 0x200,   /* column-major Y store */
     LZ_K_EPI = 0x400,   /* the beta^2 step's epilogue U = A X - Wp M */
     LZ_K_AX3 = 0x800,   /* lz_csr_spmm_axpby's fused three-term store a A X + c X + d Z */
-    LZ_K_DOT = 0x1000,  /* lz_csr_spmm_axpby_dots, _axpby4_dots (with LZ_K_AX4): the column dots leave the fused store too */
+    LZ_K_DOT = 0x1000,  /* lz_csr_spmm_axpby_dots, _axpby4_dots (with LZ_K_AX4), _rowscale (with LZ_K_RSC): the column dots leave the fused store too */
     LZ_K_AX4 = 0x2000,  /* lz_csr_spmm_axpby4: the fused store's fourth term e U (with LZ_K_AX3) */
     LZ_K_RESID = 0x4000, /* lz_csr_spmm_resid: the fused residual store A X - X diag(theta) with its dots */
+    LZ_K_RSC = 0x8000,  /* lz_csr_spmm_rowscale: the fused row-scaled store diag(s) (a A X + g X + e U) + c X + d Z */
     LZ_K_GRAM16 = 1,    /* dense ids: b = 16 MFMA Gram (fp64 and fp32) */
     LZ_K_GRAM32F = 2,   /* b = 32 fp32 MFMA Gram */
     LZ_K_GRAM_GEN = 3,  /* any b, any pitch */

@@ -138,6 +138,16 @@ int lzh_restart_coeffs_mag(int m, int b, int r, const double *T, const double *b
  * filter (lz_cheb in lz_hip.h) needs for the end of its damped interval.  fp64
  * values; n >= 1.  Returns 0, or -1 on a bad argument. */
 int lzh_gershgorin(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val, double out[2]);
+/* The same enclosure for N = D^-1/2 M D^-1/2, M = A + shift I, D = diag(M): what the
+ * Jacobi-scaled Chebyshev preconditioner (lz_cheb_jacobi_apply in lz_hip.h) needs.  N has a
+ * unit diagonal, so with s_i = 1 / d_i and rad = max_i sum_{j != i} |a_ij| sqrt(s_i s_j):
+ * out[0] = 1 - rad, out[1] = 1 + rad = max_i sum_j |m_ij| sqrt(s_i s_j).  (The Gershgorin
+ * bound of D^-1 M itself, max_i s_i sum_j |m_ij|, is useless on a varying diagonal.)  d_i:
+ * the row's stored diagonal entries summed left to right, plus the shift, as lz_csr_jacobi
+ * forms it; fp64; n >= 1, column indices in [0, n).  Returns 0, -1 on a bad argument, -2
+ * when a d_i is <= 0 or not finite. */
+int lzh_gershgorin_jacobi(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val, double shift,
+                          double out[2]);
 /* ------------------------------------------- batched conjugate gradients
  * The per-column scalar rules of lz_cg_solve (lz_hip.h), the very code its
  * one-workgroup kernels run (csrc/lz_cg.hpp), on host arrays of b entries.  State per

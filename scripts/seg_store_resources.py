@@ -15,8 +15,9 @@ SegStore enumerator.
 import re
 import sys
 
-STORES = ["Rows", "ColMajor", "Beta2", "Terms3", "Terms3Dots", "Terms4", "ShiftDots", "Terms4Dots"]
-ADDED = {"ShiftDots", "Terms4Dots"}  # stores younger than the six: a parent file need not have them
+STORES = ["Rows", "ColMajor", "Beta2", "Terms3", "Terms3Dots", "Terms4", "ShiftDots", "Terms4Dots", "RowScale",
+          "RowScaleDots"]
+ADDED = {"ShiftDots", "Terms4Dots", "RowScale", "RowScaleDots"}  # stores younger than the six: a parent file need not have them
 BOOLS = {(0, 0, 0, 0, 0): "Rows", (1, 0, 0, 0, 0): "ColMajor", (0, 1, 0, 0, 0): "Beta2", (0, 0, 1, 0, 0): "Terms3",
          (0, 0, 1, 1, 0): "Terms3Dots", (0, 0, 1, 0, 1): "Terms4"}
 HEAD = r"k_spmm_segI([fd])Li\d+ELi\d+ELi(\d+)ELb([01])ELi([01])E"
