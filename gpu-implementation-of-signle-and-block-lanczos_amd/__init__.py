@@ -60,6 +60,7 @@ TRANSPOSE_SHORT, TRANSPOSE_LDS, TRANSPOSE_SCAN_BLOCK = 16, 4096, 2048
 # of the live count
 CG_THREADS, CG_ROWS_128, CG_GRID_CAP, CG_CHECK_EVERY = 256, 32, 2048, 8
 CG_MET, CG_SPENT, CG_NOT_PD = 0, 1, 2  # Handle.solve's status per column
+MSCG_MAX_SHIFTS = 16  # Handle.solve_shifts' most shifts (csrc/lz_mscg.hpp kMscgMaxShifts)
 # lz_pcg_solve's work is PCG_WORK_BLOCKS blocks of n b elements; lz_csr_jacobi (csrc/lz_internal.hpp
 # kJacobi*) gives a row JACOBI_LANES lanes, a workgroup pass JACOBI_ROWS rows
 PCG_WORK_BLOCKS, JACOBI_LANES, JACOBI_ROWS = 5, 8, 32
@@ -158,6 +159,10 @@ HIP_SYMBOLS = [
     ("lz_cg_update", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_cg_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_vp, _c_vp, _c_vp,
                              _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    ("lz_mscg_update", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                _c_vp]),
+    ("lz_mscg_solve", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp,
+                               _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     ("lz_pcg_update", _c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                _c_vp]),
     ("lz_csr_jacobi", _c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_dbl, _c_vp, _c_vp]),
@@ -278,6 +283,8 @@ HOST_SYMBOLS = [
                                 _c_vp, _c_vp]),
     ("lzh_pcg_scalars", _c_int, [_c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                  _c_vp, _c_vp, _c_vp]),
+    ("lzh_mscg_start", _c_int, [_c_int, _c_int, _c_int] + [_c_vp] * 16),
+    ("lzh_mscg_scalars", _c_int, [_c_int, _c_int, _c_int, _c_int] + [_c_vp] * 19),
     ("lzh_gershgorin_jacobi", _c_int, [_c_i64, _c_vp, _c_vp, _c_vp, _c_dbl, _c_vp]),
     ("lzh_cheb_precond_coeffs", _c_int, [_c_int, _c_dbl, _c_dbl, _c_vp]),
     ("lzh_cheb_precond_lo", _c_dbl, [_c_int, _c_dbl]),
@@ -1613,6 +1620,80 @@ class Handle:
         if work.dim() != 1 or not work.is_contiguous() or work.numel() < blocks * n * b or work.dtype != like.dtype:
             raise LanczosError(f"{what}: work is a flat contiguous tensor of {blocks}*n*b elements of B's dtype")
         return work
+
+    def mscg_update(self, coef, live, R, W, S, P, X, rr=None):
+        """The row-local pass of one multi-shift conjugate-gradient step (lz_mscg_update): for every
+        shift k with live[k] != 0 and a_k != 0, P_k = zeta_k R + b_k P_k and X_k += a_k P_k (the old R,
+        each element finished as one fma), then cg_update's S = W + beta S, R -= alpha S and rr.  coef:
+        (2 + 3 s) b fp64 on the device, [alpha | beta | zeta_0 | a_0 | b_0 | zeta_1 | ...]; live: s
+        int32 on the device; R, W (read only), S: (n, b); P, X: (s, n, b); all contiguous, of one
+        dtype, pairwise distinct, s <= MSCG_MAX_SHIFTS.  A shift that is not live is neither read nor
+        written; a_k == 0 leaves its column of P_k and X_k bit for bit.  Returns rr."""
+        torch = _torch()
+        n, b = R.shape
+        for t in (R, W, S):
+            if tuple(t.shape) != (n, b) or t.dtype != R.dtype or not t.is_contiguous():
+                raise LanczosError("mscg_update: R, W, S (n, b) contiguous (ld = b), of one dtype")
+        s = P.shape[0] if P.dim() == 3 else -1
+        for t in (P, X):
+            if t.dim() != 3 or tuple(t.shape) != (s, n, b) or t.dtype != R.dtype or not t.is_contiguous():
+                raise LanczosError("mscg_update: P, X (s, n, b) contiguous, of R's dtype")
+        if not 1 <= s <= MSCG_MAX_SHIFTS:
+            raise LanczosError(f"mscg_update: 1 <= s <= {MSCG_MAX_SHIFTS}")
+        if coef.dtype != torch.float64 or not coef.is_contiguous() or coef.numel() != (2 + 3 * s) * b:
+            raise LanczosError("mscg_update: coef is a contiguous fp64 tensor of (2 + 3 s) b elements")
+        if live.dtype != torch.int32 or not live.is_contiguous() or live.numel() != s:
+            raise LanczosError("mscg_update: live is a contiguous int32 tensor of s elements")
+        if rr is None:
+            rr = torch.empty(b, dtype=torch.float64, device=R.device)
+        if rr.dtype != torch.float64 or not rr.is_contiguous() or rr.numel() != b:
+            raise LanczosError("mscg_update: rr is a contiguous fp64 tensor of b elements")
+        _check(self.L.lz_mscg_update(self.ptr, n, b, _dt(R), s, _ptr(coef), _ptr(live), _ptr(R), _ptr(W), _ptr(S),
+                                     _ptr(P), _ptr(X), _ptr(rr)), "lz_mscg_update")
+        return rr
+
+    def solve_shifts(self, A: CsrDevice, B, shifts, tol: Optional[float] = None, max_iter: Optional[int] = None,
+                     check_every: Optional[int] = None, max_restarts: int = 3, work=None) -> dict:
+        """Solve (A + shifts[k] I) X_k = B for every shift by multi-shift conjugate gradients
+        (lz_mscg_solve): one SpMM per iteration for all s <= MSCG_MAX_SHIFTS shifts and b <= 64
+        columns.  Conjugate gradients run on the smallest shift, the seed; every other shift takes
+        its solution from the seed's residual by three scalars per column.  Then every shift's
+        residual is measured and a shift that missed tol is polished by solve's plain conjugate
+        gradients (the finishing phase), so status 0 is a measured residual as in solve.
+        tol, max_iter, check_every, max_restarts: solve's, with its defaults.  work: (3 + s) n b
+        elements, [R | W | S | P_0 .. P_{s-1}].  No preconditioner and no start block; the seed's
+        operator must be positive definite for the shared phase to help.
+        Returns a dict: X (s, n, b) in the caller's shift order; iters (the shared phase's),
+        finish_iters (the polish's), status, converged, resid (the finishing phase's), est (the shared
+        phase's) as (s, b) arrays; iterations (shared, enqueued), n_spmm (all), finished (pairs with
+        finish_iters > 0), restarts (the finishing phase's) and seed (the index of the smallest
+        shift)."""
+        torch = _torch()
+        n, b = self._blocks("solve_shifts", A, B)
+        try:
+            sh = np.ascontiguousarray(np.asarray(shifts, np.float64).reshape(-1))
+        except (TypeError, ValueError):
+            raise LanczosError("solve_shifts: shifts is a sequence of numbers")
+        s = int(sh.size)
+        if not 1 <= s <= MSCG_MAX_SHIFTS:
+            raise LanczosError(f"solve_shifts: 1 <= len(shifts) <= {MSCG_MAX_SHIFTS}")
+        f64 = A.val.dtype == torch.float64
+        tol = (1e-10 if f64 else 1e-4) if tol is None else float(tol)
+        max_iter = min(10 * n, 10000) if max_iter is None else int(max_iter)
+        work = self._work4("solve_shifts", work, n, b, B, 3 + s)
+        if check_every is not None and check_every < 1:
+            raise LanczosError("solve_shifts: check_every >= 1")
+        opts = CgOpts(tol, max_iter, 0 if check_every is None else int(check_every), int(max_restarts))
+        X = torch.empty(s, n, b, dtype=B.dtype, device=B.device)
+        iters, fin, status = (np.zeros((s, b), np.int32) for _ in range(3))
+        resid, est, info = np.zeros((s, b)), np.zeros((s, b)), np.zeros(4, np.int32)
+        _check(self.L.lz_mscg_solve(self.ptr, n, A.nnz, _ptr(A.row_ptr), _ptr(A.col), _ptr(A.val), A.dtype, b, s,
+                                    _p(sh), _ptr(B), _ptr(X), _ptr(work), ctypes.addressof(opts), _p(iters), _p(fin),
+                                    _p(status), _p(resid), _p(est), _p(info)), "lz_mscg_solve")
+        rounded = sh.astype(np.float64 if f64 else np.float32)
+        return {"X": X, "iters": iters, "finish_iters": fin, "status": status, "converged": status == 0,
+                "resid": resid, "est": est, "iterations": int(info[0]), "n_spmm": int(info[1]),
+                "finished": int(info[2]), "restarts": int(info[3]), "seed": int(np.argmin(rounded))}
 
     def spectral_moments(self, A: CsrDevice, n_moments: int = 257, probes: Optional[int] = None,
                          b: Optional[int] = None, bounds=None, pad: float = 0.01, seed: int = 0,

@@ -13,6 +13,7 @@
 #include "lz_common.hpp"
 #include "lz_internal.hpp"
 #include "lz_kernels.hpp"
+#include "lz_mscg.hpp"
 
 namespace lz {
 
@@ -1791,6 +1792,7 @@ int lz_finalize(lz_handle *h)
     (void)hipFree(h->dots_ws);
     (void)hipFree(h->cg_ws);
     (void)hipFree(h->bcg_ws);
+    (void)hipFree(h->mscg_ws);
     (void)hipFree(h->ybuf);
     (void)hipFree(h->coef);
     (void)hipFree(h->tr_ws);
@@ -1871,6 +1873,7 @@ int lz_debug_poison_lds(lz_handle *h, uint32_t pattern)
     if (h->dots_ws) LZ_HIP_TRY(hipMemsetAsync(h->dots_ws, byte, h->dots_cap, h->stream));
     if (h->cg_ws) LZ_HIP_TRY(hipMemsetAsync(h->cg_ws, byte, h->cg_cap, h->stream));
     if (h->bcg_ws) LZ_HIP_TRY(hipMemsetAsync(h->bcg_ws, byte, h->bcg_cap, h->stream));
+    if (h->mscg_ws) LZ_HIP_TRY(hipMemsetAsync(h->mscg_ws, byte, h->mscg_cap, h->stream));
     return LZ_OK;
 }
 
@@ -2281,6 +2284,47 @@ int lz_cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const i
 {
     return krylov_entry(h, n, nnz, rp, col, val, dtype, b, kMaxB, shift, B, X, work, opts, iters, status, resid, est, info,
                         cg_solve_with(nullptr));
+}
+
+int lz_mscg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, int s, const double *coef, const int *live, void *R,
+                   const void *W, void *S, void *P, void *X, double *rr)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
+    LZ_ARG_CHECK(s >= 1 && s <= kMscgMaxShifts, "s in [1,16]");
+    LZ_ARG_CHECK(coef && live && R && W && S && P && X && rr, "coef/live/R/W/S/P/X/rr NULL");
+    const int64_t nb = n * b;
+    LZ_ARG_CHECK(pairwise_apart({span_of(R, nb, dtype), span_of(W, nb, dtype), span_of(S, nb, dtype),
+                                 span_of(P, s * nb, dtype), span_of(X, s * nb, dtype)}),
+                 "R, W, S, P and X must be pairwise distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return mscg_update<T>(h, n, b, s, coef, live, (T *)R, (const T *)W, (T *)S, (T *)P, (T *)X, rr);
+    });
+}
+
+int lz_mscg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const void *val,
+                  lz_dtype dtype, int b, int s, const double *shifts, const void *B, void *X, void *work,
+                  const lz_cg_opts *opts, int *iters, int *finish_iters, int *status, double *resid, double *est,
+                  int *info)
+{
+    LZ_HANDLE_CHECK(h);
+    LZ_TRY(check_csr(n, nnz, rp, col, val));
+    LZ_TRY(shape_args(dtype, n, 1, b, kMaxB));
+    LZ_ARG_CHECK(s >= 1 && s <= kMscgMaxShifts, "s in [1,16]");
+    LZ_ARG_CHECK(shifts && B && X && work && opts && iters && finish_iters && status && resid && est && info,
+                 "NULL argument");
+    LZ_ARG_CHECK(opts->tol > 0.0 && std::isfinite(opts->tol), "tol > 0 and finite");
+    for (int k = 0; k < s; ++k) LZ_ARG_CHECK(std::isfinite(shifts[k]), "every shift finite");
+    LZ_ARG_CHECK(opts->max_iter >= 0 && opts->max_restarts >= 0, "max_iter, max_restarts >= 0");
+    const int64_t nb = n * b;
+    LZ_ARG_CHECK(pairwise_apart({span_of(B, nb, dtype), span_of(X, s * nb, dtype), span_of(work, (3 + s) * nb, dtype)}),
+                 "B, X and work must be pairwise distinct");
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return mscg_solve<T>(h, n, nnz, rp, col, (const T *)val, b, s, shifts, (const T *)B, (T *)X, (T *)work, *opts,
+                             iters, finish_iters, status, resid, est, info);
+    });
 }
 
 int lz_pcg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, const double *coef, const void *dinv, void *R,

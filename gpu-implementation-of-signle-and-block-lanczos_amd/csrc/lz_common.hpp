@@ -136,6 +136,8 @@ struct lz_handle {
     size_t cg_cap = 0;            // bytes
     void *bcg_ws = nullptr;       // lz_bcg_solve: the control word and the b x b matrices of the rules (lz_bcg.hip)
     size_t bcg_cap = 0;           // bytes
+    void *mscg_ws = nullptr;      // lz_mscg_solve: the shared phase's state, coefficients and live counts (lz_mscg.hip)
+    size_t mscg_cap = 0;          // bytes
     // optional per-kernel-class timing with hipEvents on the handle's stream
     // (lz_prof_enable / lz_prof_read): events recorded around each launch of
     // the class, elapsed times summed at read time.

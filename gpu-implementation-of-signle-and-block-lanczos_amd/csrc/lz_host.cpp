@@ -7,6 +7,7 @@
 #include "lz_bcg.hpp"
 #include "lz_cg.hpp"
 #include "lz_minres.hpp"
+#include "lz_mscg.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -789,6 +790,71 @@ int lzh_pcg_scalars(int b, int first, int max_iter, const double *rz, const doub
         live[c] = s.live, iters[c] = s.iters, status[c] = s.status;
         *nlive += s.live;
     }
+    return 0;
+}
+
+// ---- multi-shift conjugate gradients: the rules of lz_mscg.hpp, as k_mscg_start and
+// k_mscg_scalars apply them, on host arrays (seed state: b entries; pair state: s x b row-major)
+static void mscg_live_counts(int b, int s, const int *live, const int *plive, int *live_s, int *nlive)
+{
+    *nlive = 0;
+    for (int c = 0; c < b; ++c) *nlive += live[c];
+    for (int k = 0; k < s; ++k) {
+        live_s[k] = 0;
+        for (int c = 0; c < b; ++c) live_s[k] += plive[(size_t)k * b + c];
+    }
+}
+
+int lzh_mscg_start(int b, int s, int max_iter, const double *gamma, const double *thr, double *gamma_prev,
+                   double *alpha_prev, double *est2, int *live, int *iters, int *status, double *zeta,
+                   double *zeta_prev, double *pest2, int *plive, int *piters, int *pstatus, int *live_s, int *nlive)
+{
+    if (b < 1 || s < 1 || s > lz::kMscgMaxShifts || !gamma || !thr || !gamma_prev || !alpha_prev || !est2 || !live ||
+        !iters || !status || !zeta || !zeta_prev || !pest2 || !plive || !piters || !pstatus || !live_s || !nlive)
+        return -1;
+    for (int c = 0; c < b; ++c) {
+        lz::CgCol sd{gamma_prev[c], alpha_prev[c], est2[c], live[c], iters[c], status[c]};
+        lz::cg_start_rule(gamma[c], gamma[c], thr[c], max_iter, true, sd);
+        gamma_prev[c] = sd.gamma_prev, alpha_prev[c] = sd.alpha_prev, est2[c] = sd.est2;
+        live[c] = sd.live, iters[c] = sd.iters, status[c] = sd.status;
+        for (int k = 0; k < s; ++k) {
+            const size_t i = (size_t)k * b + c;
+            lz::MscgPair p;
+            lz::mscg_start_rule(gamma[c], sd, p);
+            zeta[i] = p.zeta, zeta_prev[i] = p.zeta_prev, pest2[i] = p.est2;
+            plive[i] = p.live, piters[i] = p.iters, pstatus[i] = p.status;
+        }
+    }
+    mscg_live_counts(b, s, live, plive, live_s, nlive);
+    return 0;
+}
+
+int lzh_mscg_scalars(int b, int s, int first, int max_iter, const double *delta, const double *rr, const double *dlt,
+                     const double *thr, double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters,
+                     int *status, double *zeta, double *zeta_prev, double *pest2, int *plive, int *piters, int *pstatus,
+                     double *coef, int *live_s, int *nlive)
+{
+    if (b < 1 || s < 1 || s > lz::kMscgMaxShifts || !delta || !rr || !dlt || !thr || !gamma_prev || !alpha_prev ||
+        !est2 || !live || !iters || !status || !zeta || !zeta_prev || !pest2 || !plive || !piters || !pstatus || !coef ||
+        !live_s || !nlive)
+        return -1;
+    for (int c = 0; c < b; ++c) {
+        lz::CgCol sd{gamma_prev[c], alpha_prev[c], est2[c], live[c], iters[c], status[c]};
+        lz::MscgPair pair[lz::kMscgMaxShifts];
+        for (int k = 0; k < s; ++k) {
+            const size_t i = (size_t)k * b + c;
+            pair[k] = {zeta[i], zeta_prev[i], pest2[i], plive[i], piters[i], pstatus[i]};
+        }
+        lz::mscg_column_step(b, c, s, delta, rr[c], dlt[c], thr[c], first != 0, max_iter, sd, pair, 1, coef);
+        gamma_prev[c] = sd.gamma_prev, alpha_prev[c] = sd.alpha_prev, est2[c] = sd.est2;
+        live[c] = sd.live, iters[c] = sd.iters, status[c] = sd.status;
+        for (int k = 0; k < s; ++k) {
+            const size_t i = (size_t)k * b + c;
+            zeta[i] = pair[k].zeta, zeta_prev[i] = pair[k].zeta_prev, pest2[i] = pair[k].est2;
+            plive[i] = pair[k].live, piters[i] = pair[k].iters, pstatus[i] = pair[k].status;
+        }
+    }
+    mscg_live_counts(b, s, live, plive, live_s, nlive);
     return 0;
 }
 

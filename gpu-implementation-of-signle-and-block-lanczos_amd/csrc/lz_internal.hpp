@@ -1,5 +1,7 @@
 // lz_internal.hpp -- internal (C++) entry points between the .hip units.
 #pragma once
+#include <initializer_list>
+
 #include "lz_common.hpp"
 
 namespace lz {
@@ -63,6 +65,12 @@ int spmm_rowscale(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const
 template <typename T>
 int spmm_resid(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
                const double *theta, const T *X, T *R, double *dots, bool fused = true);
+// dots = [Y.Y | Y.X] with the bits spmm_terms' dots would have had, had a three-term step just
+// stored Y beside X (also: that step's further blocks, for its alignment test): the fused
+// store's order at its shapes, else col_dots.  Two block streams, no operator.
+template <typename T>
+int store_order_dots(lz_handle *h, int64_t n, int b, const T *Y, const T *X, std::initializer_list<const void *> also,
+                     double *dots);
 template <typename T>
 int spmm_cm(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
             const T *X, int64_t ldx, int64_t nx, T *Y, int64_t ldy);  // nx: rows of X
@@ -124,6 +132,19 @@ template <typename T>
 int cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b,
              double shift, const T *dinv, const lz_cheb_precond *pc, const T *B, T *X, T *work, const lz_cg_opts &o,
              int *iters, int *status, double *resid, double *est, int *info);
+// ---- multi-shift conjugate gradients (lz_mscg.hip): k_mscg_update runs
+// k_cg_update's shapes (kCgThreads, kCgRows128, kCgGridCap; one slab of b doubles per block).
+// The solve's work: 3 + s blocks, [R | W | S | P_0 .. P_{s-1}]; at most kMscgMaxShifts shifts
+// (lz_mscg.hpp).
+// lz_mscg_update (include/lz_hip.h)
+template <typename T>
+int mscg_update(lz_handle *h, int64_t n, int b, int s, const double *coef, const int *live, T *R, const T *W, T *S,
+                T *P, T *X, double *rr);
+// lz_mscg_solve (include/lz_hip.h)
+template <typename T>
+int mscg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *rp, const int32_t *col, const T *val, int b, int s,
+               const double *shifts, const T *B, T *X, T *work, const lz_cg_opts &o, int *iters, int *finish_iters,
+               int *status, double *resid, double *est, int *info);
 // ---- batched MINRES (lz_minres.hip): k_minres_update runs k_cg_update's
 // shapes (kCgThreads, kCgRows128, kCgGridCap; one slab of b doubles per block).
 // The solve's work: kMinresWorkBlocks blocks, [U0 | U1 | W | D0 | D1].

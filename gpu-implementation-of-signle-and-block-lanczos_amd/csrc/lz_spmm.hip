@@ -2069,6 +2069,57 @@ template int spmm_terms<double>(lz_handle *, int64_t, int64_t, const int64_t *, 
 template int spmm_terms<float>(lz_handle *, int64_t, int64_t, const int64_t *, const int32_t *, const float *, int,
                                SpmmTerms<float>, float *, double *, bool, bool);
 
+// The column dots [Y.Y | Y.X] of two stored blocks in the order of k_spmm_seg's Terms3Dots
+// store: tile q = rows 48 q .. 48 q + 47, lane t adds pieces t, t + 256 of the tile (piece = LPR
+// row + column piece) through the store's own DotAcc, dot_slab leaves the tile's slab.  No
+// operator is read: two block streams.
+template <typename T, int B>
+__global__ __launch_bounds__(256) void k_store_order_dots(int64_t n, const T *__restrict__ Y, const T *__restrict__ X,
+                                                          double *__restrict__ slabs)
+{
+    using S = SpmmShape<T, B>;
+    constexpr int VEC = S::VEC, LPR = S::LPR, TR = 48;
+    __shared__ double red[8 * B];
+    const int64_t r0 = (int64_t)blockIdx.x * TR;
+    const int nrows = n - r0 < TR ? (int)(n - r0) : TR;
+    DotAcc<T, VEC> d;
+    d.clear();
+    for (int idx = threadIdx.x; idx < nrows * LPR; idx += 256) {
+        const int64_t off = (r0 + idx / LPR) * B + (idx % LPR) * VEC;
+        d.add(ldv<T, VEC>(Y + off), ldv<T, VEC>(X + off));
+    }
+    dot_slab<T, B, VEC>(d, red, slabs + (int64_t)blockIdx.x * (2 * B));
+}
+
+// dots = [Y.Y | Y.X] with the bits spmm_terms' dots would have had, had a three-term step just
+// stored Y beside X: at the shapes whose dots leave the fused store (128-B rows under 2 GiB,
+// every block on 16 bytes -- also: that step's further blocks, to test) the store's order,
+// else col_dots.  For a solver that starts from a block it did not compute by an SpMM and must
+// agree bit for bit with one that did.
+template <typename T>
+int store_order_dots(lz_handle *h, int64_t n, int b, const T *Y, const T *X, std::initializer_list<const void *> also,
+                     double *dots)
+{
+    if (n <= 0) return LZ_OK;
+    const bool rows128 = (int64_t)b * (int64_t)sizeof(T) == 128;
+    const bool buf_ok = n * b * (int64_t)sizeof(T) < (1LL << 31) && n < (1 << 24);
+    uintptr_t bits = reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(X);
+    for (const void *p : also) bits |= reinterpret_cast<uintptr_t>(p);
+    const bool al16 = (bits & 15) == 0;
+    const char *fz = getenv("LZ_SPMM_FNZ");
+    if (!(rows128 && buf_ok && al16 && !(fz && fz[0] == '1'))) return col_dots<T>(h, n, b, Y, X, dots);
+    constexpr int B = 128 / (int)sizeof(T);
+    LZ_TRY(dots_reserve(h, n, b));
+    const int64_t tiles = ceil_div(n, (int64_t)48);
+    hipLaunchKernelGGL((k_store_order_dots<T, B>), dim3((unsigned)tiles), dim3(256), 0, h->stream, n, Y, X, h->dots_ws);
+    LZ_LAUNCH_CHECK();
+    return dots_fold(h, tiles, b, dots);
+}
+template int store_order_dots<double>(lz_handle *, int64_t, int, const double *, const double *,
+                                      std::initializer_list<const void *>, double *);
+template int store_order_dots<float>(lz_handle *, int64_t, int, const float *, const float *,
+                                     std::initializer_list<const void *>, double *);
+
 // The row-local pass of the two-launch row-scaled step: rowscale_piece's arithmetic on the
 // stored SpMM row, over n rows of b contiguous elements (ld = b), 64-bit indices; Z ==
 // nullptr: d == 0, and Z is not read.

@@ -458,6 +458,51 @@ int lz_cg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, co
                 lz_dtype dtype, int b, double shift, const void *B, void *X, void *work, const lz_cg_opts *opts,
                 int *iters, int *status, double *resid, double *est, int *info);
 
+/* ------------- multi-shift conjugate gradients (no reference counterpart)
+ * (A + sigma_k I) X_k = B for s shifts of one operator, 1 <= s <= 16, by one Krylov space:
+ * conjugate gradients run on the seed system, the smallest shift, and every other shift's
+ * residual is zeta_k r, r the seed's (csrc/lz_mscg.hpp has the scalar rules).
+ *
+ * lz_mscg_update: lz_cg_update's pass for the seed with every live shift's update in front of
+ * it.  coef: (2 + 3 s) b device doubles, [alpha | beta | zeta_0 | a_0 | b_0 | zeta_1 | ...], b
+ * each, rounded once to the blocks' dtype; live: s device ints; R, W (read only), S: n x b
+ * row-major with ld = b; P and X: s contiguous n x b blocks each, in the caller's shift order.
+ * Per element, for each shift k with live[k] != 0 and a_k != 0:
+ *   t = zeta_k r (the old r, one rounded product),  P_k = b_k == 0 ? t : fma(b_k, P_k, t),
+ *   X_k = fma(a_k, P_k, X_k);
+ * a_k == 0 leaves that column of P_k and X_k bit for bit; a shift with live[k] == 0 is skipped
+ * whole, nothing of P_k or X_k read or written whatever its coefficients say.  Then
+ *   S = beta == 0 ? W : fma(beta, S, W),  R = alpha == 0 ? R : fma(-alpha, S, R)
+ * and rr[c] = sum_i R[i][c]^2 of the stored R as lz_cg_update sums it.  With s = 1 and coef =
+ * [alpha | beta | 1 | alpha | beta] it stores lz_cg_update's bits in R, S, X_0, rr and the live
+ * columns' P_0.  3 + 2 (live shifts) blocks read, 2 + 2 (live shifts) written; lz_cg_update's two
+ * forms and its LZ_CG_GENERIC / LZ_CG_NT switches (P_k, X_k, S, W non-temporal, R plain).  R, W,
+ * S, P and X must not overlap: LZ_E_ARG. */
+int lz_mscg_update(lz_handle *h, int64_t n, int b, lz_dtype dtype, int s, const double *coef, const int *live, void *R,
+                   const void *W, void *S, void *P, void *X, double *rr);
+/* The solve.  shifts: s host doubles, each rounded once to the dtype; B: n x b (read only); X:
+ * s n b elements, written (X_k the solution at shifts[k]; the start is zero); work: (3 + s) n b
+ * elements, [R | W | S | P_0 .. P_{s-1}], not read on entry.  s outside [1,16], b outside [1,64],
+ * overlapping B / X / work, tol <= 0 or a shift that is not finite: LZ_E_ARG.
+ * Shared phase: X = 0, R = B; per iteration one lz_csr_spmm_axpby_dots (W = (A + min shift) R),
+ * one one-workgroup launch for all scalars, one lz_mscg_update; one 4-byte read of the seed's live
+ * count per check_every iterations.  A (shift, column) pair is frozen once zeta_k^2 r.r reaches
+ * tol^2 |B_c|^2, when its seed column stops, or when its zeta recurrence breaks down; a shift
+ * none of whose pairs is live no longer moves.  No restart: the residuals must stay collinear.
+ * Finishing phase: lz_cg_solve's solver on every shift in turn from the X_k just produced, with
+ * max(0, max_iter - the shift's most shared iterations) iterations and max_restarts: a shift
+ * that is there costs one SpMM, the measurement; one that missed is polished by plain
+ * conjugate gradients (so is every shift at which A + sigma_k I is positive definite when the
+ * seed's operator is not).
+ * On the host, s x b row-major each: iters (the shared phase's), finish_iters (the polish's),
+ * status and resid (the finishing phase's, lz_cg_solve's codes), est (sqrt(zeta^2 r.r) / |B_c|
+ * of the shared phase); info[4] = {shared iterations enqueued, SpMMs in all, pairs with
+ * finish_iters > 0, finishing restarts}. */
+int lz_mscg_solve(lz_handle *h, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const void *val,
+                  lz_dtype dtype, int b, int s, const double *shifts, const void *B, void *X, void *work,
+                  const lz_cg_opts *opts, int *iters, int *finish_iters, int *status, double *resid, double *est,
+                  int *info);
+
 /* ------------- diagonally preconditioned conjugate gradients (no reference counterpart)
  * lz_cg_solve's method with z = D^-1 r, D^-1 = diag(dinv), per column:
  *   gamma = r.z, rho = r.r, delta = (M z).z, beta = gamma / gamma_prev,

@@ -182,6 +182,34 @@ int lzh_cg_scalars(int b, int first, int max_iter, const double *gamma, const do
 int lzh_pcg_scalars(int b, int first, int max_iter, const double *rz, const double *rr, const double *delta,
                     const double *thr, double *gamma_prev, double *alpha_prev, double *est2, int *live, int *iters,
                     int *status, double *coef, int *nlive);
+/* ------------------------------------------- multi-shift conjugate gradients
+ * The scalar rules of lz_mscg_solve's shared phase (lz_hip.h), the very code its
+ * one-workgroup kernels run (csrc/lz_mscg.hpp), on host arrays.  The seed column's state
+ * is lzh_cg_scalars' (b entries each); a (shift, column) pair's state is zeta, zeta_prev
+ * (both 1 at the start), pest2 (zeta^2 r.r when it froze), plive, piters, pstatus, s x b
+ * row-major each, 1 <= s <= 16.  live_s[k]: shift k's live pairs; *nlive: the seed's live
+ * columns.  Both return 0, or -1 on a bad argument.
+ *
+ * lzh_mscg_start: gamma[c] = |B_c|^2 (R = B), thr[c] = tol^2 |B_c|^2.  The seed's initial
+ * lzh_cg_start; a pair is live where its seed column is.
+ * lzh_mscg_scalars: one iteration.  dshift[k] = sigma_k - sigma_seed >= 0 (s entries),
+ * rr[c] = R_c.R_c of the seed's recurrence, delta[c] = (M R_c).R_c.  The seed's
+ * lzh_cg_scalars step gives alpha, beta; alpha_prev is the seed's before that step, 1
+ * when first.  Per pair, in this order: not live -- (zeta, a, b) = (0, 0, 0), state
+ * untouched; alpha == 0 (the seed column froze or broke down) -- frozen, pest2 = zeta^2
+ * rr, status 1, or 2 with the seed's status 2; zeta^2 rr <= thr -- frozen, pest2 = zeta^2
+ * rr; else zeta_new = zeta zeta_prev alpha_prev / (alpha beta (zeta_prev - zeta) +
+ * zeta_prev alpha_prev (1 + dshift alpha)), a zero or non-finite denominator or a
+ * non-finite zeta_new -- frozen, status 2; else the step emits zeta, a = alpha zeta_new /
+ * zeta, b = beta (zeta / zeta_prev)^2, then zeta_prev = zeta, zeta = zeta_new, piters +=
+ * 1.  coef: (2 + 3 s) b doubles, [alpha | beta | zeta_0 | a_0 | b_0 | zeta_1 | ...]. */
+int lzh_mscg_start(int b, int s, int max_iter, const double *gamma, const double *thr, double *gamma_prev,
+                   double *alpha_prev, double *est2, int *live, int *iters, int *status, double *zeta,
+                   double *zeta_prev, double *pest2, int *plive, int *piters, int *pstatus, int *live_s, int *nlive);
+int lzh_mscg_scalars(int b, int s, int first, int max_iter, const double *dshift, const double *rr,
+                     const double *delta, const double *thr, double *gamma_prev, double *alpha_prev, double *est2,
+                     int *live, int *iters, int *status, double *zeta, double *zeta_prev, double *pest2, int *plive,
+                     int *piters, int *pstatus, double *coef, int *live_s, int *nlive);
 /* The steps of the Chebyshev polynomial preconditioner z = q(M) r (lz_cheb_precond in
  * lz_hip.h), the numbers lz_cheb_precond_apply uses: with theta = (hi + lo) / 2, delta =
  * (hi - lo) / 2, sigma_1 = theta / delta, rho_0 = 1 / sigma_1, rho_j = 1 / (2 sigma_1 -
